@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: frames/s end-to-end (detect + refine + uplift) on synthetic 1280x720 video.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--ops-json FILE]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one pass of the hot path over one stream batch that is already resident in HBM:
@@ -55,7 +55,31 @@ def parse():
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-certify', action='store_true', help='plain bf16 argmax (no fp32 re-evaluation of near-ties)')
     ap.add_argument('--no-extras', action='store_true', help='skip the config 2/3/5 legs (cnn-only, uplift-only, generator)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the records of the last timed step (all ranks, rank order) as DIR/<key>.npy')
+    ap.add_argument('--ops-json', metavar='FILE', help='write the per-op timings behind `roofline` to FILE (nothing is written into the source tree)')
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(gathered, out_dir):
+    """The records the timed path handed to its caller in its last step ({key: [tensor of rank 0, rank 1, ...]}), one DIR/<key>.npy
+    per key with the ranks' rows concatenated: float32 stays float32, everything else (xyv float64, n_valid int64) becomes float64.
+    The inputs are seeded (weights seed 0, clip seed = rank), so two builds run with the same flags can be compared file for file."""
+    arrays = {}
+    for k, per_rank in gathered.items():
+        a = np.concatenate([t.detach().cpu().numpy() for t in per_rank])
+        arrays[k] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit('bench.py: --dump-outputs would write %d bytes (limit %d)' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
 
 
 class Pipeline:
@@ -715,6 +739,10 @@ def spawn_ranks(a):
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(a.gpus), '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.abspath(__file__), '--gpus', str(a.gpus), '--steps', str(a.steps), '--warmup', str(a.warmup)]
     cmd += ['--no-cpu-baseline'] * a.no_cpu_baseline + ['--no-roofline'] * a.no_roofline + ['--no-extras'] * a.no_extras + ['--no-certify'] * a.no_certify
+    if a.dump_outputs:
+        cmd += ['--dump-outputs', os.path.abspath(a.dump_outputs)]
+    if a.ops_json:
+        cmd += ['--ops-json', os.path.abspath(a.ops_json)]
     env = dict(os.environ)
     env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
     env.setdefault('OMP_NUM_THREADS', str(max(1, min(8, (os.cpu_count() or 8) // max(1, a.gpus)))))
@@ -863,6 +891,8 @@ def main():
                     'gather_ms_max': [round(float(v) * 1e3, 3) for v in allr[:, 3]],
                     'note': 'ms_per_step = each rank\'s own K steps up to its last synchronize (before the closing barrier); gather = host wall clock of '
                             'gather_records (pack + all_gather_into_tensor + unpack on rank 0), which also absorbs the wait for the slowest rank of the step'}
+    if a.dump_outputs and rank == 0:          # after the timed region, before any later leg reuses the worker
+        dump_outputs(gathered, a.dump_outputs)
     # stream -> hardware-queue grouping of every rank's worker (after the timed region, one rank at a time: ranks that share a
     # GPU in a dry run would disturb each other's probes): the single-GPU mapping is the best one seen and every
     # rank should have it -- an N-GPU line then says so itself
@@ -955,9 +985,9 @@ def main():
                 line['peaks_measured'] = {'error': repr(e)[:300]}
             line['cnn_gflop_per_frame'] = GFLOP_PER_FRAME_EXECUTED
             line['cnn_tflops_end_to_end'] = round(frames / dt * GFLOP_PER_FRAME_EXECUTED / 1e3, 2)
-            os.makedirs(os.path.join(ROOT, 'gpurun_out'), exist_ok=True)
-            with open(os.path.join(ROOT, 'gpurun_out', 'bench_ops.json'), 'w') as f:
-                json.dump(ops, f, indent=1)
+            if a.ops_json:
+                with open(a.ops_json, 'w') as f:
+                    json.dump(ops, f, indent=1)
         if not a.no_extras and world == 1:
             del pipe
             torch.cuda.empty_cache()

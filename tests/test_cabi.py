@@ -175,6 +175,14 @@ def test_bench_refuses_more_ranks_than_gpus():
     assert r.returncode == 2 and 'only' in r.stderr and not r.stdout.strip()
 
 
+def test_bench_refuses_zero_steps():
+    """`--steps` is the number of timed steps and `ms_per_step` divides by it: fewer than one is refused before anything else runs."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and '--steps' in r.stderr and not r.stdout.strip()
+
+
 def test_blob_layout_roundtrip():
     sd = weights.random_wasb_state_dict(3)
     blob = weights.pack_wasb_blob(sd)
