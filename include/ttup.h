@@ -189,9 +189,10 @@ int ttup_wasb_certify_margins(ttup_wasb* net, int batch, float* margin_dev, void
  * passes; heatmaps beyond the budget are flagged 2 (64: 128 since ABI 103, TTUP_CERT_CH) */
 int ttup_wasb_certify_budget(ttup_wasb* net, int max_crops);
 /* running counters of the handle since creation / the last reset, copied to TWELVE long longs on the host (synchronises): [0] heatmaps,
- * [1] single candidate, [2] resolved on fp32 crops, [3] not certified (= [8] + [9] + [10]), [4] crops, [5] candidates of the resolved
- * heatmaps, [6] low word = bits of the largest |bf16 - fp32| seen at a candidate, [7] single-candidate heatmaps that got a crop
- * (exact-window mode / audit crops), [8] not certified: candidate list overflow, [9]: more crops than one heatmap / frame may add,
+ * [1] single candidate (status 0, audit picks included), [2] resolved on fp32 crops (status 1), [3] not certified (status 2, = [8] + [9]
+ * + [10]; [1] + [2] + [3] = [0]), [4] crops, [5] candidates of the resolved heatmaps, [6] low word = bits of the largest |bf16 - fp32|
+ * seen at a candidate, [7] single-candidate heatmaps whose crop was kept (exact-window mode / audit crops; one dropped for lack of
+ * room is not counted), [8] not certified: candidate list overflow, [9]: more crops than one heatmap / frame may add,
  * [10]: the call's crop list was full, [11] crops of class 2 among [4] (candidates within a 14-position core: pruned to a smaller cone;
  * ABI 103).  (ABI version 100 copied eight.) */
 int ttup_wasb_certify_stats(ttup_wasb* net, long long* out_host12, int reset);

@@ -1,0 +1,339 @@
+"""The certified argmax at the limits of its budgets (csrc/certify.hip, cert_plan_kernel) on the MI355X box (-m gpu).
+
+A heatmap whose candidates do not fit -- more than K candidates, more new crops than `max_crops_per_map` (or than the frame's
+`maxf = min(maxc * C, 32)`), or a call whose crop list is full -- is flagged 2 and repaired on the full-frame fp32 path.  These
+tests drive the ball (C = 1) and the table detector (C = 13, the channels of a frame share its crops) through every one of those
+branches, with and without exact windows and audit crops, on 640x352 frames with blobs in the corners and on the edges (crops
+clamped against the image borders), and compare every result with the full-frame fp32 path -- which the goldens pin to the
+reference's own argmax.  Each case asserts the premise it was built for: a case that does not reach its branch fails."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import has_gpu
+from upliftingtabletennis_amd import synth, weights
+
+pytestmark = pytest.mark.gpu
+if has_gpu():
+    from upliftingtabletennis_amd import wasb
+
+W, H = 640, 352
+K_CAND = 256                  # candidates kept per heatmap (csrc/wasb_net.h CertState::K)
+FRAME_CROPS = 32              # crops one frame may use in all (csrc/certify.hip CERT_MAX_FRAME_CROPS)
+HEAD = 'model.final_layers.0'
+N_NOISE_ROWS = 9              # mixed / dot table weights: head channels 0..8 differ from the planted ones, 9..12 are planted
+
+# blob centres: the four corners, the middle of every edge, then interior points (0.2 px off a pixel centre: one brightest pixel)
+TRACK = np.array([(4.2, 4.2), (635.2, 4.2), (4.2, 347.2), (635.2, 347.2), (320.2, 2.2), (2.2, 180.2), (637.2, 170.2),
+                  (330.2, 349.2), (84.2, 80.2), (555.2, 268.2), (200.2, 150.2), (440.2, 60.2), (100.2, 300.2), (600.2, 100.2),
+                  (250.2, 20.2), (20.2, 250.2)])
+
+# detector -> heatmap channels, frames per call, samples per call
+DETECTORS = {'ball': dict(C=1, n_frames=14, batch=12), 'table': dict(C=13, n_frames=16, batch=16)}
+
+
+def _state_dict(kind):
+    if kind == 'ball-noise':
+        return weights.random_wasb_state_dict(31)
+    if kind == 'ball-planted':
+        return weights.random_wasb_state_dict(31, planted=True)
+    if kind == 'table-noise':
+        return weights.random_wasb_state_dict(33, in_ch=3, head_out=13)
+    if kind == 'table-planted':
+        return weights.random_wasb_state_dict(33, planted=True, in_ch=3, head_out=13, plant_all_heads=True)
+    if kind == 'table-mixed':
+        # the 13 output rows of the final head conv spliced from noise (many candidates) and planted (one candidate) weights: the
+        # late single-candidate channels sit behind channels that use up the frame's crops
+        sd = weights.random_wasb_state_dict(33, planted=True, in_ch=3, head_out=13, plant_all_heads=True)
+        nz = weights.random_wasb_state_dict(33, in_ch=3, head_out=13)
+        for p in ('.weight', '.bias'):
+            sd[HEAD + p] = sd[HEAD + p].copy()
+            sd[HEAD + p][:N_NOISE_ROWS] = nz[HEAD + p][:N_NOISE_ROWS]
+        return sd
+    if kind == 'table-dots':
+        # the planted trunk carries the G channel through trunk channel 0; a second identity path carries R / B (input channel 0)
+        # through trunk channel 1.  Head channels 0..8 read channel 1 (the dots), 9..12 channel 0 (the blob)
+        sd = weights.random_wasb_state_dict(33, planted=True, in_ch=3, head_out=13, plant_all_heads=True)
+        p = 'model'
+        for conv, bn, tap in (('.conv1', '.bn1', (0, 1, 1)), ('.conv2', '.bn2', (1, 1, 1)),
+                              ('.layer1.0.downsample.0', '.layer1.0.downsample.1', (1, 0, 0)), ('.transition1.0.0', '.transition1.0.1', (1, 1, 1))):
+            w = sd[p + conv + '.weight']
+            w[1] = 0.0
+            w[(1,) + tap] = 1.0
+            for k, v in (('.weight', 1.0), ('.bias', 0.0), ('.running_mean', 0.0), ('.running_var', 1.0)):
+                sd[p + bn + k][1] = v
+        w = sd[HEAD + '.weight']
+        w[:N_NOISE_ROWS, 0, 0, 0] = 0.0
+        w[:N_NOISE_ROWS, 1, 0, 0] = 1.0
+        return sd
+    raise KeyError(kind)
+
+
+# 32 dots (4 x 8, 48 / 56 px apart: one crop each) at positions that are multiples of 8 and at least 72 px (the receptive-field
+# radius) inside the frame, on a constant background: every dot sees the same neighbourhood, so the dot channels have 32 tied
+# candidates.  The G blob sits on the border, more than 72 px from every dot.
+DOTS = [(80 + 48 * i, 80 + 56 * j) for i in range(4) for j in range(8)]
+DOT_BLOBS = [(4, 4), (635, 4), (4, 347), (635, 347), (320, 2), (2, 180), (637, 170), (330, 349)]
+
+
+def _dot_frames(n):
+    fr = np.full((n, H, W, 3), 70, np.uint8)
+    for y, x in DOTS:
+        fr[:, y, x, 0] = fr[:, y, x, 2] = 255
+    for f in range(n):
+        x, y = DOT_BLOBS[f % len(DOT_BLOBS)]
+        fr[f, y, x, 1] = 255                     # one pixel: a single candidate on the G channels
+    return fr
+
+
+def _frames(det, content):
+    n = DETECTORS[det]['n_frames']
+    if content == 'track':
+        fr = synth.synth_frames(n, H, W, seed=41, track=TRACK[:n])[0]
+    elif content == 'dots':
+        fr = _dot_frames(n)
+    elif content == 'flat':          # wide saturated blobs: flat-topped near-ties (hundreds of equal pixels)
+        fr = synth.hard_clip(n, H, W, seed=43, sigma=7.0, gain=2.0)[0]
+    else:
+        raise KeyError(content)
+    return torch.from_numpy(fr).cuda()
+
+
+_CACHE = {}
+
+
+def _setup(det, kind, content):
+    """(bf16 handle, frames, calibrated eps, fp32 idx, fp32 win) of one detector / weight set / content, built once per module."""
+    key = (det, kind, content)
+    if key not in _CACHE:
+        sd = _state_dict(kind)
+        fr = _frames(det, content)
+        b = DETECTORS[det]['batch']
+        if det == 'ball':
+            net = wasb.WASBNet(sd, resolution=(W, H), max_batch=b, dtype='bf16')
+            f32 = wasb.WASBNet(sd, resolution=(W, H), max_batch=1, dtype='f32')
+            x = wasb.preprocess_triples(fr, (W, H))
+        else:
+            net = wasb.MyHRNet(sd, resolution=(W, H), max_batch=b, dtype='bf16')
+            f32 = wasb.MyHRNet(sd, resolution=(W, H), max_batch=1, dtype='f32')
+            x = wasb.preprocess_frames(fr, (W, H))
+        eps = net.calibrate(fr, n=4)
+        ref_idx, ref_win = [], []
+        for t in range(x.shape[0]):          # the full-frame fp32 path, one sample at a time
+            _, i1, w1 = wasb.WASBNet.forward(f32, x[t:t + 1], want_heatmap=False, want_peaks=True)
+            ref_idx.append(i1); ref_win.append(w1)
+        _CACHE[key] = (net, fr, eps, torch.cat(ref_idx), torch.cat(ref_win))
+    return _CACHE[key]
+
+
+def _maxf(det, maxc):
+    return min(maxc * DETECTORS[det]['C'], FRAME_CROPS)
+
+
+def _configure(net, det, eps, maxc, budget, exact, audit=(0, 0)):
+    """set_certify(eps, 0, maxc) + exact windows + call budget ('maxf', 'default' or a number) + audit crops; returns the budget."""
+    net.set_certify(eps, 0, maxc, exact_windows=exact)
+    if budget == 'maxf':
+        budget = _maxf(det, maxc)
+    if budget != 'default':
+        net.certify_budget(budget)
+    net.certify_audit_crops(*audit)
+    return budget
+
+
+def _counts(heat, eps):
+    """Candidates of every heatmap as the scan defines them: pixels >= max - 2 * eps, in fp32."""
+    h = heat.reshape(heat.shape[0] * heat.shape[1], -1)
+    thr = h.max(1).values - torch.tensor(2 * np.float32(eps), dtype=torch.float32, device=h.device)
+    return (h >= thr[:, None]).sum(1).cpu().numpy()
+
+
+def _run(net, fr):
+    """One certified call: (idx, win, status & 3, stats of this call alone, candidate counts, eps), idx / win repaired."""
+    net.certify_stats(reset=True)
+    heat, idx, win = net.forward_frames(fr, want_heatmap=True)
+    st = net.certify_status(idx.shape[0]).cpu().numpy() & 3
+    s = net.certify_stats(reset=True)
+    cnt = _counts(heat, net.eps)
+    raw_idx, raw_win = idx.clone(), win.clone()
+    net.fix_uncertified(idx, win, frames_u8=fr, status=st)
+    return dict(idx=idx, win=win, raw_idx=raw_idx, raw_win=raw_win, st=st, s=s, cnt=cnt)
+
+
+def _check_counters(r, C, budget, exact, audit_on):
+    """The counters of one call against the status array the same call returned."""
+    s, st, cnt = r['s'], r['st'], r['cnt']
+    assert s['heatmaps'] == st.shape[0], s
+    assert s['single'] + s['resolved'] + s['not_certified'] == s['heatmaps'], s
+    assert s['not_certified'] == s['over_candidates'] + s['over_crops_per_map'] + s['over_crop_list'], s
+    assert (s['single'], s['resolved'], s['not_certified']) == tuple(int((st == v).sum()) for v in (0, 1, 2)), (s, np.bincount(st, minlength=3))
+    assert s['over_candidates'] == int((cnt > K_CAND).sum()), (s, cnt.max())
+    if budget != 'default':
+        assert s['crops'] <= budget, (s, budget)
+    assert s['small_crops'] <= s['crops'], s
+    # a single-candidate heatmap that got its crop: status 1 in exact-window mode, 0 (an audit pick) otherwise; the channels of a
+    # table frame may share one crop, so exact_singles <= crops holds for the ball detector
+    ones = int((cnt == 1).sum())
+    assert s['exact_singles'] <= ones, (s, ones)
+    if C == 1:
+        assert s['exact_singles'] <= s['crops'], s
+    if exact:
+        assert s['exact_singles'] <= int(((cnt == 1) & (st == 1)).sum()), s
+        if s['not_certified'] == 0:
+            assert s['exact_singles'] == ones, (s, ones)
+    else:
+        # production mode: status 0 is exactly the single-candidate heatmaps (audit picks included: they only measure)
+        assert np.array_equal(st == 0, cnt == 1), (np.nonzero((st == 0) != (cnt == 1))[0].tolist(), st[(st == 0) != (cnt == 1)])
+        if not audit_on:
+            assert s['exact_singles'] == 0, s
+
+
+def _check_parity(r, ref_idx, ref_win, exact):
+    bad = (r['idx'] != ref_idx).nonzero().flatten().tolist()
+    assert not bad, ('index differs from the fp32 path', bad, r['st'][bad])
+    fp32 = torch.from_numpy(r['st'] != 0).to(ref_win.device) if not exact else torch.ones_like(ref_idx, dtype=torch.bool)
+    wbad = ((r['win'] != ref_win).any(1) & fp32).nonzero().flatten().tolist()
+    assert not wbad, ('fp32 window differs from the fp32 path', wbad, r['st'][wbad])
+
+
+# (detector, weights, content, eps factor, maxc, budget, exact windows, counters that must be > 0)
+MATRIX = [
+    ('ball', 'ball-noise', 'track', 1, 1, 'default', False, ('over_crops_per_map', 'resolved')),
+    ('ball', 'ball-noise', 'track', 1, 2, 1, False, ('over_crop_list',)),
+    ('ball', 'ball-noise', 'track', 1, 3, 'maxf', False, ('resolved',)),
+    ('ball', 'ball-noise', 'track', 1, 8, 'default', True, ('resolved',)),
+    ('ball', 'ball-noise', 'track', 1, 32, 'default', False, ('resolved',)),
+    ('ball', 'ball-noise', 'track', 1, 32, 1, True, ('over_crop_list',)),
+    ('ball', 'ball-planted', 'track', 1, 1, 'default', True, ('exact_singles',)),
+    ('ball', 'ball-planted', 'track', 1, 8, 1, True, ('exact_singles', 'over_crop_list')),
+    ('ball', 'ball-planted', 'track', 1, 2, 'maxf', False, ('single',)),
+    ('ball', 'ball-planted', 'flat', 1, 3, 'default', False, ('over_candidates',)),
+    ('table', 'table-noise', 'track', 1, 1, 'default', False, ('over_crops_per_map', 'resolved')),
+    ('table', 'table-noise', 'track', 1, 2, 1, False, ('over_crop_list',)),
+    ('table', 'table-noise', 'track', 1, 3, 'maxf', True, ('resolved',)),
+    ('table', 'table-noise', 'track', 1, 8, 'default', False, ('resolved',)),
+    ('table', 'table-noise', 'track', 1, 32, 'default', True, ('resolved',)),
+    ('table', 'table-planted', 'track', 1, 1, 'default', True, ('exact_singles',)),
+    ('table', 'table-planted', 'track', 1, 8, 1, False, ('single',)),
+    ('table', 'table-mixed', 'track', 1, 3, 'default', False, ('single', 'resolved')),
+    ('table', 'table-mixed', 'track', 1, 8, 'maxf', True, ('exact_singles', 'resolved')),
+    ('table', 'table-mixed', 'track', 1, 32, 1, False, ('over_crop_list',)),
+    ('table', 'table-dots', 'dots', 1, 8, 'default', True, ('over_crops_per_map', 'exact_singles')),
+    ('table', 'table-dots', 'dots', 1, 32, 'maxf', False, ('resolved', 'over_crop_list')),
+]
+_IDS = ['%s-%s-%s-x%g-maxc%d-budget%s%s' % (m[0], m[1].split('-')[1], m[2], m[3], m[4], m[5], '-exact' if m[6] else '') for m in MATRIX]
+_REACHED = {}
+
+
+@pytest.mark.parametrize('det,kind,content,factor,maxc,budget,exact,premise', MATRIX, ids=_IDS)
+def test_budget_matrix_matches_the_fp32_path(det, kind, content, factor, maxc, budget, exact, premise):
+    """Every index equals the full-frame fp32 path's after `fix_uncertified`; wherever the status is not 0 (and everywhere in
+    exact-window mode) the 3x3 window does too, bit for bit; the counters agree with the status array of the same call."""
+    net, fr, eps, ref_idx, ref_win = _setup(det, kind, content)
+    b = _configure(net, det, eps * factor, maxc, budget, exact)
+    r = _run(net, fr)
+    s = r['s']
+    print('\n%s: eps %.4g, status %s, %s' % (_IDS[MATRIX.index((det, kind, content, factor, maxc, budget, exact, premise))], eps * factor,
+                                            np.bincount(r['st'], minlength=3).tolist(), {k: v for k, v in s.items() if k != 'max_candidate_err'}))
+    _REACHED['runs'] = _REACHED.get('runs', 0) + 1
+    for k in s:
+        if k != 'max_candidate_err':
+            _REACHED[k] = _REACHED.get(k, 0) + s[k]
+    _check_parity(r, ref_idx, ref_win, exact)
+    _check_counters(r, DETECTORS[det]['C'], b, exact, audit_on=False)
+    missing = [k for k in premise if s[k] <= 0]
+    assert not missing, ('premise not reached', missing, s)
+
+
+def test_more_than_k_candidates_are_repaired_to_the_fp32_result():
+    """A flat-topped blob (saturated over hundreds of pixels) whose candidate band -- eps widened to the depth of the flat top, which
+    only adds candidates -- holds more than K = 256 pixels: flagged 2 (candidate list overflow), repaired to the fp32 path's index."""
+    net, fr, eps, ref_idx, ref_win = _setup('ball', 'ball-planted', 'flat')
+    heat, _, _ = net.forward_frames(fr, want_heatmap=True)
+    h = heat.reshape(heat.shape[0], -1)
+    # the (K + 40)-th largest value of the flattest heatmap: its band then holds more than K pixels
+    depth = (h.max(1).values - h.topk(K_CAND + 40, dim=1).values[:, -1]).min().item()
+    e = max(eps, 0.5 * depth * 1.01)
+    _configure(net, 'ball', e, 8, 'default', False)
+    r = _run(net, fr)
+    s = r['s']
+    print('\nflat top: eps %.4g (calibrated %.4g), candidates %s, %s' % (e, eps, r['cnt'].tolist(), s))
+    _REACHED['over_candidates'] = _REACHED.get('over_candidates', 0) + s['over_candidates']
+    assert s['over_candidates'] > 0, s
+    assert (r['st'][r['cnt'] > K_CAND] == 2).all()
+    _check_parity(r, ref_idx, ref_win, False)
+    _check_counters(r, 1, 'default', False, audit_on=False)
+
+
+# (detector, weights, content, eps factor, maxc, audit picks that must find no room).  The planted ball weights at twice the
+# calibrated eps have single- and multi-candidate heatmaps; on the dot weights with maxc = 32, channel 0 fills the frame's 32 crops,
+# so the audit pick of a G channel (frames 9..12 with every = 1) meets the per-frame crop limit.
+AUDIT_CASES = [('ball', 'ball-planted', 'track', 2, 3, False), ('ball', 'ball-planted', 'track', 2, 8, False),
+               ('table', 'table-dots', 'dots', 1, 3, False), ('table', 'table-dots', 'dots', 1, 8, False),
+               ('table', 'table-dots', 'dots', 1, 32, True), ('table', 'table-mixed', 'track', 1, 8, False)]
+AUDIT_TIGHT = 4
+
+
+@pytest.mark.parametrize('det,kind,content,factor,maxc,must_drop', AUDIT_CASES, ids=['%s-%s-%s-x%g-maxc%d' % c[:5] for c in AUDIT_CASES])
+def test_audit_crops_never_change_a_result(det, kind, content, factor, maxc, must_drop):
+    """An audit crop only MEASURES |bf16 - fp32| at a single candidate whose index is already certain: with audit crops on (every
+    frame, or every 4th at each phase) the single-candidate heatmaps keep status 0 and the returned indices and 3x3 windows are those
+    of the run without them -- also when the frame's crops or the call's crop list leave no room for the audit (the pick then stays
+    a certified single candidate).  When the call's crop list overflows, WHICH frames get its slots depends on the order the
+    workgroups reach it: status 1 and 2 may then trade places (both end up with the fp32 path's values); without overflow the
+    whole status array is the same."""
+    net, fr, eps, ref_idx, ref_win = _setup(det, kind, content)
+    C = DETECTORS[det]['C']
+    n = ref_idx.shape[0] // C
+    dropped, picked = 0, 0
+    for budget in (AUDIT_TIGHT, 'default'):
+        b = _configure(net, det, eps * factor, maxc, budget, False)
+        r0 = _run(net, fr)
+        _check_counters(r0, C, b, False, audit_on=False)
+        _check_parity(r0, ref_idx, ref_win, False)
+        for audit in [(1, 0)] + [(4, p) for p in range(4)]:
+            _configure(net, det, eps * factor, maxc, budget, False, audit)
+            r1 = _run(net, fr)
+            full = r0['s']['over_crop_list'] > 0 or r1['s']['over_crop_list'] > 0
+            diff = np.nonzero((r1['st'] != r0['st']) if not full else ((r1['st'] == 0) != (r0['st'] == 0)))[0]
+            assert diff.size == 0, ('audit crops %s changed the status (maxc %d, budget %s): heatmaps %s (frame, channel) %s: %s -> %s'
+                                    % (audit, maxc, budget, diff.tolist(), [(int(m) // C, int(m) % C) for m in diff], r0['st'][diff], r1['st'][diff]))
+            assert torch.equal(r1['idx'], r0['idx']) and torch.equal(r1['win'], r0['win']), (audit, budget)
+            single = torch.from_numpy(r0['st'] == 0).to(r0['raw_win'].device)
+            assert torch.equal(r1['raw_win'][single], r0['raw_win'][single]), (audit, budget)
+            _check_counters(r1, C, b, False, audit_on=True)
+            if audit == (1, 0):
+                # frames whose audit channel (f // every) % C has a single candidate: each asks for an audit crop
+                want = sum(1 for f in range(n) if r0['cnt'][f * C + f % C] == 1)
+                picked += want
+                dropped += want - r1['s']['exact_singles']
+                assert r1['s']['exact_singles'] <= want, (r1['s'], want)
+    print('\n%s maxc %d: %d audit picks, %d dropped for lack of room' % (kind, maxc, picked, dropped))
+    _REACHED['audit_dropped'] = _REACHED.get('audit_dropped', 0) + dropped
+    assert picked > 0
+    if must_drop:
+        assert dropped > 0, 'premise: some audit picks find no room in their frame (%d picks)' % picked
+
+
+COUNTER_CASES = [m for m in MATRIX if not m[6]]
+
+
+@pytest.mark.parametrize('det,kind,content,factor,maxc,budget,exact,premise', COUNTER_CASES, ids=[i for i, m in zip(_IDS, MATRIX) if not m[6]])
+def test_counters_agree_with_the_status_with_audit_crops_on(det, kind, content, factor, maxc, budget, exact, premise):
+    """With audit crops on, the counters of a call still add up and agree with its status array: an audit-only heatmap comes back
+    status 0 and is counted as a single candidate; `exact_singles` counts only the audit crops that were kept."""
+    net, fr, eps, ref_idx, ref_win = _setup(det, kind, content)
+    for audit in ((1, 0), (4, 1)):
+        b = _configure(net, det, eps * factor, maxc, budget, False, audit)
+        r = _run(net, fr)
+        _check_counters(r, DETECTORS[det]['C'], b, False, audit_on=True)
+        _check_parity(r, ref_idx, ref_win, False)
+
+
+def test_every_planner_branch_was_reached():
+    """Summary of the module (runs last): each budget branch of the planner was taken somewhere above."""
+    if _REACHED.get('runs', 0) < len(MATRIX) or 'audit_dropped' not in _REACHED:
+        pytest.skip('summary of the whole module: run the file as a whole')
+    print('\nbranches reached: %s' % _REACHED)
+    for k in ('over_candidates', 'over_crops_per_map', 'over_crop_list', 'exact_singles', 'audit_dropped'):
+        assert _REACHED.get(k, 0) > 0, (k, _REACHED)

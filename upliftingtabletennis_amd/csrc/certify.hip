@@ -16,7 +16,8 @@
 //   4. resolve   the candidate with the largest fp32 value (ties -> smaller index, like torch.argmax) becomes the index,
 //                and its 3x3 window is taken from the fp32 crop, so the sub-pixel fit also sees fp32 values.
 // Heatmaps whose candidates overflow the budget (more than K candidates, more than `maxc` crops, crop list full) are
-// flagged 2 in `status`; the caller decides (the Python shim re-runs those frames on the full-frame fp32 handle).
+// flagged 2 in `status`; the caller decides (the Python shim re-runs those frames on the full-frame fp32 handle).  An audit crop
+// that finds no room is dropped instead: its heatmap has one candidate and stays status 0, whatever the audit phase.
 #include "wasb_net.h"
 #include <stdlib.h>
 
@@ -126,7 +127,6 @@ __global__ __launch_bounds__(64) void cert_plan_kernel(PlanArgs a) {
             ci[rank] = v; cb[rank] = s_bf[i]; s_sorted[rank] = v;
         }
         __syncthreads();
-        if (lane == 0 && cnt == 1) atomicAdd(&a.stats[7], 1ull);
         // the lane's candidates lane, lane + 64, ...: position and the slot of the first crop that holds them (-1: none yet)
         int cy[PER], cx[PER], found[PER];
 #pragma unroll
@@ -195,6 +195,7 @@ __global__ __launch_bounds__(64) void cert_plan_kernel(PlanArgs a) {
             ++n_my;
             __syncthreads();
         }
+        if (over && audit_pick && !a.exact) { if (lane == 0) { a.status[map] = 0 | gbit; atomicAdd(&a.stats[1], 1ull); } continue; }          // (no room in the frame for the audit: still a certified single candidate)
         if (over) { if (lane == 0) { a.status[map] = 2 | gbit; atomicAdd(&a.stats[3], 1ull); atomicAdd(&a.stats[9], 1ull); } continue; }          // (n_my_s keeps the list without this heatmap's new crops)
 #pragma unroll
         for (int m = 0; m < PER; ++m)
@@ -234,8 +235,9 @@ __global__ __launch_bounds__(64) void cert_plan_kernel(PlanArgs a) {
         for (int k = lane; k < cnt; k += 64) a.cand_crop[(size_t)map * a.K + k] += base;
         if (lane == 0) {
             a.status[map] = 1 | gbit | abit;
-            atomicAdd(&a.stats[2], 1ull);
-            atomicAdd(&a.stats[5], (unsigned long long)cnt);
+            if (cnt == 1) atomicAdd(&a.stats[7], 1ull);          // (counted where the single candidate's crop is kept)
+            if (abit) atomicAdd(&a.stats[1], 1ull);              // an audit-only heatmap returns as a single candidate (cert_resolve_kernel)
+            else { atomicAdd(&a.stats[2], 1ull); atomicAdd(&a.stats[5], (unsigned long long)cnt); }
         }
     }
 }
