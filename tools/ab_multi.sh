@@ -1,6 +1,6 @@
 #!/bin/bash
 # N-way comparison of library builds on ONE box (boxes differ by +-4 %): tools/ops_report.py per build, the builds taking turns.
-#   tools/ab_multi.sh <rounds> <lib|default> <lib|default> ...        (lib: a path, or a tag T for upliftingtabletennis_amd/_ablate/libttup_T.so;
+#   tools/ab_multi.sh <rounds> <lib|default> <lib|default> ...        (lib: the path of a libttup build;
 #   <lib>+VAR=value runs that build with the environment variable set, e.g. default+TTUP_BB2_GENERIC=1)
 # Output: gpurun_out/abm/<tag>_<round>.log and the per-kernel medians of every build side by side.
 N=$1; shift
@@ -11,7 +11,7 @@ for r in $(seq 1 $N); do
   for spec in "$@"; do
     t=${spec%%+*}; ev=""; [ "$t" != "$spec" ] && ev=${spec#*+}
     tag=$(basename "$t" .so); tag=${tag#libttup_}; [ -n "$ev" ] && tag=${tag}+$ev
-    lib=$t; [ -f "$lib" ] || lib=upliftingtabletennis_amd/_ablate/libttup_$t.so
+    lib=$t; [ "$t" = default ] || lib=$(realpath --relative-to=. "$t")
     if [ "$t" = default ]; then env -u TTUP_LIB $ev TTUP_REPS=${TTUP_REPS:-10} python3 tools/ops_report.py > "gpurun_out/abm/${tag}_$r.log" 2>&1
     else env $ev TTUP_LIB=$PWD/$lib TTUP_REPS=${TTUP_REPS:-10} python3 tools/ops_report.py > "gpurun_out/abm/${tag}_$r.log" 2>&1; fi
   done

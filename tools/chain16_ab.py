@@ -37,11 +37,8 @@ np.savez(sys.argv[1], **out)
 def main():
     outs = {}
     with tempfile.TemporaryDirectory() as d:
-        # `python tools/chain16_ab.py stream`: the streaming form (csrc/experiments/chain16s.h.inc -- not compiled; when it is wired in
-        # again, TTUP_C16_STREAM=1 selects it) against the tile form instead
-        pair = (('new', {'TTUP_C16_STREAM': '1'}), ('old', {})) if sys.argv[1:] == ['stream'] else (('new', {}), ('old', {'TTUP_BB2_GENERIC': '1'}))
-        for tag, env in pair:
-            e = dict(os.environ); e.pop('TTUP_BB2_GENERIC', None); e.pop('TTUP_C16_STREAM', None); e.update(env)
+        for tag, env in (('new', {}), ('old', {'TTUP_BB2_GENERIC': '1'})):
+            e = dict(os.environ); e.pop('TTUP_BB2_GENERIC', None); e.update(env)
             f = os.path.join(d, tag + '.npz')
             r = subprocess.run([sys.executable, '-c', CHILD, f], env=e, capture_output=True, text=True, timeout=1800)
             if r.returncode != 0:

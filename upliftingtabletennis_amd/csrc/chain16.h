@@ -17,14 +17,6 @@
 //     the tile, so that they arrive with it instead of costing a second memory round trip behind the first barrier.
 #pragma once
 
-// -DTTUP_TIMING -DTTUP_TIMING_C16W (tools/build_ablate.sh TIMING,TIMING_C16W; tools/c16_wave_timing.py): s_memtime stamps of EVERY wave of the
-// first 512 workgroups at the phase boundaries, kept in scalar registers until the kernel ends
-#if defined(TTUP_TIMING) && defined(TTUP_TIMING_C16W)
-#define C16_WSTAMP(k) do { wst[k] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define C16_WSTAMP(k) do { } while (0)
-#endif
-
 struct C16IdmTab {
     unsigned short v[64 * 8];
     constexpr C16IdmTab() : v() {
@@ -36,11 +28,9 @@ struct C16IdmTab {
 __device__ const C16IdmTab c16_idm_tab = C16IdmTab();
 
 constexpr int C16_PB = 32;                  // bytes per pixel record (16 bf16 channels)
-// L2 prefetch distance in workgroups (0 = off): see c16_chain_kernel.  Measured (two boxes, ms per launch, sum / stored-output forms):
+// L2 prefetch distance in workgroups: see c16_chain_kernel.  Measured (two boxes, ms per launch, sum / stored-output forms):
 // off 0.7184-0.7440; 512: -1.4 %; 256: -1.3 ... -2.3 % (-1.6 ... -3.2 % on the stored-output forms); 192 like 256; 128: +0.4 %; 64: +2.7 %
-#ifndef TTUP_C16_PREFETCH
-#define TTUP_C16_PREFETCH 256
-#endif
+constexpr int C16_PREFETCH = 256;
 // work split of conv1 / conv2 / conv3 of the 24x32 tile (regions 30x38, 28x36, 26x34): rows for waves 0-3 | 4-5 | 6-7, strip pairs likewise
 // (measured against equal bands of four rows with the strip pairs dealt to the last wave first: -1.2 ... -1.7 % on the launches with
 // stored outputs, +-0 on the stage-4 form; two neighbouring splits -- conv2 at 4 | 3 | 3 rows, or 5-row bands for the older waves in
@@ -92,11 +82,7 @@ __device__ __forceinline__ void c16_conv_lds(const char* s_in, char* s_out, cons
     for (int s = 0; s < 5; ++s) af[s] = fr.af[s];
     if (SECOND && g >= 2) af[4] = idm;          // the block input rides in the unused tenth tap (exact: bf16 x 1.0 into the fp32 sum)
     const f32x4 bias = fr.bias;
-#ifdef TTUP_ABL_NOPAD
-    const bool interior = true;
-#else
     const bool interior = gy0 >= 0 && gy0 + RHO <= H && gx0 >= 0 && gx0 + RWO <= W;
-#endif
     // ---- the band: rows yb .. yb+rows-1, column groups 0 and 1
     if (rows > 0) {
         const char* rowb = s_in + ((yb + IOFF) * RWI) * C16_PB;
@@ -145,7 +131,6 @@ __device__ __forceinline__ void c16_conv_lds(const char* s_in, char* s_out, cons
     // ---- the ragged strip (columns 32 .. 32+RX-1): pairs of COLUMN groups -- lane n = row n (group A) and row RHO/2 + n (group B) of one
     // strip column.  On the odd row strides of the chain's buffers 16 consecutive rows of a column fall on 16 different 16-byte slots,
     // like the 16 consecutive pixels of a band group (bb_conv's strip groups, round 4); same k-step order and operands per output pixel.
-#ifndef TTUP_ABL_NOSTRIPWORK
     {
         constexpr int RPG = RHO / 2;
         static_assert(RPG <= 16, "a strip column is two 16-lane groups");
@@ -186,7 +171,6 @@ __device__ __forceinline__ void c16_conv_lds(const char* s_in, char* s_out, cons
         for (int k = 0; k < NPMAX; ++k)
             if (k < np) pair(p0 + k);
     }
-#endif
 }
 
 // The last conv of the chain (region TH x TW = 24 x 32: two full column groups, three rows per wave) and what rides in its epilogue.
@@ -237,9 +221,6 @@ __device__ __forceinline__ void c16_conv_out(const char* s_in, const char* s_res
     tbx[0] = s_terms + (t2lane ? T2OFF + (n >> 2) * C16_PB : (n >> 1) * C16_PB) + c8 * 16;
     tbx[1] = tbx[0] + (t2lane ? 4 * C16_PB : 8 * C16_PB);
     const char* tb3 = s_terms + T3OFF + (n >> 3) * C16_PB + c8 * 16;
-#ifdef TTUP_C16_NARROW
-    const unsigned st_16 = (unsigned)((n * 16 + g * 4) * 2);             // lane's 8 bytes inside a 16-pixel run of 16-channel records
-#endif
     const float head_one = (n == 0) ? 1.f : 0.f;          // A operand of the head's cross-lane sum (row 0 of a 16x4 matrix of ones)
     float hvs[2 * RB];
     bf16x8 fa[2][RB + 2];
@@ -284,17 +265,6 @@ __device__ __forceinline__ void c16_conv_out(const char* s_in, const char* s_res
                     q[xt][0] = relu_pk(pack2(ys[0], ys[1])); q[xt][1] = relu_pk(pack2(ys[2], ys[3]));
                 }
             }
-#ifdef TTUP_ABL_C4_NOSTORE
-            asm volatile("" :: "v"(p[0][0]), "v"(p[0][1]), "v"(p[1][0]), "v"(p[1][1]));
-            if (NS >= 1) asm volatile("" :: "v"(q[0][0]), "v"(q[0][1]), "v"(q[1][0]), "v"(q[1][1]));
-#elif defined(TTUP_C16_NARROW)
-#pragma unroll
-            for (int xt = 0; xt < 2; ++xt) {
-                const bool live = row_in && (xt ? cl1 : cl0);
-                if (a.y && live) *(u32x2*)((char*)(a.y + rowpix * 16) + (opaque_u32(st_16) + (unsigned)(xt * 512))) = u32x2{p[xt][0], p[xt][1]};
-                if (NS >= 1 && live) *(u32x2*)((char*)(a.ysum + rowpix * 16) + (opaque_u32(st_16) + (unsigned)(xt * 512))) = u32x2{q[xt][0], q[xt][1]};
-            }
-#else
             // the two column groups' 8-byte pieces become ONE 16-byte store per lane (chunk g >> 1 of pixel n of group g & 1): half the
             // store instructions for the same bytes -- the store path is paid per instruction
             // (the swaps run with every lane active, BEFORE the divergent stores: a live lane's partner may be dead)
@@ -304,7 +274,6 @@ __device__ __forceinline__ void c16_conv_out(const char* s_in, const char* s_res
             if (NS >= 1) so = c16_pair_chunk(q[0][0], q[0][1], q[1][0], q[1][1]);
             if (a.y && live) *(u32x4*)((char*)(a.y + rowpix * 16) + opaque_u32(st_w)) = yo;
             if (NS >= 1 && live) *(u32x4*)((char*)(a.ysum + rowpix * 16) + opaque_u32(st_w)) = so;
-#endif
         } else {
 #pragma unroll
             for (int xt = 0; xt < 2; ++xt) {
@@ -319,11 +288,7 @@ __device__ __forceinline__ void c16_conv_out(const char* s_in, const char* s_res
                 // sum over the pixel's 4 lane groups on the matrix pipe (exact fp32): D[0][n] = sum_g 1 * part(n, g)
                 const f32x4 hd = __builtin_amdgcn_mfma_f32_16x16x4f32(head_one, part, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
                 const float hv = hd[0] + a.hbias;
-#ifdef TTUP_ABL_C4_NOSTORE
-                asm volatile("" :: "v"(hv));
-#else
                 if (row_in && (xt ? hl1 : hl0)) *(float*)((char*)(a.heat + rowpix) + (opaque_u32((unsigned)(n * 4)) + (unsigned)(xt * 64))) = hv;
-#endif
                 hvs[2 * r + xt] = hv;
             }
         }
@@ -373,21 +338,9 @@ __global__ __launch_bounds__(512, 4) void c16_chain_kernel(BBArgs a) {
     char* bufB = smem + SZ_A;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // 3-D grid (tile column, tile row, image); XCD = linear workgroup id % 8: every XCD takes a strip of adjacent tile columns (see bb_chain2_kernel)
-#ifdef TTUP_NO_XCD_MAP
-    const int bx = blockIdx.x;
-#else
     const int bx = (gridDim.x & 7) == 0 ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
-#endif
     const int b = blockIdx.z, tt = blockIdx.y * a.tiles_x + bx;
     const int oy0 = blockIdx.y * TH, ox0 = bx * TW;
-#ifdef TTUP_TIMING
-    const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    TTUP_STAMP(0);
-#if defined(TTUP_TIMING) && defined(TTUP_TIMING_C16W)
-    unsigned long long wst[16] = {};
-#endif
-    C16_WSTAMP(0);
     BBFrag16 fr;
     bf16x8 idm;
     f32x4 hw4 = {0.f, 0.f, 0.f, 0.f};
@@ -438,25 +391,17 @@ __global__ __launch_bounds__(512, 4) void c16_chain_kernel(BBArgs a) {
         for (int k = 0; k < IN_PT; ++k)
             if (rl < RL && rl + k * RL < R0H) *(u32x4*)(dst + k * RL * SA * C16_PB) = v[k];
     }
-    C16_WSTAMP(1);
     __syncthreads();
-    TTUP_STAMP(1);
-    C16_WSTAMP(2);
-#if TTUP_C16_PREFETCH > 0
     unsigned pf_sink = 0;          // the register the prefetch lands in: kept alive (below) until the load has certainly arrived -- the compiler does not know about it
     // L2 prefetch for the workgroup that takes this one's place: workgroups are dealt to the XCDs round-robin by linear id and 512 are
-    // resident (two per CU), so workgroup id + TTUP_C16_PREFETCH (a multiple of 8: same XCD, same L2) starts about one tile time from
+    // resident (two per CU), so workgroup id + C16_PREFETCH (a multiple of 8: same XCD, same L2) starts about one tile time from
     // now.  One lane per 128-byte line of ITS input region reads one dword -- 320 lane-loads for 40 KB -- into a register nobody
     // reads (an asm the compiler does not count: its later waits can only get stricter, and s_endpgm waits for everything).
     {
-        const int lid = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x + TTUP_C16_PREFETCH;
+        const int lid = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x + C16_PREFETCH;
         const int gxy = gridDim.x * gridDim.y;
         const int pz = lid / gxy, prem = lid - pz * gxy, py = prem / (int)gridDim.x, pxr = prem - py * (int)gridDim.x;
-#ifdef TTUP_NO_XCD_MAP
-        const int pbx = pxr;
-#else
         const int pbx = (gridDim.x & 7) == 0 ? (pxr & 7) * (gridDim.x >> 3) + (pxr >> 3) : pxr;
-#endif
         constexpr int LPR = (R0W * C16_PB + 127) / 128;          // 128-byte lines per region row (the region starts 128-byte aligned: ox0 - 4 pixels of 32 bytes)
         const int prow = tid / LPR, pline = tid - prow * LPR;
         const int gyp = py * TH - L + prow, gxp = pbx * TW - L + pline * 4;          // 4 pixels per line
@@ -465,26 +410,16 @@ __global__ __launch_bounds__(512, 4) void c16_chain_kernel(BBArgs a) {
             asm volatile("global_load_dword %0, %1, off" : "=v"(pf_sink) : "v"(pp) : "memory");
         }
     }
-#endif
     c16_conv_lds<SA, 0, R0H - 2, R0W - 2, false, 1, 0, SB, 0, C16_SPLIT1>(bufA, bufB, nullptr, fr, idm, oy0 - 3, ox0 - 3, a.H, a.W, wave, lane);
-    TTUP_STAMP(2);
-    C16_WSTAMP(3);
     // next conv's fragments: requested BEFORE the barrier, in flight across it.  (Requested a whole conv earlier into a second register
     // set -- 110-116 instead of 86-100 VGPRs -- the kernel is no faster: 0.7311 against 0.7310 ms for its three launches.)
     bb_load_frag16(fr, a.w[1], a.bias[1], lane);
     __syncthreads();
-    TTUP_STAMP(3);
-    C16_WSTAMP(4);
     c16_conv_lds<SB, 0, R0H - 4, R0W - 4, true, SA, 2, SA, 2, C16_SPLIT2>(bufB, bufA, bufA, fr, idm, oy0 - 2, ox0 - 2, a.H, a.W, wave, lane);
-    C16_WSTAMP(5);
-#if TTUP_C16_PREFETCH > 0
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // (everything older has long arrived: conv1 and conv2 lie between)
     asm volatile("" :: "v"(pf_sink));
-#endif
     bb_load_frag16(fr, a.w[2], a.bias[2], lane);
     __syncthreads();
-    TTUP_STAMP(4);
-    C16_WSTAMP(6);
     // The fuse-layer terms of the last epilogue (1x1-conv'd lower branches at 1/2, 1/4, 1/8 resolution): the tile's slices (12x16 + 6x8 +
     // 3x4 pixel records = 8 KB at most) are requested now, travel while conv3 runs, and are parked in the tail of bufB that conv3's
     // packed 26x34 output leaves free.  One branch-free load per thread (a unit outside the image reads the term's first bytes: it is
@@ -509,18 +444,11 @@ __global__ __launch_bounds__(512, 4) void c16_chain_kernel(BBArgs a) {
         treg = *(const u32x4*)(ok ? tp + ((long long)(b * hs + ty) * ws + tx) * 16 + (u & 1) * 8 : a.st[0]);
     }
     c16_conv_lds<SA, 2, R0H - 6, R0W - 6, false, 1, 0, S3, 0, C16_SPLIT3>(bufA, bufB, nullptr, fr, idm, oy0 - 1, ox0 - 1, a.H, a.W, wave, lane);
-    C16_WSTAMP(7);
     if (NS > 0 && tid < BN) ((u32x4*)s_terms)[tid] = treg;
     bb_load_frag16(fr, a.w[3], a.bias[3], lane);
     __syncthreads();
-    TTUP_STAMP(5);
-    C16_WSTAMP(8);
     BBBest best; best.v = -INFINITY; best.i = 0x7fffffffffffffffLL;
     c16_conv_out<S3, TH, TW, SA, 4, MODE>(bufB, bufA, s_terms, fr, idm, hw4, a, oy0, ox0, b, wave, lane, &best);
-#ifdef TTUP_TIMING_SPLIT
-    TTUP_STAMP(6);
-#endif
-    C16_WSTAMP(9);
     if (MODE == 7) {
         // argmax partial of this tile.  (value, index) pairs become one 64-bit key -- order-preserving bits of the value (NaN on top,
         // -0 = +0 as torch.argmax has it) above the complemented index -- so that "greater value, then lower index" is an unsigned
@@ -543,20 +471,6 @@ __global__ __launch_bounds__(512, 4) void c16_chain_kernel(BBArgs a) {
             }
         }
     }
-#ifndef TTUP_TIMING_SPLIT
-    TTUP_STAMP(6);
-#endif
-#if defined(TTUP_TIMING) && defined(TTUP_TIMING_C16W)
-    C16_WSTAMP(10);
-    __builtin_amdgcn_s_waitcnt(0);           // (vmcnt 0: the tile's stores have left)
-    C16_WSTAMP(11);
-    if (lane == 0 && TTUP_BID < 512) {
-#pragma unroll
-        for (int k = 0; k < 12; ++k) ttup_tbuf[(TTUP_BID * 8 + wave) * 16 + k] = wst[k];
-    }
-#elif defined(TTUP_TIMING)
-    if (tid == 0 && TTUP_BID < 8192) ttup_tbuf[TTUP_BID * 8 + 7] = __builtin_amdgcn_s_memrealtime() - rt0;      // 100 MHz ticks for the same span
-#endif
 }
 
 template <int TH, int TW, int MODE>

@@ -19,41 +19,14 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
-#ifdef TTUP_TIMING
-// debug build only (tools/build_ablate.sh TIMING): phase timestamps (s_memtime) of wave 0.
-//   TTUP_STAMP(k)        one-tile-per-workgroup kernels: slot k of workgroup blockIdx.x          (bb_chain2_kernel)
-//   TTUP_STAMP_IT(id,it,k) persistent kernels: kernel id (0 stem, 1 bneck, 2 32-channel block), tile iteration it < 64 of workgroups < 32
-__device__ unsigned long long ttup_tbuf[8192 * 8];
-__device__ unsigned long long ttup_tbuf_it[3 * 32 * 64 * 8];
-#define TTUP_BID ((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x)
-#ifdef TTUP_TIMING_C16W
-#define TTUP_STAMP(k) do { } while (0)          // (the per-wave stamps of csrc/chain16.h own the buffer)
-#else
-#define TTUP_STAMP(k) do { if (tid == 0 && TTUP_BID < 8192) ttup_tbuf[TTUP_BID * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#endif
-#ifdef TTUP_TIMING_WAVES
-// ... of EVERY wave of ONE kernel (id == TTUP_TIMING_WAVES): the buffer is read as [8 waves][12 workgroups][64 iterations][8 slots] (tools/wave_timing.py)
-#define TTUP_STAMP_IT(id, it, k) do { if ((id) == TTUP_TIMING_WAVES && (tid & 63) == 0 && blockIdx.x < 12 && (it) < 64) ttup_tbuf_it[((((tid >> 6)) * 12 + blockIdx.x) * 64 + (it)) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define TTUP_STAMP_IT(id, it, k) do { if (tid == 0 && blockIdx.x < 32 && (it) < 64) ttup_tbuf_it[(((id) * 32 + blockIdx.x) * 64 + (it)) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#endif
-#else
-#define TTUP_STAMP(k) do { } while (0)
-#define TTUP_STAMP_IT(id, it, k) do { } while (0)
-#endif
-
 // MI355X: 8 XCDs with a private L2 each, workgroups dealt to them round-robin by linear id.  Persistent kernels walk tiles
 // t = blockIdx.x + it * gridDim.x (gridDim.x a multiple of 8), so tile t runs on XCD t % 8 and raster neighbours -- which share
 // halo rows / columns -- sit behind eight different L2s.  This remaps the sequence so that every XCD walks one contiguous
 // eighth of the raster order: neighbours' halos become hits in the XCD's own L2 (PMC: 1.51 -> 1.40 GB of L2 fills per frame).
 // Not applied in conv_mfma_kernel: its HBM-bound full-resolution conv gets 5-10 % slower with eight widely separated streams.
 __device__ __forceinline__ int xcd_tile(int t, int total) {
-#ifdef TTUP_NO_XCD_MAP
-    return t;
-#else
     const int main = total & ~7;
     return t < main ? (t & 7) * (main >> 3) + (t >> 3) : t;
-#endif
 }
 
 struct ConvKArgs {
@@ -138,14 +111,6 @@ __device__ __forceinline__ void prefetch_arrived(const T (&r)[N]) {
     for (int k = 0; k < N; ++k) asm volatile("" :: "v"(r[k]));
 }
 
-// -DTTUP_PRIO_YOUNG (experiment, MI355X_MICROARCH.md "Static priority for the younger half"): waves 4-7 of an 8-wave workgroup lose
-// the SIMD's issue arbitration to waves 0-3 (priority, then age); one s_setprio 1 for them at kernel start hands them the older half's timing
-__device__ __forceinline__ void prio_young_half() {
-#ifdef TTUP_PRIO_YOUNG
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
-#endif
-}
-
 // Persistent, software-pipelined version: a workgroup walks work items (tile, channel chunk); the global loads of
 // item i+1 (halo tile chunk + that chunk's weight fragments) are issued into registers BEFORE the MFMA loop of item i
 // and written to LDS after it, so HBM/L2 latency hides behind the matrix work (single LDS buffer, two barriers per item).
@@ -200,13 +165,11 @@ __global__ __launch_bounds__(NW * 64) void conv_mfma_kernel(ConvKArgs a) {
         const bf16_t* src = first ? a.src0 : a.src1;
         const int csrc = first ? a.c0 : a.c1;
         const int ch0 = (first ? chunk : chunk - a.nchunk0) * CK;
-#if !defined(TTUP_NO_FAST_PREFETCH) && !defined(TTUP_ABLATE_LOADS)
         if (FASTP && first && gy0 >= 0 && gy0 + IH <= a.H && gx0 >= 0 && gx0 + IW <= a.W) {          // halo tile inside the image: scalar base + lane constants
             const char* base = (const char*)(a.src0 + ((size_t)(b * a.H + gy0) * a.W + gx0) * a.c0 + ch0);
 #pragma unroll
             for (int k = 0; k < IN_PT; ++k) pin[k] = *(const u32x4*)(base + opaque_u32(voff[FASTP ? k : 0]));
         } else
-#endif
         {
 #pragma unroll
             for (int k = 0; k < IN_PT; ++k) {
@@ -214,10 +177,8 @@ __global__ __launch_bounds__(NW * 64) void conv_mfma_kernel(ConvKArgs a) {
                 const int c8 = u % (CK / 8), pix = u / (CK / 8);
                 const int gy = gy0 + pix / IW, gx = gx0 + pix % IW;
                 pin[k] = u32x4{0u, 0u, 0u, 0u};
-#ifndef TTUP_ABLATE_LOADS
                 if (u < IN_UNITS && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W)
                     pin[k] = *(const u32x4*)(src + ((size_t)(b * a.H + gy) * a.W + gx) * csrc + ch0 + c8 * 8);
-#endif
             }
         }
         if (nchunk > 1 || item == 0) {
@@ -300,17 +261,10 @@ __global__ __launch_bounds__(NW * 64) void conv_mfma_kernel(ConvKArgs a) {
                 const bf16x8 bfr = *(const bf16x8*)(bp + ((r * S + dyc) * IW + cg * 16 * S) * CK);
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
-#ifdef TTUP_ABLATE_MFMA
-                    asm volatile("" :: "v"(af[m]), "v"(bfr));
-#else
                     acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[m], bfr, acc[m][t], 0, 0, 0);
-#endif
                 }
             }
         }
-#ifdef TTUP_ABLATE_EPILOGUE
-        if (chunk != nchunk - 1 || a.H > 0) continue;
-#endif
         // (no prefetch_arrived in front of the epilogue here: this kernel runs two to four workgroups per CU, another workgroup's MFMAs
         // cover a store drain at the top of the next item, and the HBM-bound 32 -> 32 conv at full resolution measured 4 % SLOWER with
         // the wait moved in front of its stores -- 0.204 against 0.196 ms, round 5)
@@ -554,53 +508,22 @@ __device__ __forceinline__ void conv64_tile_mfma(f32x4 (&acc)[4][2], const bf16_
     };
     load_b(brow[0], 0, 0);
     load_a(af[0], 0);
-#ifdef TTUP_ABL_MFMA32          // timing experiment (wrong results): the k-step's eight 16x16x32 MFMAs as four 32x32x16 ones on the same operand registers, two accumulator chains
-    typedef __attribute__((ext_vector_type(16))) float f32x16;
-    f32x16 c32[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) c32[t][m * 4 + r] = acc[m][t][r];
-#endif
 #pragma unroll
     for (int s = 0; s < 18; ++s) {
         const int dy = s % 3, gi = s / 3;                       // gi = (plane, tap column) group: c = gi / 3, dx = gi % 3
         if (s + 1 < 18) {
             const int s1 = s + 1, dy1 = s1 % 3, g1 = s1 / 3, c1 = g1 / 3, dx1 = g1 % 3;
             if (dy1 == 0) load_b(brow[g1 & 1], c1, dx1);
-#ifdef TTUP_ABL_NOAFRAG          // timing experiment (wrong results): the weight fragments of step 0 serve every step -- what the LDS reads of the A operand cost
-            af[s1 & 1][0] = af[s & 1][0]; af[s1 & 1][1] = af[s & 1][1]; af[s1 & 1][2] = af[s & 1][2]; af[s1 & 1][3] = af[s & 1][3];
-#else
             load_a(af[s1 & 1], c1 * 9 + dy1 * 3 + dx1);
-#endif
         }
         hook(s);
-#ifndef TTUP_NO_FRAG_PIPELINE
         __builtin_amdgcn_sched_barrier(0);
-#endif
-#ifdef TTUP_ABL_MFMA32
-#pragma unroll
-        for (int m = 0; m < 4; ++m) c32[m & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[s & 1][m], brow[gi & 1][dy + (m & 1)], c32[m & 1], 0, 0, 0);
-#else
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int m = 0; m < 4; ++m) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[s & 1][m], brow[gi & 1][dy + t], acc[m][t], 0, 0, 0);
-#endif
-#ifndef TTUP_NO_FRAG_PIPELINE
         __builtin_amdgcn_sched_barrier(0);
-#endif
     }
-#ifdef TTUP_ABL_MFMA32
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[m][t][r] = c32[t][m * 4 + r];
-#endif
 }
 
 // ------------------------------------------------------------------ 3x3 64 -> 64 with resident weights
@@ -658,14 +581,12 @@ __global__ __launch_bounds__(512) void conv64_kernel(ConvKArgs a) {
         const int tl = xcd_tile(blockIdx.x + it * gridDim.x, a.total_tiles);
         const int b = tl / a.tiles_per_img, t = tl % a.tiles_per_img;
         const int gy0 = (t / a.tiles_x) * 8 - 1, gx0 = (t % a.tiles_x) * 32 - 1;
-#ifndef TTUP_NO_FAST_PREFETCH
         if (gy0 >= 0 && gy0 + IH <= a.H && gx0 >= 0 && gx0 + IW <= a.W) {          // halo tile inside the image: scalar base + lane constants
             const char* base = (const char*)(a.src0 + ((size_t)(b * a.H + gy0) * a.W + gx0) * 64);
 #pragma unroll
             for (int k = 0; k < IN_PT; ++k) pin[k] = *(const u32x4*)(base + opaque_u32(voff[k]));
             return;
         }
-#endif
 #pragma unroll
         for (int k = 0; k < IN_PT; ++k) {
             const int u = tid + k * 512;
@@ -797,7 +718,6 @@ static int launch_conv64_t(const ConvKArgs& a, hipStream_t st) {
 // address) and overwrites its slot with zeros once its own pieces have landed, before the barrier publishes the buffer.
 template <bool L16, bool L32>
 __global__ __launch_bounds__(512) void conv64_dma_kernel(ConvKArgs a) {
-    prio_young_half();
     constexpr int IH = 10, IW = 34, NPIX = IH * IW;
     constexpr int W_U = 2 * 9 * 4 * 64;                         // 16-byte units
     constexpr int IN_UNITS = NPIX * 8, IN_PT = (IN_UNITS + 511) / 512;
@@ -942,26 +862,16 @@ __global__ __launch_bounds__(512) void conv64_dma_kernel(ConvKArgs a) {
             }
         }
     };
-    // STAGGER (as in the stem; -DTTUP_CONV64_STAGGER): waves 4-7 -- the second wave of every SIMD -- run the epilogue of a tile at the
-    // START of the next iteration, under the partner wave's MFMA loop, instead of beside the partner's own epilogue with the matrix pipe
-    // idle; the accumulators and the block input stay in registers across the barrier.  MEASURED here (round 5): 0.340 against 0.3375 ms
-    // for the eight launches -- no gain (the epilogue's vector work competes for the issue port the partner's MFMA loop needs): off
-#ifdef TTUP_CONV64_STAGGER
-    constexpr bool STAGGER = true;
-#else
-    constexpr bool STAGGER = false;
-#endif
-    const bool late = STAGGER && wave >= 4;
+    // (the stem's STAGGER -- waves 4-7 run a tile's epilogue at the start of the next iteration, under the partner wave's MFMA loop --
+    // MEASURED here (round 5): 0.340 against 0.3375 ms for the eight launches, no gain: the epilogue's vector work competes for the
+    // issue port the partner's MFMA loop needs)
     f32x4 acc[4][2];
     u32x4 rres[2][2] = {};
-    int eb = 0, eoy0 = 0, eox0 = 0;
-    bool pending = false;
     for (int it = 0; it < my_tiles; ++it) {
         const int tl = xcd_tile(blockIdx.x + it * gridDim.x, a.total_tiles);
         const int b = tl / a.tiles_per_img, tt = tl % a.tiles_per_img;
         const int oy0 = (tt / a.tiles_x) * 8, ox0 = (tt % a.tiles_x) * 32;
         __syncthreads();                      // tile it visible (every wave waited for its own pieces); every wave is done with the other buffer
-        if (late && pending) epilogue(acc, rres, eb, eoy0, eox0);
         // the block input (residual) of both pixel groups travels during the MFMA loop (the registers the staged tile no longer needs)
         if (a.residual) {
 #pragma unroll
@@ -988,10 +898,8 @@ __global__ __launch_bounds__(512) void conv64_dma_kernel(ConvKArgs a) {
         // tile it+1 and the block input have landed -- waited for HERE, in front of this tile's stores (behind them the same wait drains them)
         __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0)
         if (more) zero_fix(it + 1);
-        if (late) { eb = b; eoy0 = oy0; eox0 = ox0; pending = true; }
-        else epilogue(acc, rres, b, oy0, ox0);
+        epilogue(acc, rres, b, oy0, ox0);
     }
-    if (late && pending) epilogue(acc, rres, eb, eoy0, eox0);
 }
 
 template <bool L16, bool L32>
@@ -1032,7 +940,7 @@ static int launch_conv64(const PackedConv& p, const ConvLaunch& l, hipStream_t s
     if (l.lin16 && l.lin32) return launch_conv64_t<true, true>(a, st);
     if (l.lin16) return launch_conv64_t<true, false>(a, st);
     if (l.lin32) return launch_conv64_t<false, true>(a, st);
-    // (the 32x32x16-MFMA form of this conv, round 5: 0.8 % slower -- csrc/experiments/rejected_kernels.hip.inc)
+    // (the 32x32x16-MFMA form of this conv, round 5: 0.8 % slower -- git show d528471:upliftingtabletennis_amd/csrc/experiments/rejected_kernels.hip.inc)
     return launch_conv64_t<false, false>(a, st);
 }
 
@@ -1065,7 +973,6 @@ struct StemArgs {
 // than the layer-wise conv): results agree to bf16 rounding flips, like the other fused kernels (tests/test_gpu_parity.py).
 template <int NF, bool K4 = false>
 __global__ __launch_bounds__(512) void stem_kernel(StemArgs a) {
-    prio_young_half();
     static_assert(!K4 || NF == 3, "the 4-step conv1 is the three-frame form");
     constexpr int XH = 12, XW = 36, TH1 = 10, TW1 = 34, NP1 = TH1 * TW1;       // X0 region, conv1 output region
     constexpr int KS1 = K4 ? 4 : 5;                                              // conv1 k-steps
@@ -1135,14 +1042,12 @@ __global__ __launch_bounds__(512) void stem_kernel(StemArgs a) {
         const int b = tl / a.tiles_per_img, t = tl % a.tiles_per_img;
         const int gy0 = (t / a.tiles_x) * 8 - 2, gx0 = (t % a.tiles_x) * 32 - 2;
         if (NF) {
-#ifndef TTUP_NO_FAST_PREFETCH
             if (gy0 >= 0 && gy0 + XH <= a.H && gx0 >= 0 && gx0 + XW <= a.W) {          // halo tile inside the image: scalar base + lane constants
                 const char* base = (const char*)(a.x0 + (((size_t)b * a.H + gy0) * a.W + gx0) * 4);
 #pragma unroll
                 for (int k = 0; k < X_PT; ++k) pf[k] = *(const u32x2*)(base + opaque_u32(xoff[k]));
                 return;
             }
-#endif
 #pragma unroll
             for (int k = 0; k < X_PT; ++k) {
                 const int u = tid + k * 512;
@@ -1193,11 +1098,8 @@ __global__ __launch_bounds__(512) void stem_kernel(StemArgs a) {
             for (int q = 0; q < 2; ++q) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) pk[q][i] = relu_pk(pack2(acc[2 * q + (i >> 1)][t][2 * (i & 1)], acc[2 * q + (i >> 1)][t][2 * (i & 1) + 1]));
-#ifndef TTUP_ABLATE_SG
                 if (ok) *(u32x4*)(a.t2 + ((size_t)(b * a.H + oy) * a.W + ox) * 64 + g * 16 + q * 8) = pk[q];
-#endif
             }
-#ifndef TTUP_ABLATE_S3
             f32x4 c3[2] = {b3[0], b3[1]};
 #pragma unroll
             for (int k = 0; k < 2; ++k)
@@ -1209,14 +1111,9 @@ __global__ __launch_bounds__(512) void stem_kernel(StemArgs a) {
                 for (int i = 0; i < 4; ++i) po[i] = relu_pk(pack2(c3[i >> 1][2 * (i & 1)], c3[i >> 1][2 * (i & 1) + 1]));
                 *(u32x4*)(a.a1 + ((size_t)(b * a.H + oy) * a.W + ox) * 32 + g * 8) = po;
             }
-#endif
         }
     };
-#ifdef TTUP_NO_STAGGER
-    constexpr bool STAGGER = false;
-#else
     constexpr bool STAGGER = K4;
-#endif
     const bool late = __builtin_amdgcn_readfirstlane(wave) >= 4;
     f32x4 acc[4][2];
     int eb = 0, eoy0 = 0, eox0 = 0;
@@ -1232,12 +1129,9 @@ __global__ __launch_bounds__(512) void stem_kernel(StemArgs a) {
         const int b = tl / a.tiles_per_img, tt = tl % a.tiles_per_img;
         const int oy0 = (tt / a.tiles_x) * 8, ox0 = (tt % a.tiles_x) * 32;
         const bool t1_inside = oy0 >= 1 && oy0 + 9 <= a.H && ox0 >= 1 && ox0 + 33 <= a.W;          // the whole 10x34 conv1 region lies inside the image
-        TTUP_STAMP_IT(0, it, 0);
-        TTUP_STAMP_IT(0, it, 1);
         // ONE barrier covers "X0 tile complete" (committed in the middle of the previous iteration) and "previous conv2 done reading
         // the T1 tile" (and the weights on the first pass)
         __syncthreads();
-        TTUP_STAMP_IT(0, it, 2);
         // ---------------- conv1 on the 10x34 region (22 groups of 16 pixels, linear pixel index)
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
@@ -1247,7 +1141,6 @@ __global__ __launch_bounds__(512) void stem_kernel(StemArgs a) {
             const int y = pc / TW1, x = pc % TW1;
             const bf16_t* xb = s_x + (y * XW + x) * XS;
             f32x4 acc[4] = {b1[0], b1[1], b1[2], b1[3]};
-#ifndef TTUP_ABLATE_S1
 #pragma unroll
             for (int s5 = 0; s5 < KS1; ++s5) {
                 bf16x8 bfr;
@@ -1261,7 +1154,6 @@ __global__ __launch_bounds__(512) void stem_kernel(StemArgs a) {
                     acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr, acc[m], 0, 0, 0);
                 }
             }
-#endif
             if (p < NP1) {
                 // conv2's zero padding: conv1 outputs outside the image are zeros.  Only border tiles have any (wave-uniform test on the
                 // scalar unit): interior tiles skip the per-lane position test and the eight selects per pixel group (round 5: the
@@ -1282,11 +1174,9 @@ __global__ __launch_bounds__(512) void stem_kernel(StemArgs a) {
                 }
             }
         }
-        TTUP_STAMP_IT(0, it, 3);
         __syncthreads();
         commit();                                        // conv1 was the X0 buffer's last reader; unconditional (see conv64_kernel): on the last tile a stale image nobody reads
         if (it + 2 < my_tiles) issue(it + 2);
-        TTUP_STAMP_IT(0, it, 4);
         // ---------------- conv2 on the 8x32 tile, both 32-channel planes straight from LDS
         // STAGGER (waves 4-7, the second wave of every SIMD): the epilogue of a tile is deferred to the start of the NEXT tile's conv2
         // phase, so it runs under the partner wave's MFMA loop instead of beside the partner's own epilogue (both waves of a SIMD
@@ -1294,11 +1184,8 @@ __global__ __launch_bounds__(512) void stem_kernel(StemArgs a) {
         if (STAGGER && late && pending) epilogue(acc, eb, eoy0, eox0);
 #pragma unroll
         for (int m = 0; m < 4; ++m) { acc[m][0] = b2[m]; acc[m][1] = b2[m]; }
-#ifndef TTUP_ABLATE_S2
         static_assert(TW1 == 34 && NP1 == 340, "conv64_tile_mfma's tile");
         conv64_tile_mfma(acc, bB, s_w2, wave, lane);
-#endif
-        TTUP_STAMP_IT(0, it, 5);
         if (STAGGER && late) { eb = b; eoy0 = oy0; eox0 = ox0; pending = true; }
         else epilogue(acc, b, oy0, ox0);
     }
@@ -1319,15 +1206,14 @@ int launch_stem(const PackedConv& p1, const PackedConv& p2, const PackedConv& p3
     static_assert(SMEM <= 160 * 1024, "LDS budget");
     TTUP_REQUIRE(frames_per_sample == 0 || frames_per_sample == 1 || frames_per_sample == 3, TTUP_EINVAL, "stem: frames per sample must be 0 (X0 records), 1 or 3");
     const bool k4 = p1.k == 1;          // conv1 packed as 128 slots x 1 tap: the 4-step three-frame form (csrc/wasb_net.hip)
-    TTUP_REQUIRE(!k4 || frames_per_sample == 3, TTUP_EINVAL, "stem: the 4-step conv1 packing is the three-frame form");
-    const void* kfn = k4 ? (const void*)stem_kernel<3, true> : frames_per_sample == 3 ? (const void*)stem_kernel<3> : frames_per_sample == 1 ? (const void*)stem_kernel<1> : (const void*)stem_kernel<0>;
+    TTUP_REQUIRE(k4 == (frames_per_sample == 3), TTUP_EINVAL, "stem: the 4-step conv1 packing is the three-frame form");
+    const void* kfn = k4 ? (const void*)stem_kernel<3, true> : frames_per_sample == 1 ? (const void*)stem_kernel<1> : (const void*)stem_kernel<0>;
     if (int rc = ensure_max_lds(kfn, SMEM)) return rc;
     const int grid = a.total_tiles < 256 ? a.total_tiles : 256;
     if (grid == 0) return TTUP_OK;
-    // (a two-wave-group pipeline of the stem, round 5: 14 % slower -- csrc/experiments/rejected_kernels.hip.inc)
-    kernel_note(k4 ? "stem_kernel<3, true>" : frames_per_sample == 3 ? "stem_kernel<3, false>" : frames_per_sample == 1 ? "stem_kernel<1, false>" : "stem_kernel<0, false>");
+    // (a two-wave-group pipeline of the stem, round 5: 14 % slower -- git show d528471:upliftingtabletennis_amd/csrc/experiments/rejected_kernels.hip.inc)
+    kernel_note(k4 ? "stem_kernel<3, true>" : frames_per_sample == 1 ? "stem_kernel<1, false>" : "stem_kernel<0, false>");
     if (k4) hipLaunchKernelGGL((stem_kernel<3, true>), dim3(grid), dim3(512), SMEM, st, a);
-    else if (frames_per_sample == 3) hipLaunchKernelGGL(stem_kernel<3>, dim3(grid), dim3(512), SMEM, st, a);
     else if (frames_per_sample == 1) hipLaunchKernelGGL(stem_kernel<1>, dim3(grid), dim3(512), SMEM, st, a);
     else hipLaunchKernelGGL(stem_kernel<0>, dim3(grid), dim3(512), SMEM, st, a);
     TTUP_LAUNCH_CHECK();
@@ -1360,7 +1246,6 @@ __device__ __forceinline__ int st_off(int pix, int c8) { return pix * 32 + ((c8 
 // reduces row r.  Four barriers per tile.  The fp32 summation order of phase 2b (four partial sums) differs from the
 // layer-wise kernel's, everything else is the same arithmetic.
 __global__ __launch_bounds__(512) void bneck_trans_kernel(FusedArgs a) {
-    prio_young_half();
     constexpr int IH = 10, IW = 34, NPIX = IH * IW;            // 340 halo pixels
     constexpr int NT1 = 22;
     constexpr int W1_U = 3 * 8 * 64, W5_U = 4 * 9 * 64;         // 16-byte units
@@ -1404,7 +1289,6 @@ __global__ __launch_bounds__(512) void bneck_trans_kernel(FusedArgs a) {
         const int tl = xcd_tile(blockIdx.x + it * gridDim.x, a.total_tiles);
         const int b = tl / a.tiles_per_img, tt = tl % a.tiles_per_img;
         const int gy0 = (tt / a.tiles_x) * 8 - 1, gx0 = (tt % a.tiles_x) * 32 - 1;
-#ifndef TTUP_NO_FAST_PREFETCH
         if (gy0 >= 0 && gy0 + IH <= a.H && gx0 >= 0 && gx0 + IW <= a.W) {          // halo tile inside the image: scalar bases + lane constants
             const size_t gp0 = (size_t)(b * a.H + gy0) * a.W + gx0;
             const char* base_a = (const char*)(a.a2 + gp0 * 32);
@@ -1419,7 +1303,6 @@ __global__ __launch_bounds__(512) void bneck_trans_kernel(FusedArgs a) {
             }
             return;
         }
-#endif
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
             const int j = wave + 8 * t;
@@ -1448,14 +1331,12 @@ __global__ __launch_bounds__(512) void bneck_trans_kernel(FusedArgs a) {
         const int tl = xcd_tile(blockIdx.x + it * gridDim.x, a.total_tiles);
         const int b = tl / a.tiles_per_img, tt = tl % a.tiles_per_img;
         const int oy0 = (tt / a.tiles_x) * 8, ox0 = (tt % a.tiles_x) * 32;
-        TTUP_STAMP_IT(1, it, 0);
         __syncthreads();            // previous tile's reduction has read its partial sums (weights visible on the first pass)
-        TTUP_STAMP_IT(1, it, 1);
         // ---------------- phase 1: layer1 halo tile.  Output-channel pairs outermost: a weight fragment read from LDS serves all
         // (up to three) pixel groups of the wave -- 24 fragment reads per wave and tile instead of 72 (the kernel is LDS-bound);
         // every accumulator still sums its three K chunks in the same order
         // (pipelined like conv64_tile_mfma: the two weight fragments of step (q, chunk) + 1 -- and the next pair's bias -- are requested
-        // before the MFMAs of step (q, chunk); -DTTUP_NO_FRAG_PIPELINE: each step reads its own)
+        // before the MFMAs of step (q, chunk))
         bf16x8 afp[2][2];
         f32x4 bqp[2][2];
         auto load_w1 = [&](int st, bf16x8 (&a2)[2]) __attribute__((always_inline)) {          // st = q * 3 + chunk
@@ -1477,14 +1358,9 @@ __global__ __launch_bounds__(512) void bneck_trans_kernel(FusedArgs a) {
 #pragma unroll
             for (int chunk = 0; chunk < 3; ++chunk) {
                 const int st = q * 3 + chunk;
-#ifdef TTUP_NO_FRAG_PIPELINE
-                load_w1(st, afp[st & 1]);
-                if (chunk == 0) load_bq(q, bqp[q & 1]);
-#else
                 if (st + 1 < 12) load_w1(st + 1, afp[(st + 1) & 1]);
                 if (chunk == 0 && q + 1 < 4) load_bq(q + 1, bqp[(q + 1) & 1]);
                 __builtin_amdgcn_sched_barrier(0);
-#endif
                 const bf16x8 af0 = afp[st & 1][0], af1 = afp[st & 1][1];
 #pragma unroll
                 for (int t = 0; t < 3; ++t) {
@@ -1493,9 +1369,7 @@ __global__ __launch_bounds__(512) void bneck_trans_kernel(FusedArgs a) {
                     acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af0, bfr, acc[t][0], 0, 0, 0);
                     acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af1, bfr, acc[t][1], 0, 0, 0);
                 }
-#ifndef TTUP_NO_FRAG_PIPELINE
                 __builtin_amdgcn_sched_barrier(0);
-#endif
             }
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
@@ -1511,9 +1385,7 @@ __global__ __launch_bounds__(512) void bneck_trans_kernel(FusedArgs a) {
                 *(u32x4*)(s_l1 + l1_off(pix, g * 4 + q)) = pk;
             }
         }
-        TTUP_STAMP_IT(1, it, 2);
         __syncthreads();
-        TTUP_STAMP_IT(1, it, 3);
         if (it + 1 < my_tiles) issue_pix(it + 1);               // next tile's pixel fragments: in flight during phases 2a and 2b
         // ---------------- phase 2a: 3x3 s1 128 -> 16 on the LDS tile.  A wave owns two VERTICALLY adjacent 16-pixel groups
         // (rows 2q, 2q+1 of column half ch): the four input rows they touch are read once per (chunk, tap column) and
@@ -1521,36 +1393,6 @@ __global__ __launch_bounds__(512) void bneck_trans_kernel(FusedArgs a) {
         {
             const int q2 = wave >> 1, ch = wave & 1;
             f32x4 acc[2] = {b5, b5};
-#if defined(TTUP_NO_FRAG_PIPELINE) || defined(TTUP_ABL_2A_NOMFMA) || defined(TTUP_ABL_2A_NOLOAD)
-#pragma unroll 2
-            for (int c = 0; c < 4; ++c)
-#pragma unroll
-                for (int dx = 0; dx < 3; ++dx) {
-                    bf16x8 brow[4];
-#pragma unroll
-                    for (int rr = 0; rr < 4; ++rr) {
-#ifdef TTUP_ABL_2A_NOLOAD
-                        brow[rr] = __builtin_bit_cast(bf16x8, pb[rr % 3][dx]);          // (timing ablation: registers instead of LDS reads)
-#else
-                        brow[rr] = *(const bf16x8*)(s_l1 + l1_off((2 * q2 + rr) * IW + ch * 16 + n + dx, c * 4 + g));
-#endif
-                    }
-#pragma unroll
-                    for (int dy = 0; dy < 3; ++dy) {
-#ifdef TTUP_ABL_2A_NOLOAD
-                        const bf16x8 af = af6[dy * 3 + dx];
-#else
-                        const bf16x8 af = *(const bf16x8*)(s_w5 + ((c * 9 + dy * 3 + dx) * 64 + lane) * 8);
-#endif
-#ifdef TTUP_ABL_2A_NOMFMA
-                        asm volatile("" :: "v"(af), "v"(brow[dy]), "v"(brow[dy + 1]));
-#else
-                        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, brow[dy], acc[0], 0, 0, 0);
-                        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, brow[dy + 1], acc[1], 0, 0, 0);
-#endif
-                    }
-                }
-#else
             // pipelined like conv64_tile_mfma: the seven fragments of (chunk, tap column) group j+1 are requested before the six MFMAs
             // of group j, and a scheduling barrier keeps the requests there (same k order per accumulator): phase 2a 5.2 k -> 4.7 k cycles,
             // the kernel -3 % (round 5).  It needs 28 more registers than the plain loop: with the 48 swizzled fragment addresses hoisted out
@@ -1588,7 +1430,6 @@ __global__ __launch_bounds__(512) void bneck_trans_kernel(FusedArgs a) {
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
-#endif
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int oy = oy0 + 2 * q2 + t, ox = ox0 + ch * 16 + n;
@@ -1597,7 +1438,6 @@ __global__ __launch_bounds__(512) void bneck_trans_kernel(FusedArgs a) {
                         u32x2{relu_pk(pack2(acc[t][0], acc[t][1])), relu_pk(pack2(acc[t][2], acc[t][3]))};
             }
         }
-        TTUP_STAMP_IT(1, it, 4);
         // ---------------- phase 2b: 3x3 s2 128 -> 32, K-chunk cc / m-tile m6 of all four output rows
         f32x4 part[4];
         {
@@ -1615,9 +1455,7 @@ __global__ __launch_bounds__(512) void bneck_trans_kernel(FusedArgs a) {
                 }
             }
         }
-        TTUP_STAMP_IT(1, it, 5);
         __syncthreads();            // every wave is done reading the L1 tile: its storage now carries the partial sums
-        TTUP_STAMP_IT(1, it, 6);
         {
             float* s_part = (float*)s_l1;
 #pragma unroll
@@ -1777,7 +1615,7 @@ __device__ __forceinline__ void bb_load_frag16(BBFrag16& f, const bf16_t* wfrag,
 // compiled out in csrc/chain16.h (c16_chain_kernel), this one is the fallback for other term layouts and the cross-check of those.
 template <int R> struct BBRow { static constexpr int value = R; };
 // NWV (C=32 only): waves that share the conv's rows -- `wave` is the wave's index among them (rows wave, wave + NWV, ...).  af32: the C=32
-// conv's 18 weight fragments already in registers (a two-group variant kept them there for the life of the workgroup: csrc/experiments).
+// conv's 18 weight fragments already in registers (a two-group variant kept them there for the life of the workgroup: git show d528471:upliftingtabletennis_amd/csrc/experiments/rejected_kernels.hip.inc).
 template <int C, int RWI, int IOFF, int RHO, int RWO, bool SECOND, int RWR, int ROFF, bool GLOBAL_OUT, int ORW, int OOFF, int NWV = 8>
 __device__ __forceinline__ void bb_conv(const bf16_t* s_in, bf16_t* s_out, const bf16_t* s_res, const bf16_t* wfrag, const float* biasp,
                                         bf16_t* gout, int gy0, int gx0, int H, int W, int b, int wave, int lane,
@@ -1828,11 +1666,7 @@ __device__ __forceinline__ void bb_conv(const bf16_t* s_in, bf16_t* s_out, const
     const int res_ch = (C == 32) ? ((g ^ (((n + ROFF) >> 1) & 3)) << 3) : ((((g >> 1) ^ (((n + ROFF) >> 2) & 1)) << 3) + (g & 1) * 4);
     const int out_ch = (C == 32) ? ((g ^ (((n + OOFF) >> 1) & 3)) << 3) : ((((g >> 1) ^ (((n + OOFF) >> 2) & 1)) << 3) + (g & 1) * 4);
     // zero padding of the next conv: outputs outside the image must be 0; only border tiles have any (wave-uniform test)
-#ifdef TTUP_ABL_NOPAD
-    const bool interior = true;
-#else
     const bool interior = gy0 >= 0 && gy0 + RHO <= H && gx0 >= 0 && gx0 + RWO <= W;
-#endif
     constexpr bool CAN_FOLLOW = GLOBAL_OUT && C == 32;
     bf16x8 af_f = {};
     f32x4 bias_f = {0.f, 0.f, 0.f, 0.f};
@@ -1968,19 +1802,6 @@ __device__ __forceinline__ void bb_conv(const bf16_t* s_in, bf16_t* s_out, const
             for (int xt = 0; xt < XT; ++xt)
 #pragma unroll
                 for (int m = 0; m < MT; ++m) acc[xt][m] = bias[m];
-#ifdef TTUP_NO_FRAG_PIPELINE
-#pragma unroll
-            for (int s = 0; s < KSTEPS; ++s) {
-                bf16x8 bfr[XT];
-#pragma unroll
-                for (int xt = 0; xt < XT; ++xt)
-                    bfr[xt] = (xt < XT - 1) ? *(const bf16x8*)(pk0[s] + yj * ROWSTEP + xt * 16 * C) : *(const bf16x8*)(pkl[s] + yj * ROWSTEP);
-#pragma unroll
-                for (int xt = 0; xt < XT; ++xt)
-#pragma unroll
-                    for (int m = 0; m < MT; ++m) acc[xt][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[s][m], bfr[xt], acc[xt][m], 0, 0, 0);
-            }
-#else
             // pipelined (see conv64_tile_mfma): the pixel fragments of k-step s+1 are requested before the MFMAs of step s
             bf16x8 bfr[2][XT];
             auto load_step = [&](int s, bf16x8 (&bf)[XT]) __attribute__((always_inline)) {
@@ -1999,7 +1820,6 @@ __device__ __forceinline__ void bb_conv(const bf16_t* s_in, bf16_t* s_out, const
                     for (int m = 0; m < MT; ++m) acc[xt][m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[s][m], bfr[s & 1][xt], acc[xt][m], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
-#endif
 #pragma unroll
             for (int xt = 0; xt < XT; ++xt) epi(xt, NWV * yj, y, acc[xt]);
         }
@@ -2033,11 +1853,7 @@ __device__ __forceinline__ void bb_conv(const bf16_t* s_in, bf16_t* s_out, const
         // -- 12 / 7 / 4 groups instead of 30 / 28 / 26 two-thirds-empty ones -- and handed to the waves with spare time: the last
         // wave's band is short or empty (RHO is not a multiple of 8), so it takes the first K0 strip groups, the others one or two each.
         // Same k-step order and operands per output pixel as a band group: bit-identical results.
-#ifdef TTUP_NO_STRIP
-        constexpr bool STRIP = false;
-#else
         constexpr bool STRIP = RAGGED && !GLOBAL_OUT;
-#endif
         constexpr int XTR = STRIP ? XT - 1 : XT;
         if (yb < RHO) {
             bf16x8 fa[XT][RB + 2];
@@ -2088,11 +1904,7 @@ __device__ __forceinline__ void bb_conv(const bf16_t* s_in, bf16_t* s_out, const
             constexpr int ROWS7 = RHO - 7 * RB < 0 ? 0 : (RHO - 7 * RB > RB ? RB : RHO - 7 * RB);      // band rows of the last wave
             // a strip group costs about two band groups (five fragment reads instead of three, one dependent MFMA chain, per-lane
             // addresses): the last wave takes as many as fit in HALF of its band's gap (in band-group units), the rest go round
-#ifdef TTUP_STRIP_K0_FULL
-            constexpr int K0 = NSG < 2 * (RB - ROWS7) ? NSG : 2 * (RB - ROWS7);
-#else
             constexpr int K0 = NSG < RB - ROWS7 ? NSG : RB - ROWS7;
-#endif
             static_assert(NSG - K0 <= 16, "at most two strip groups per wave after the last wave's share");
             auto strip = [&](int j) __attribute__((always_inline)) {
                 int row, col;
@@ -2131,14 +1943,12 @@ __device__ __forceinline__ void bb_conv(const bf16_t* s_in, bf16_t* s_out, const
                 }
                 if (valid) *(u32x2*)(s_out + ((row + OOFF) * ORW + col + OOFF) * C + ((((g >> 1) ^ (((col + OOFF) >> 2) & 1)) << 3) + (g & 1) * 4)) = u32x2{q0, q1};
             };
-#ifndef TTUP_ABL_NOSTRIPWORK
             if (wave == 7) {
 #pragma unroll
                 for (int j = 0; j < K0; ++j) strip(j);
             }
             if (K0 + wave < NSG) strip(K0 + wave);
             if (NSG - K0 > 8 && K0 + 8 + wave < NSG) strip(K0 + 8 + wave);
-#endif
         }
     }
 }
@@ -2148,7 +1958,6 @@ __device__ __forceinline__ void bb_conv(const bf16_t* s_in, bf16_t* s_out, const
 // per workgroup with its 5 weight fragments per conv straight from L2 (persistent variants measured slower there).
 template <int C, int NB, int TH, int TW>
 __global__ __launch_bounds__(512) void bb_chain_kernel(BBArgs a) {
-    prio_young_half();
     constexpr int L = 2 * NB;
     constexpr int R0H = TH + 2 * L, R0W = TW + 2 * L;
     constexpr int SZ_A = R0H * R0W * C, SZ_B = (R0H - 2) * (R0W - 2) * C;
@@ -2183,7 +1992,6 @@ __global__ __launch_bounds__(512) void bb_chain_kernel(BBArgs a) {
         const int tl = xcd_tile(blockIdx.x + it * gridDim.x, a.total_tiles);
         const int b = tl / a.tiles_per_img, tt = tl % a.tiles_per_img;
         const int gy0 = (tt / a.tiles_x) * TH - L, gx0 = (tt % a.tiles_x) * TW - L;
-#ifndef TTUP_NO_FAST_PREFETCH
         if (gy0 >= 0 && gy0 + R0H <= a.H && gx0 >= 0 && gx0 + R0W <= a.W) {
             // the whole halo region lies inside the image (wave-uniform): a scalar base + the per-lane constants -- no coordinates, no
             // bounds tests, no 64-bit per-lane address arithmetic (round 5: the general form below is ~25 vector instructions per load,
@@ -2193,7 +2001,6 @@ __global__ __launch_bounds__(512) void bb_chain_kernel(BBArgs a) {
             for (int k = 0; k < IN_PT; ++k) pin[k] = *(const u32x4*)(base + opaque_u32(voff[k]));
             return;
         }
-#endif
 #pragma unroll
         for (int k = 0; k < IN_PT; ++k) {
             const int u = tid + k * 512;
@@ -2240,9 +2047,7 @@ __global__ __launch_bounds__(512) void bb_chain_kernel(BBArgs a) {
         const int tl = xcd_tile(blockIdx.x + it * gridDim.x, a.total_tiles);
         const int b = tl / a.tiles_per_img, tt = tl % a.tiles_per_img;
         const int oy0 = (tt / a.tiles_x) * TH, ox0 = (tt % a.tiles_x) * TW;
-        if (C == 32) TTUP_STAMP_IT(2, it, 0);
         __syncthreads();                       // previous tile fully consumed (resident weights visible on the first pass)
-        if (C == 32) TTUP_STAMP_IT(2, it, 1);
 #pragma unroll
         for (int k = 0; k < IN_PT; ++k) {
             const int u = tid + k * 512;
@@ -2251,7 +2056,6 @@ __global__ __launch_bounds__(512) void bb_chain_kernel(BBArgs a) {
         if (!WGLOBAL && !RESIDENT) store_wt(0);
         __syncthreads();
         if (it + 1 < my_tiles) issue_in(it + 1);
-        if (C == 32) TTUP_STAMP_IT(2, it, 2);
         if (!WGLOBAL && !RESIDENT) load_wt(1);
         const bf16_t* w0 = WGLOBAL ? a.w[0] : s_wt;
         const bf16_t* w1 = WGLOBAL ? a.w[1] : (RESIDENT ? s_wt + W_UNITS * 8 : s_wt);
@@ -2261,9 +2065,7 @@ __global__ __launch_bounds__(512) void bb_chain_kernel(BBArgs a) {
             const bf16_t* wfl = RESIDENT ? (const bf16_t*)(s_misc + 2 * C + 16) : a.wf;
             const float* bfl = RESIDENT ? s_misc + 2 * C : a.bf;
             bb_conv<C, R0W, 0, R0H - 2, R0W - 2, false, 1, 0, false, R0W - 2, 0>(bufA, bufB, nullptr, w0, bias0, nullptr, oy0 - 1, ox0 - 1, a.H, a.W, b, wave, lane);
-            if (C == 32) TTUP_STAMP_IT(2, it, 3);
             __syncthreads();
-            if (C == 32) TTUP_STAMP_IT(2, it, 4);
             if (!WGLOBAL && !RESIDENT) { store_wt(0); __syncthreads(); if (it + 1 < my_tiles) load_wt(0); }
             // the next tile's input (requested before the first conv) is waited for HERE, in front of the second conv's stores
             if (RESIDENT) prefetch_arrived(pin);
@@ -2302,17 +2104,9 @@ __global__ __launch_bounds__(512, 4) void bb_chain2_kernel(BBArgs a) {       // 
     // 3-D grid (tile column, tile row, image): no division to find the tile
     // (XCD = linear workgroup id % 8 = blockIdx.x % 8 when the row has a multiple of 8 tiles: every XCD then takes a strip of
     // adjacent tile columns through all rows and images instead of every eighth column -- see xcd_tile)
-#ifdef TTUP_NO_XCD_MAP
-    const int bx = blockIdx.x;
-#else
     const int bx = (gridDim.x & 7) == 0 ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
-#endif
     const int b = blockIdx.z, tt = blockIdx.y * a.tiles_x + bx;
     const int oy0 = blockIdx.y * TH, ox0 = bx * TW;
-#ifdef TTUP_TIMING
-    const unsigned long long rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
-    TTUP_STAMP(0);
     BBFrag16 fr;
     {
         // all of the thread's loads are issued before the first LDS store: ONE memory round trip for the tile, not one per unit.
@@ -2334,13 +2128,8 @@ __global__ __launch_bounds__(512, 4) void bb_chain2_kernel(BBArgs a) {       // 
             const int gy = gyb + k * RL;
             // branch-free: an invalid unit reads the tensor's first bytes and is zeroed afterwards (a branch around the load
             // would make every load wait for the one before it)
-#ifdef TTUP_ABL_NOSTAGE
-            const bool ok = false; (void)col_ok; (void)gy;
-            const u32x4 t = u32x4{0u, 0u, 0u, 0u};
-#else
             const bool ok = col_ok && rl + k * RL < R0H && gy >= 0 && gy < a.H;
             const u32x4 t = *(const u32x4*)(ok ? src + k * row_step : a.x);
-#endif
             v[k] = u32x4{ok ? t.x : 0u, ok ? t.y : 0u, ok ? t.z : 0u, ok ? t.w : 0u};
         }
         bf16_t* dst = bufA + bb_off<C>(rl * SA + col, col, c8);
@@ -2351,19 +2140,15 @@ __global__ __launch_bounds__(512, 4) void bb_chain2_kernel(BBArgs a) {       // 
     const bf16x8 idm = bb_identity_frag(lane);
     if (C == 16) bb_load_frag16(fr, a.w[0], a.bias[0], lane);          // first conv's fragments: in flight across the barrier
     __syncthreads();
-    TTUP_STAMP(1);
     const BBFrag16* pre = C == 16 ? &fr : nullptr;
     bb_conv<C, SA, 0, R0H - 2, R0W - 2, false, 1, 0, false, SB, 0>(bufA, bufB, nullptr, a.w[0], a.bias[0], nullptr, oy0 - 3, ox0 - 3, a.H, a.W, b, wave, lane,
                                                                             nullptr, nullptr, nullptr, nullptr, nullptr, pre);
-    TTUP_STAMP(2);
     if (C == 16) bb_load_frag16(fr, a.w[1], a.bias[1], lane);          // next conv's fragments: requested BEFORE the barrier
     __syncthreads();
-    TTUP_STAMP(3);
     bb_conv<C, SB, 0, R0H - 4, R0W - 4, true, SA, 2, false, SA, 2>(bufB, bufA, bufA, a.w[1], a.bias[1], nullptr, oy0 - 2, ox0 - 2, a.H, a.W, b, wave, lane,
                                                                             nullptr, nullptr, nullptr, nullptr, nullptr, pre, nullptr, idm);
     if (C == 16) bb_load_frag16(fr, a.w[2], a.bias[2], lane);
     __syncthreads();
-    TTUP_STAMP(4);
     // The fuse-layer terms that the last conv's epilogue adds (1x1-conv'd lower branches at 1/2, 1/4, 1/8 resolution): the tile's
     // slices (12x16 + 6x8 + 3x4 pixels of 16 channels = 8 KB at most) are requested now, travel while conv3 runs, and are parked in
     // the tail of bufB that conv3's 26x34 output leaves free -- the epilogue then reads them from LDS instead of paying a memory
@@ -2398,13 +2183,9 @@ __global__ __launch_bounds__(512, 4) void bb_chain2_kernel(BBArgs a) {       // 
     if (C == 16 && tunit >= 0) { static_assert(C != 16 || T_FREE * 2 >= ((TH >> 1) * (TW >> 1) + (TH >> 2) * (TW >> 2) + (TH >> 3) * (TW >> 3)) * 32, "bufB tail holds the term slices"); ((u32x4*)s_terms)[tunit] = treg; }
     if (C == 16) bb_load_frag16(fr, a.w[3], a.bias[3], lane);
     __syncthreads();
-    TTUP_STAMP(5);
     BBBest best; best.v = -INFINITY; best.i = 0x7fffffffffffffffLL;
     bb_conv<C, R0W - 6, 0, TH, TW, true, SA, 4, true, 1, 0>(bufB, nullptr, bufA, a.w[3], a.bias[3], a.y, oy0, ox0, a.H, a.W, b, wave, lane,
                                                                    nullptr, nullptr, nullptr, &a, &best, pre, &tlds, idm);
-#ifdef TTUP_TIMING_SPLIT
-    TTUP_STAMP(6);
-#endif
     if (C == 16 && a.heat) {
         // run-time form: lanes -> wave (shuffles) -> workgroup (through the now idle LDS)
 #pragma unroll
@@ -2423,12 +2204,6 @@ __global__ __launch_bounds__(512, 4) void bb_chain2_kernel(BBArgs a) {       // 
             a.pi[(size_t)b * a.tiles_per_img + tt] = best.i;
         }
     }
-#ifndef TTUP_TIMING_SPLIT
-    TTUP_STAMP(6);
-#endif
-#ifdef TTUP_TIMING
-    if (tid == 0 && TTUP_BID < 8192) ttup_tbuf[TTUP_BID * 8 + 7] = __builtin_amdgcn_s_memrealtime() - rt0;      // 100 MHz ticks for the same span
-#endif
 }
 
 template <int C, int TH, int TW>
@@ -2471,11 +2246,7 @@ static int launch_bb_t(const BBArgs& a, int batch, int h, int w, hipStream_t st)
 }
 
 // tile of the C=16 two-block chain (multiples of 8: the fuse-term slices are aligned to the tile)
-#ifndef TTUP_BB2_TH
-#define TTUP_BB2_TH 24
-#define TTUP_BB2_TW 32
-#endif
-constexpr int BB2_TH = TTUP_BB2_TH, BB2_TW = TTUP_BB2_TW;
+constexpr int BB2_TH = 24, BB2_TW = 32;
 int bb_chain_tiles_per_img(int h, int w) { return cdiv(w, BB2_TW) * cdiv(h, BB2_TH); }
 
 int launch_bb_chain(const PackedConv* const* convs, int n_convs, const void* x, void* y, int batch, int h, int w,
@@ -2508,28 +2279,23 @@ int launch_bb_chain(const PackedConv* const* convs, int n_convs, const void* x, 
     // tile shapes tuned on MI355X: larger tiles amortise the per-tile overhead and waste fewer ragged 16-pixel MFMA groups
     if (c == 16 && n_convs == 4) {
         // the epilogue forms the network uses are compiled out in c16_chain_kernel (csrc/chain16.h); anything else -- other term layouts,
-        // TTUP_BB2_GENERIC=1 (read once per process), other -DTTUP_BB2_TH/TW tiles -- takes the run-time form (bb_chain2_kernel)
+        // TTUP_BB2_GENERIC=1 (read once per process) -- takes the run-time form (bb_chain2_kernel)
         static const bool generic = getenv("TTUP_BB2_GENERIC") != nullptr;
-#ifdef TTUP_ABL_EPI4          // timing build (wrong results): the plain chain for every launch
-        return launch_c16_t<24, 32, 4>(a, batch, h, w, st);
-#endif
-        if constexpr (BB2_TH == 24 && BB2_TW == 32) {
-            bool shifts_ok = true;          // the compiled-out forms assume term k at 1/2^(k+1) resolution (HRNet's fuse layers)
-            for (int k = 0; k < a.nsum && k < 3; ++k) shifts_ok = shifts_ok && a.ssh[k] == k + 1;
-            const bool sum_stored = !generic && shifts_ok && a.nsum >= 1 && a.nsum <= 3 && a.ysum && !a.heat;      // a.y (the pre-fuse tensor) optional
-            const bool tail = !generic && shifts_ok && a.nsum == 3 && a.heat && !a.y && !a.ysum;
-            const bool plain = !generic && a.nsum == 0 && !a.heat && !a.ysum && a.y;
-            if (plain) return launch_c16_t<24, 32, 4>(a, batch, h, w, st);
-            if (tail) return launch_c16_t<24, 32, 7>(a, batch, h, w, st);
-            if (sum_stored && a.nsum == 1) return launch_c16_t<24, 32, 1>(a, batch, h, w, st);
-            if (sum_stored && a.nsum == 2) return launch_c16_t<24, 32, 2>(a, batch, h, w, st);
-            if (sum_stored && a.nsum == 3) return launch_c16_t<24, 32, 3>(a, batch, h, w, st);
-        }
+        bool shifts_ok = true;          // the compiled-out forms assume term k at 1/2^(k+1) resolution (HRNet's fuse layers)
+        for (int k = 0; k < a.nsum && k < 3; ++k) shifts_ok = shifts_ok && a.ssh[k] == k + 1;
+        const bool sum_stored = !generic && shifts_ok && a.nsum >= 1 && a.nsum <= 3 && a.ysum && !a.heat;      // a.y (the pre-fuse tensor) optional
+        const bool tail = !generic && shifts_ok && a.nsum == 3 && a.heat && !a.y && !a.ysum;
+        const bool plain = !generic && a.nsum == 0 && !a.heat && !a.ysum && a.y;
+        if (plain) return launch_c16_t<BB2_TH, BB2_TW, 4>(a, batch, h, w, st);
+        if (tail) return launch_c16_t<BB2_TH, BB2_TW, 7>(a, batch, h, w, st);
+        if (sum_stored && a.nsum == 1) return launch_c16_t<BB2_TH, BB2_TW, 1>(a, batch, h, w, st);
+        if (sum_stored && a.nsum == 2) return launch_c16_t<BB2_TH, BB2_TW, 2>(a, batch, h, w, st);
+        if (sum_stored && a.nsum == 3) return launch_c16_t<BB2_TH, BB2_TW, 3>(a, batch, h, w, st);
         return launch_bb2_t<16, BB2_TH, BB2_TW>(a, batch, h, w, st);
     }
     if (c == 16 && n_convs == 2) return launch_bb_t<16, 1, 8, 32>(a, batch, h, w, st);
     if (c == 32 && n_convs == 2) {
-        // (a two-wave-group pipeline of this block, round 5: bit-identical and 1.5 % slower -- csrc/experiments/rejected_kernels.hip.inc)
+        // (a two-wave-group pipeline of this block, round 5: bit-identical and 1.5 % slower -- git show d528471:upliftingtabletennis_amd/csrc/experiments/rejected_kernels.hip.inc)
         return launch_bb_t<32, 1, 22, 30>(a, batch, h, w, st);                   // conv regions 24x32 / 22x30
     }
     set_error("bb_chain: C=%d with %d convs unsupported", c, n_convs);
@@ -2676,24 +2442,16 @@ static int launch_mfma(const PackedConv& p, const ConvLaunch& l, hipStream_t st)
 
 template <int CK, int KS, int S, int TH, int TW>
 static int dispatch_cout(const PackedConv& p, const ConvLaunch& l, hipStream_t st) {
-    static const int nw = getenv("TTUP_CONV_WAVES") ? atoi(getenv("TTUP_CONV_WAVES")) : 8;
     // the stride-2 32 -> 64 conv alone is faster with four-wave workgroups (0.107 against 0.113 ms for its two launches, round 5: twice the
     // workgroups per CU behind its 52-KB staging); every other variant is 5-26 % slower that way
-    static const bool nw_forced = getenv("TTUP_CONV_WAVES") != nullptr;
-    if (!nw_forced && CK == 32 && S == 2 && p.cout == 64) return launch_mfma<CK, 64, KS, S, TH, TW, 4>(p, l, st);
-    if (nw == 8) {
-        switch (p.cout) {
-            case 16: return launch_mfma<CK, 16, KS, S, TH, TW, 8>(p, l, st);
-            case 32: return launch_mfma<CK, 32, KS, S, TH, TW, 8>(p, l, st);
-            case 64: return launch_mfma<CK, 64, KS, S, TH, TW, 8>(p, l, st);
-            case 128: return launch_mfma<CK, 128, KS, S, TH, TW, 8>(p, l, st);
-        }
+    if constexpr (CK == 32 && S == 2) {
+        if (p.cout == 64) return launch_mfma<CK, 64, KS, S, TH, TW, 4>(p, l, st);
     }
     switch (p.cout) {
-        case 16: return launch_mfma<CK, 16, KS, S, TH, TW, 4>(p, l, st);
-        case 32: return launch_mfma<CK, 32, KS, S, TH, TW, 4>(p, l, st);
-        case 64: return launch_mfma<CK, 64, KS, S, TH, TW, 4>(p, l, st);
-        case 128: return launch_mfma<CK, 128, KS, S, TH, TW, 4>(p, l, st);
+        case 16: return launch_mfma<CK, 16, KS, S, TH, TW, 8>(p, l, st);
+        case 32: return launch_mfma<CK, 32, KS, S, TH, TW, 8>(p, l, st);
+        case 64: return launch_mfma<CK, 64, KS, S, TH, TW, 8>(p, l, st);
+        case 128: return launch_mfma<CK, 128, KS, S, TH, TW, 8>(p, l, st);
     }
     set_error("conv: cout %d unsupported", p.cout);
     return TTUP_EINVAL;
@@ -3139,13 +2897,3 @@ int launch_preprocess_crops(const uint8_t* frames, int n_frames, int src_h, int 
 
 }  // namespace ttup
 
-#ifdef TTUP_TIMING
-extern "C" int ttup_debug_read_timing(unsigned long long* out_host, int n_words) {
-    (void)hipDeviceSynchronize();
-    return (int)hipMemcpyFromSymbol(out_host, HIP_SYMBOL(ttup::ttup_tbuf), (size_t)n_words * sizeof(unsigned long long));
-}
-extern "C" int ttup_debug_read_timing_it(unsigned long long* out_host, int n_words) {
-    (void)hipDeviceSynchronize();
-    return (int)hipMemcpyFromSymbol(out_host, HIP_SYMBOL(ttup::ttup_tbuf_it), (size_t)n_words * sizeof(unsigned long long));
-}
-#endif

@@ -247,32 +247,14 @@ __global__ __launch_bounds__(NW * 64) void conv_x3_kernel(ConvX3Args a) {
 #pragma unroll
                     for (int m = 0; m < MT; ++m) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[PA[q]][m], bfr[PB[q]][t], acc[m][t], 0, 0, 0);
         };
-#ifdef TTUP_X3_FRAG_PIPELINE
-        constexpr bool PIPE = MT == 1;          // two fragment sets are 24 (MT + NT) registers: only the 16-cout blocks have them to spare
-#else
-        // measured (round 5, full frame and 256 / 384-pixel crops): the pipelined form is 2-3 % SLOWER here (3.50 against 3.39 ms per
-        // frame) -- it costs the 16-channel kernels an occupancy step (116 -> 132 registers: one workgroup per CU instead of two)
-        constexpr bool PIPE = false;
-#endif
-        if constexpr (PIPE) {
-            // pipelined like conv64_tile_mfma (csrc/conv.hip): the fragments of k-step s+1 are requested before the MFMAs of step s and a
-            // scheduling barrier keeps the requests there -- same summation order per accumulator
-            bf16x8 af[2][3][MT], bfr[2][3][NT];
-            load_step(0, af[0], bfr[0]);
+        // (not pipelined like conv64_tile_mfma in csrc/conv.hip, measured round 5 on full frames and 256 / 384-pixel crops: 2-3 % SLOWER
+        // here, 3.50 against 3.39 ms per frame -- it costs the 16-channel kernels an occupancy step, 116 -> 132 registers: one workgroup
+        // per CU instead of two)
 #pragma unroll
-            for (int s = 0; s < KSTEPS; ++s) {
-                if (s + 1 < KSTEPS) load_step(s + 1, af[(s + 1) & 1], bfr[(s + 1) & 1]);
-                __builtin_amdgcn_sched_barrier(0);
-                mfma_step(af[s & 1], bfr[s & 1]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else {
-#pragma unroll
-            for (int s = 0; s < KSTEPS; ++s) {
-                bf16x8 af[3][MT], bfr[3][NT];
-                load_step(s, af, bfr);
-                mfma_step(af, bfr);
-            }
+        for (int s = 0; s < KSTEPS; ++s) {
+            bf16x8 af[3][MT], bfr[3][NT];
+            load_step(s, af, bfr);
+            mfma_step(af, bfr);
         }
         arrived();
         if (chunk != nchunk - 1) { item = nxt; continue; }
@@ -362,13 +344,12 @@ int launch_conv_x3(const PackedConv& p, const ConvLaunch& l, hipStream_t st) {
     const int mt = p.mt3;
 #define X3_CASE(CK, MT, KS, S, TH, TW, NW) if (p.ck == CK && mt == MT) return launch_x3<CK, MT, KS, S, TH, TW, NW>(p, l, st)
     // pruned launches (the crop net): 16-pixel-wide tiles follow an op's region more closely than 8x32 ones (certification per varied
-    // step 18.2 -> 16.7 ms on one box with the first four; TTUP_X3_WIDE=1 keeps the 32-wide tiles)
-    static const bool wide = getenv("TTUP_X3_WIDE") != nullptr;
-    if (!wide && l.roi.flag && p.k == 3 && p.stride == 1) {
+    // step 18.2 -> 16.7 ms on one box with the first four)
+    if (l.roi.flag && p.k == 3 && p.stride == 1) {
         X3_CASE(32, 1, 3, 1, 16, 16, 8); X3_CASE(32, 2, 3, 1, 16, 16, 8); X3_CASE(32, 4, 3, 1, 8, 16, 8);
         X3_CASE(16, 1, 3, 1, 16, 16, 8); X3_CASE(16, 2, 3, 1, 16, 16, 8); X3_CASE(16, 4, 3, 1, 16, 16, 8);
     }
-    if (!wide && l.roi.flag && p.k == 1 && p.stride == 1) {
+    if (l.roi.flag && p.k == 1 && p.stride == 1) {
         X3_CASE(32, 1, 1, 1, 16, 16, 8); X3_CASE(32, 2, 1, 1, 16, 16, 8); X3_CASE(32, 4, 1, 1, 16, 16, 8);
     }
     if (p.k == 3 && p.stride == 1) {

@@ -2019,24 +2019,17 @@ int run_layer(ttup_uplift* net, const Layer& L, float* x, long long tokens, int 
         a.w_proj = L.proj.w3_dev; a.w_fc1 = L.fc1.w3_dev; a.w_fc2 = L.fc2.w3_dev;
         a.g2 = L.g2; a.b2 = L.b2; a.bias1 = L.fc1.b_dev; a.bias2 = L.fc2.b_dev;
         // 64-token tiles (80 KB of LDS: two workgroups per CU) also for large token counts: 2 % faster at B = 10 000 than the 128-token
-        // tile (160 KB, one workgroup per CU) although every tile then streams the weights again; TTUP_UPLIFT_MLP_BM128=1 selects the latter
-        static const bool bm128 = getenv("TTUP_UPLIFT_MLP_BM128") != nullptr;
-        const bool big = tokens >= 128 * 512 && bm128;
-        const int bm = big ? 128 : 64;
+        // tile (160 KB, one workgroup per CU) although every tile then streams the weights again
+        constexpr int bm = 64;
         const size_t smem = (size_t)3 * bm * 128 * sizeof(uint16_t) + (size_t)bm * 128 * sizeof(float);
         const dim3 grid((unsigned)((tokens + bm - 1) / bm));
-        if (big) {
-            if ((rc = ensure_max_lds((const void*)mlp_block_x3_kernel<2>, 160 * 1024))) return rc;
-            hipLaunchKernelGGL(mlp_block_x3_kernel<2>, grid, dim3(512), smem, st, a);
+        static const bool four = getenv("TTUP_UPLIFT_MLP_4WAVES") != nullptr;          // the round-3 form: 4 waves, two n-tiles each
+        if (four) {
+            if ((rc = ensure_max_lds((const void*)mlp_block_x3_kernel<1>, 160 * 1024))) return rc;
+            hipLaunchKernelGGL(mlp_block_x3_kernel<1>, grid, dim3(256), smem, st, a);
         } else {
-            static const bool four = getenv("TTUP_UPLIFT_MLP_4WAVES") != nullptr;          // the round-3 form: 4 waves, two n-tiles each
-            if (four) {
-                if ((rc = ensure_max_lds((const void*)mlp_block_x3_kernel<1>, 160 * 1024))) return rc;
-                hipLaunchKernelGGL(mlp_block_x3_kernel<1>, grid, dim3(256), smem, st, a);
-            } else {
-                if ((rc = ensure_max_lds((const void*)mlp_block8_x3_kernel, 160 * 1024))) return rc;
-                hipLaunchKernelGGL(mlp_block8_x3_kernel, grid, dim3(512), smem, st, a);
-            }
+            if ((rc = ensure_max_lds((const void*)mlp_block8_x3_kernel, 160 * 1024))) return rc;
+            hipLaunchKernelGGL(mlp_block8_x3_kernel, grid, dim3(512), smem, st, a);
         }
         TTUP_LAUNCH_CHECK();
         return TTUP_OK;

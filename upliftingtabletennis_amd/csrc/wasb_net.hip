@@ -324,7 +324,7 @@ int build(ttup_wasb* net, const std::vector<FoldedConv>& folded) {
         // ... and, for triples, the 4-k-step form of that conv (csrc/conv.hip stem_kernel<3, true>): K = 3 tap rows x 40 slots, slot
         // o of a row = pixel dx = o / 12, frame (o % 12) / 4, colour o % 4 (colour 3 and o >= 36: zero weights), packed as a
         // "1x1 conv with 128 inputs" so that k-step s, lane group g, element j holds k = 32 s + 8 g + j
-        if (net->in_ch == 9 && !getenv("TTUP_STEM_K5")) {
+        if (net->in_ch == 9) {
             FoldedConv c1k = c1;
             c1k.cin = 128; c1k.k = 1; c1k.w.assign((size_t)64 * 128, 0.f);
             for (int co = 0; co < 64; ++co)
@@ -857,9 +857,7 @@ extern "C" int ttup_wasb_time_ops(ttup_wasb* net, int batch, int reps, int max_o
     TTUP_HIP_CHECK(hipEventCreate(&e1));
     int rc = TTUP_OK;
     net->use_lane(0);
-    static const int only_op = getenv("TTUP_TIME_ONLY_OP") ? atoi(getenv("TTUP_TIME_ONLY_OP")) : -1;      // debugging aid: time a single op
     for (int i = 0; i < n && rc == TTUP_OK; ++i) {
-        if (only_op >= 0 && i != only_op) { ms_out[i] = 0.f; op_info(net, i, info_out + 8 * i, nullptr); continue; }
         const Op& op = net->ops[i];
         auto once = [&]() { return (op.kind == Op::UPSUM_HEAD || op.head) ? run_head_op(net, batch, net->heat_scratch, net->argmax_scratch, net->win_scratch, st) : run_op(net, op, batch, st); };
         rc = once();                       // warm-up launch of this op
