@@ -15,12 +15,12 @@ IMAGES_ZIP_FILENAME = "example_images.zip"
 
 
 def ball_detection(model_name='segformerpp_b2', **kwargs):
-    """Loads the ball detection model.  Built here: 'wasb' (the in-tree HRNet); 'segformerpp_*' raises NotImplementedError."""
+    """Loads the ball detection model.  Built here: 'wasb' (the in-tree HRNet) and 'vitpose' (ViTPose-small, fp32); 'segformerpp_*' raises NotImplementedError."""
     return BallDetector(model_name=model_name, **kwargs)
 
 
 def table_detection(model_name='segformerpp_b2', **kwargs):
-    """Loads the table detection model.  Built here: 'hrnet' (the in-tree HRNet); 'segformerpp_*' raises NotImplementedError."""
+    """Loads the table detection model.  Built here: 'hrnet' (the in-tree HRNet) and 'vitpose' (ViTPose-small, fp32); 'segformerpp_*' raises NotImplementedError."""
     return TableDetector(model_name=model_name, **kwargs)
 
 

@@ -48,6 +48,7 @@ extern "C" {
 
 typedef struct ttup_wasb   ttup_wasb;
 typedef struct ttup_uplift ttup_uplift;
+typedef struct ttup_vitpose ttup_vitpose;
 
 int         ttup_version(void);
 /* 16 hex digits: the hash of the sources (every .hip and .h under csrc/, include/ttup.h) and compiler flags this library was built
@@ -202,6 +203,28 @@ int ttup_wasb_set_priority(ttup_wasb* net, int high);
 int ttup_wasb_micro_batch(ttup_wasb* net);
 /* heatmap channels per sample returned by forward: 1 (ball) or 13 (table) */
 int ttup_wasb_out_channels(ttup_wasb* net);
+
+/* ---------------------------------------------------------------- a2': ViTPose-small detector (csrc/vitpose.hip)
+ * Replaces VitPose.forward (balldetection/models/vitpose.py:92-103, classify_invisible=False; tabledetection/models/vitpose.py)
+ * behind `self.model(x)` for model_name 'vitpose'.  fp32 arithmetic throughout (fp32-operand MFMA), no bf16 path.
+ * blob: upliftingtabletennis_amd.weights.pack_vitpose_blob:
+ *   char magic[8]="TTUPVIT1"; int32 in_ch, out_ch, 384, 12 (depth), 12 (heads), 1536 (mlp), 256 (deconv), n_pos;
+ *   float pos_embed[n_pos][384]; patch w[384][in_ch][16][16], b[384];
+ *   12 x { norm1 w,b[384]; qkv w[1152][384], b[1152]; proj w[384][384], b[384]; norm2 w,b[384]; fc1 w[1536][384], b[1536];
+ *          fc2 w[384][1536], b[384] };  last_norm w,b[384];
+ *   deconv 1: w[4][256][4*384], b[256]; deconv 2: w[4][256][4*256], b[256] -- each ConvTranspose2d(k4,s2,p1) + BN folded into four
+ *   2x2 sub-convolutions (phase 2*py+px, reduction index (2*dy+dx)*cin + c; weights.vitpose_fold_head);  final w[out_ch][256], b[out_ch].
+ * height/width: network input (multiples of 16; n_pos must be (height/16)*(width/16)+1); max_batch: largest B of forward;
+ * micro_batch: samples per internal pass (0 = min(8, max_batch)); out_ch 1 (ball) or up to 16 (13: table keypoints). */
+int  ttup_vitpose_create(const void* blob, size_t blob_bytes, int height, int width, int max_batch, int micro_batch,
+                         int in_ch, int out_ch, ttup_vitpose** out);
+void ttup_vitpose_destroy(ttup_vitpose* net);
+int  ttup_vitpose_micro_batch(ttup_vitpose* net);
+/* x_dev: float32 (B,in_ch,H,W) NCHW, 16-byte aligned.  heat_dev: float32 (B,out_ch,H/4,W/4) (nullable).
+ * argmax_dev: int64 (B*out_ch) flat index of the first maximum of each heatmap, win_dev: float32 (B*out_ch,9) zero-padded 3x3
+ * window around it (both or neither). */
+int  ttup_vitpose_forward(ttup_vitpose* net, const float* x_dev, int batch, float* heat_dev, int64_t* argmax_dev,
+                          float* win_dev, void* stream);
 
 /* ---------------------------------------------------------------- a3/a4: heatmap argmax + refine
  * Replaces extract_position_torch_gaussian (ball: helper_balldetection.py:29-110, called at

@@ -65,6 +65,10 @@ SIGNATURES = {
     'ttup_odefit_forward': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _c.c_double, _i, _c.c_double, _vp, _vp, _vp, _vp, _vp]),
     'ttup_odefit_integrate': (_i, [_vp, _vp, _vp, _i, _i, _i, _c.c_double, _vp, _vp, _vp]),
     'ttup_trajgen_select': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'ttup_vitpose_create': (_i, [_vp, _sz, _i, _i, _i, _i, _i, _i, _c.POINTER(_vp)]),
+    'ttup_vitpose_destroy': (None, [_vp]),
+    'ttup_vitpose_micro_batch': (_i, [_vp]),
+    'ttup_vitpose_forward': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

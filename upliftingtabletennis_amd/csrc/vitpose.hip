@@ -1,0 +1,527 @@
+// ViTPose-small detector (balldetection/models/vitpose.py, tabledetection/models/vitpose.py over vit_pose/vit_models): patch
+// embedding, 12 pre-LN transformer blocks, last_norm, two stride-2 deconvolutions + BN + ReLU, final 1x1 conv, then the argmax /
+// 3x3 window of refine.hip.
+//
+// Arithmetic: fp32 throughout.  Every matrix product runs on v_mfma_f32_16x16x4_f32 (fp32 operands, fp32 accumulation: the same
+// products and sums as an fmaf chain, MI355X_MICROARCH "f32-input MFMA"), so the only difference from the reference's fp32 CPU
+// forward is the summation order.  A split-bf16 form on the bf16 matrix pipe (uplift.hip's linear_x3) keeps ~16 operand bits,
+// which is short of this detector's accuracy bar.
+//
+// Kernels
+//   gemm_kernel<AM>      C[m][n] = epilogue(sum_k A[m][k] W[n][k]), W row-major (nn.Linear layout).  64x64 block tile, BK = 32,
+//                        4 waves of 32x32 (2x2 MFMA tiles), A and W tiles through LDS (row stride 36 floats: the MFMA operand
+//                        reads -- 16 rows x 4 k per instruction -- hit 64 distinct banks).  A modes:
+//                          A_DENSE  row-major activations;
+//                          A_LN     the same through LayerNorm (row mean / rstd from ln_stats_kernel, gain + bias per k): the
+//                                   LN prologue of qkv and fc1;
+//                          A_PATCH  implicit im2col of the Conv2d(k16, s16, p2) patch embedding on the NCHW input;
+//                          A_DECONV implicit 2x2 gather of one output phase of ConvTranspose2d(k4, s2, p1) on NHWC input.
+//                        Epilogue: + bias, then GELU (erf) | + residual | + pos_embed[1+tok] + pos_embed[0] | ReLU; rows go to
+//                        a row-major output or, for a deconv phase, to pixel (2y+py, 2x+px) of the NHWC output.
+//   ln_stats_kernel      one wave per token: mean and 1/sqrt(var + 1e-6) of 384 values (two-pass, in registers).
+//   attention_kernel     flash-style, 32-dim heads, 64 queries per workgroup (16 per wave), K/V tiles of 64 keys through LDS,
+//                        online softmax; scores are computed transposed (S^T = K Q^T) so that a lane holds 16 keys of ONE query:
+//                        the row max / sum is 15 in-lane ops + 2 cross-lane steps, and P^T in that layout is directly the B
+//                        operand of O^T += V^T P^T (the k-order of the product is permuted, the sum is the same).  No N x N matrix.
+//   conv1x1_kernel       the final 1x1 conv (256 -> C_out, + bias) from NHWC to the NCHW heatmap, 64 pixels per workgroup staged in
+//                        LDS.  It is not fused into deconv 2: a deconv tile holds 64 of the 256 channels the 1x1 reduces over.
+#include "no_packed_fp32_begin.h"      // this unit runs beside the CNN's chain kernels: no packed fp32 (common.h)
+#include "common.h"
+#include "wasb_net.h"
+
+#include <cstring>
+#include <vector>
+
+#define VITPOSE_MAGIC_STR "TTUPVIT1"
+
+namespace ttup {
+namespace vit {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int DIM = 384, HEADS = 12, HD = 32, MLP = 1536, DEC = 256, DEPTH = 12;
+constexpr int BM = 64, BN = 64, BK = 32, LDS_STRIDE = BK + 4;
+
+enum { A_DENSE = 0, A_LN = 1, A_PATCH = 2, A_DECONV = 3 };
+enum { E_GELU = 1, E_RESID = 2, E_POS = 4, E_RELU = 8 };
+
+struct GemmArgs {
+    const float* a;          // A_DENSE / A_LN: (M, K) row-major; A_PATCH: NCHW input; A_DECONV: NHWC input
+    const float* w;          // (N, K)
+    const float* bias;       // (N)
+    const float* ln_g;       // A_LN: (K) gain, bias
+    const float* ln_b;
+    const float* stats;      // A_LN: (M, 2) mean, rstd
+    const float* res;        // E_RESID: (M, N), may alias out
+    const float* pos;        // E_POS: (N_tok + 1, N)
+    float* out;
+    int M, N, K;
+    int cin, ih, iw;         // A_PATCH: input channels and size; A_DECONV: input channels and (phase) grid h x w
+    int ntok;                // tokens per sample (E_POS)
+    int py, px;              // A_DECONV: output phase
+    int flags;
+};
+
+__device__ __forceinline__ float gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
+
+// Four consecutive k of row m of A (k multiple of 4).
+template <int AM>
+__device__ __forceinline__ f32x4 load_a4(const GemmArgs& p, int m, int k) {
+    f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    if (m >= p.M) return z;
+    if (AM == A_DENSE || AM == A_LN) {
+        f32x4 v = *(const f32x4*)(p.a + (size_t)m * p.K + k);
+        if (AM == A_LN) {
+            const float mu = p.stats[2 * m], rs = p.stats[2 * m + 1];
+            const f32x4 g = *(const f32x4*)(p.ln_g + k), b = *(const f32x4*)(p.ln_b + k);
+            v.x = (v.x - mu) * rs * g.x + b.x;
+            v.y = (v.y - mu) * rs * g.y + b.y;
+            v.z = (v.z - mu) * rs * g.z + b.z;
+            v.w = (v.w - mu) * rs * g.w + b.w;
+        }
+        return v;
+    } else if (AM == A_PATCH) {
+        const int hp = p.ih >> 4, wp = p.iw >> 4, per = hp * wp;
+        const int b = m / per, t = m - b * per, ty = t / wp, tx = t - ty * wp;
+        const int c = k >> 8, ky = (k >> 4) & 15, kx = k & 15;
+        // padding 2 (vit.py:222: 4 + 2 * (ratio // 2 - 1), ratio 1): a quad starts at x = 2 mod 4, so it is read as two float2,
+        // each wholly on one side of a border (x even, W even)
+        const int y = 16 * ty - 2 + ky, x = 16 * tx - 2 + kx;
+        if (y < 0 || y >= p.ih) return z;
+        const float* r = p.a + (((size_t)b * p.cin + c) * p.ih + y) * p.iw;
+        if (x >= 0 && x < p.iw) { const float2 u = *(const float2*)(r + x); z.x = u.x; z.y = u.y; }
+        if (x + 2 >= 0 && x + 2 < p.iw) { const float2 u = *(const float2*)(r + x + 2); z.z = u.x; z.w = u.y; }
+        return z;
+    } else {
+        const int per = p.ih * p.iw;
+        const int b = m / per, t = m - b * per, y = t / p.iw, x = t - y * p.iw;
+        const int tap = k / p.cin, c = k - tap * p.cin;
+        const int iy = y + p.py + (tap >> 1) - 1, ix = x + p.px + (tap & 1) - 1;
+        if (iy < 0 || iy >= p.ih || ix < 0 || ix >= p.iw) return z;
+        return *(const f32x4*)(p.a + (((size_t)b * p.ih + iy) * p.iw + ix) * p.cin + c);
+    }
+}
+
+template <int AM>
+__global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
+    __shared__ float sa[BM * LDS_STRIDE];
+    __shared__ float sw[BN * LDS_STRIDE];
+    const int tid = ttup_tid_x(), lane = tid & 63, wave = tid >> 6;
+    const int m0 = ttup_bid_x() * BM, n0 = ttup_bid_y() * BN;
+    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+    const int lr = lane & 15, lg = lane >> 4;
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    // tile loads: 64 rows x 8 quads per operand, two passes of 32 rows
+    const int lrow = tid >> 3, lq = (tid & 7) * 4;
+    f32x4 ra[2], rw[2];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            ra[h] = load_a4<AM>(p, m0 + lrow + 32 * h, k0 + lq);
+            rw[h] = *(const f32x4*)(p.w + (size_t)(n0 + lrow + 32 * h) * p.K + k0 + lq);
+        }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < p.K; k0 += BK) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            *(f32x4*)(sa + (lrow + 32 * h) * LDS_STRIDE + lq) = ra[h];
+            *(f32x4*)(sw + (lrow + 32 * h) * LDS_STRIDE + lq) = rw[h];
+        }
+        __syncthreads();
+        if (k0 + BK < p.K) fetch(k0 + BK);            // next tile in flight during this tile's MFMAs
+#pragma unroll
+        for (int s = 0; s < BK / 4; ++s) {
+            float av[2], wv[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) av[i] = sa[(wm + 16 * i + lr) * LDS_STRIDE + 4 * s + lg];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) wv[j] = sw[(wn + 16 * j + lr) * LDS_STRIDE + 4 * s + lg];
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], wv[j], acc[i][j], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    // epilogue: lane holds C[wm + 16i + 4*lg + r][wn + 16j + lr]
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int n = n0 + wn + 16 * j + lr;
+        const float bn = p.bias[n];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int m = m0 + wm + 16 * i + 4 * lg + r;
+                if (m >= p.M) continue;
+                float v = acc[i][j][r] + bn;
+                if (p.flags & E_POS) {
+                    const int tok = m % p.ntok;
+                    v = v + p.pos[(size_t)(1 + tok) * p.N + n] + p.pos[n];
+                }
+                if (p.flags & E_GELU) v = gelu(v);
+                if (p.flags & E_RESID) v = p.res[(size_t)m * p.N + n] + v;
+                if (p.flags & E_RELU) v = fmaxf(v, 0.f);
+                size_t o;
+                if (AM == A_DECONV) {
+                    const int per = p.ih * p.iw, b = m / per, t = m - b * per, y = t / p.iw, x = t - y * p.iw;
+                    o = (((size_t)b * 2 * p.ih + 2 * y + p.py) * (2 * p.iw) + 2 * x + p.px) * p.N + n;
+                } else {
+                    o = (size_t)m * p.N + n;
+                }
+                p.out[o] = v;
+            }
+        }
+    }
+}
+
+// one wave per row of DIM floats -> (mean, 1/sqrt(var + eps)), eps 1e-6 (vit.py:274)
+__global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__ x, int M, float* __restrict__ stats) {
+    const int row = ttup_bid_x() * 4 + (ttup_tid_x() >> 6), lane = ttup_tid_x() & 63;
+    if (row >= M) return;
+    const float* r = x + (size_t)row * DIM;
+    float v[DIM / 64];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < DIM / 64; ++i) { v[i] = r[lane + 64 * i]; s += v[i]; }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    const float mu = s * (1.0f / DIM);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < DIM / 64; ++i) { const float d = v[i] - mu; q += d * d; }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) q += __shfl_xor(q, off, 64);
+    if (lane == 0) {
+        stats[2 * row] = mu;
+        stats[2 * row + 1] = 1.0f / sqrtf(q * (1.0f / DIM) + 1e-6f);
+    }
+}
+
+constexpr int AQ = 64, AKV = 64, ASTR = HD + 4;
+
+// qkv: (B*N, 3*DIM) rows [q | k | v], each [head][32]; out: (B*N, DIM) [head][32].  grid (ceil(N/64), HEADS, B), 256 threads.
+__global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ qkv, int N, float scale, float* __restrict__ out) {
+    __shared__ float sk[AKV * ASTR];
+    __shared__ float sv[AKV * ASTR];
+    const int tid = ttup_tid_x(), lane = tid & 63, wave = tid >> 6;
+    const int head = ttup_bid_y(), b = ttup_bid_z();
+    const int lr = lane & 15, lg = lane >> 4;
+    const size_t row0 = (size_t)b * N;
+    const int qi = ttup_bid_x() * AQ + wave * 16 + lr;            // this lane's query
+    // Q^T as the B operand of S^T = K Q^T: step s needs Q[query lr][d = 4s + lg]
+    float q[HD / 4];
+    {
+        const bool ok = qi < N;
+        const float* qr = qkv + (row0 + (ok ? qi : 0)) * (3 * DIM) + head * HD;
+#pragma unroll
+        for (int s = 0; s < HD / 4; ++s) q[s] = ok ? qr[4 * s + lg] * scale : 0.f;
+    }
+    f32x4 o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    float m_run = -INFINITY, l_run = 0.f;
+    const int lrow = tid >> 3, lq = (tid & 7) * 4;                // K/V tile load: 64 keys x 8 quads, two passes of 32 keys
+    for (int kv0 = 0; kv0 < N; kv0 += AKV) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int key = kv0 + lrow + 32 * h;
+            f32x4 kk = {0.f, 0.f, 0.f, 0.f}, vv = {0.f, 0.f, 0.f, 0.f};
+            if (key < N) {
+                const float* kr = qkv + (row0 + key) * (3 * DIM) + DIM + head * HD + lq;
+                kk = *(const f32x4*)kr;
+                vv = *(const f32x4*)(kr + DIM);
+            }
+            *(f32x4*)(sk + (lrow + 32 * h) * ASTR + lq) = kk;
+            *(f32x4*)(sv + (lrow + 32 * h) * ASTR + lq) = vv;
+        }
+        __syncthreads();
+        // S^T tile t: lane holds S^T[key kv0 + 16t + 4lg + r][query lr]
+        f32x4 st[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            st[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < HD / 4; ++s)
+                st[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(sk[(16 * t + lr) * ASTR + 4 * s + lg], q[s], st[t], 0, 0, 0);
+        }
+        float mx = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (kv0 + 16 * t + 4 * lg + r >= N) st[t][r] = -INFINITY;
+                mx = fmaxf(mx, st[t][r]);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+        const float m_new = fmaxf(m_run, mx);                 // finite: every tile holds at least one key < N
+        const float alpha = expf(m_run - m_new);
+        float sum = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                st[t][r] = expf(st[t][r] - m_new);
+                sum += st[t][r];
+            }
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        l_run = l_run * alpha + sum;
+        m_run = m_new;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) o[u] *= alpha;
+        // O^T[d = 16u + 4lg + r][query lr] += sum_key V^T[d][key] P^T[key][query]; k-step (t, r) takes key 16t + 4*(lane/16) + r
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+                    o[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(sv[(16 * t + 4 * lg + r) * ASTR + 16 * u + lr], st[t][r], o[u], 0, 0, 0);
+        __syncthreads();
+    }
+    if (qi < N) {
+        const float inv = 1.0f / l_run;
+        float* orow = out + (row0 + qi) * DIM + head * HD;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) *(f32x4*)(orow + 16 * u + 4 * lg) = o[u] * inv;
+    }
+}
+
+// x: NHWC (B, H, W, DEC) -> heat (B, cout, H, W) = w (cout, DEC) x + bias; 64 pixels per workgroup
+__global__ __launch_bounds__(256) void conv1x1_kernel(const float* __restrict__ x, long long npix, int hw, const float* __restrict__ w,
+                                                      const float* __restrict__ bias, int cout, float* __restrict__ heat) {
+    __shared__ float sx[64 * (64 + 1)];
+    const int tid = ttup_tid_x();
+    const long long p0 = (long long)ttup_bid_x() * 64;
+    const int pl = tid & 63, cg = tid >> 6;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};          // output channels cg, cg+4, cg+8, cg+12
+    for (int c0 = 0; c0 < DEC; c0 += 64) {
+        for (int e = tid; e < 64 * 64; e += 256) {
+            const int pp = e >> 6, c = e & 63;
+            sx[pp * 65 + c] = p0 + pp < npix ? x[(size_t)(p0 + pp) * DEC + c0 + c] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int co = cg + 4 * j;
+            if (co < cout)
+                for (int c = 0; c < 64; ++c) acc[j] += sx[pl * 65 + c] * w[co * DEC + c0 + c];
+        }
+        __syncthreads();
+    }
+    const long long pix = p0 + pl;
+    if (pix >= npix) return;
+    const long long b = pix / hw, t = pix - b * hw;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int co = cg + 4 * j;
+        if (co < cout) heat[((size_t)b * cout + co) * hw + t] = acc[j] + bias[co];
+    }
+}
+
+// last_norm applied once: out[m][k] = (x[m][k] - mean) * rstd * g[k] + b[k], one quad per thread
+__global__ __launch_bounds__(256) void ln_apply_kernel(GemmArgs p) {
+    const long long e = (long long)ttup_bid_x() * 256 + ttup_tid_x();
+    if (e >= (long long)p.M * (DIM / 4)) return;
+    const int m = (int)(e / (DIM / 4)), k = (int)(e - (long long)m * (DIM / 4)) * 4;
+    *(f32x4*)(p.out + (size_t)m * DIM + k) = load_a4<A_LN>(p, m, k);
+}
+
+struct Block {
+    const float *n1w, *n1b, *qkvw, *qkvb, *projw, *projb, *n2w, *n2b, *fc1w, *fc1b, *fc2w, *fc2b;
+};
+
+}  // namespace vit
+}  // namespace ttup
+
+using namespace ttup;
+using namespace ttup::vit;
+
+struct ttup_vitpose {
+    int H, W, hp, wp, ntok, in_ch, out_ch, max_batch, micro;
+    float* weights = nullptr;                   // every tensor of the blob (after the header), device copy
+    const float *pos, *patch_w, *patch_b, *lnw, *lnb, *dc_w[2], *dc_b[2], *fin_w, *fin_b;
+    Block blk[DEPTH];
+    float *x = nullptr, *stats = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *d2 = nullptr, *heat = nullptr;
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+};
+
+static void vitpose_free(ttup_vitpose* n) {
+    for (void* p : {(void*)n->weights, (void*)n->x, (void*)n->stats, (void*)n->qkv, (void*)n->att, (void*)n->hid, (void*)n->d2,
+                    (void*)n->heat, n->ws})
+        if (p) (void)hipFree(p);
+    delete n;
+}
+
+extern "C" int ttup_vitpose_create(const void* blob, size_t blob_bytes, int height, int width, int max_batch, int micro_batch,
+                                   int in_ch, int out_ch, ttup_vitpose** out) {
+    TTUP_REQUIRE(out && blob, TTUP_EINVAL, "ttup_vitpose_create: null argument");
+    *out = nullptr;
+    TTUP_REQUIRE(height >= 16 && width >= 16 && height % 16 == 0 && width % 16 == 0, TTUP_EINVAL,
+                 "ttup_vitpose_create: height and width must be positive multiples of 16 (got %dx%d)", height, width);
+    TTUP_REQUIRE(max_batch >= 1 && micro_batch >= 0 && in_ch >= 1 && out_ch >= 1 && out_ch <= 16, TTUP_EINVAL,
+                 "ttup_vitpose_create: bad max_batch %d / micro_batch %d / in_ch %d / out_ch %d (1..16)", max_batch, micro_batch, in_ch, out_ch);
+    const int ntok = (height / 16) * (width / 16);
+    TTUP_REQUIRE(blob_bytes >= 8 + 32 && memcmp(blob, VITPOSE_MAGIC_STR, 8) == 0, TTUP_EFORMAT, "ttup_vitpose_create: not a ViTPose blob");
+    int hdr[8];
+    memcpy(hdr, (const char*)blob + 8, sizeof hdr);
+    TTUP_REQUIRE(hdr[0] == in_ch && hdr[1] == out_ch, TTUP_EFORMAT, "ttup_vitpose_create: blob has in_ch %d / out_ch %d, asked for %d / %d",
+                 hdr[0], hdr[1], in_ch, out_ch);
+    TTUP_REQUIRE(hdr[2] == DIM && hdr[3] == DEPTH && hdr[4] == HEADS && hdr[5] == MLP && hdr[6] == DEC, TTUP_EFORMAT,
+                 "ttup_vitpose_create: only ViTPose-small (384 / 12 / 12 / 1536 / 256) is built");
+    TTUP_REQUIRE(hdr[7] == ntok + 1, TTUP_EFORMAT, "ttup_vitpose_create: pos_embed has %d rows, a %dx%d input needs %d", hdr[7], height, width, ntok + 1);
+    // float counts in blob order (include/ttup.h)
+    std::vector<size_t> sizes = {(size_t)hdr[7] * DIM, (size_t)DIM * in_ch * 256, DIM};
+    for (int i = 0; i < DEPTH; ++i)
+        for (size_t s : {(size_t)DIM, (size_t)DIM, (size_t)3 * DIM * DIM, (size_t)3 * DIM, (size_t)DIM * DIM, (size_t)DIM, (size_t)DIM, (size_t)DIM,
+                         (size_t)MLP * DIM, (size_t)MLP, (size_t)DIM * MLP, (size_t)DIM})
+            sizes.push_back(s);
+    for (size_t s : {(size_t)DIM, (size_t)DIM, (size_t)4 * DEC * 4 * DIM, (size_t)DEC, (size_t)4 * DEC * 4 * DEC, (size_t)DEC, (size_t)out_ch * DEC, (size_t)out_ch})
+        sizes.push_back(s);
+    size_t total = 0;
+    for (size_t s : sizes) total += s;
+    TTUP_REQUIRE(blob_bytes == 40 + total * 4, TTUP_EFORMAT, "ttup_vitpose_create: blob has %zu bytes, expected %zu", blob_bytes, 40 + total * 4);
+
+    ttup_vitpose* n = new ttup_vitpose();
+    n->H = height; n->W = width; n->hp = height / 16; n->wp = width / 16; n->ntok = ntok;
+    n->in_ch = in_ch; n->out_ch = out_ch; n->max_batch = max_batch;
+    n->micro = micro_batch ? (micro_batch < max_batch ? micro_batch : max_batch) : (max_batch < 8 ? max_batch : 8);
+    auto fail = [&](int rc) { vitpose_free(n); return rc; };
+#define VP_CHECK(expr) do { if ((expr) != hipSuccess) { ttup::set_error("%s failed (%s:%d)", #expr, __FILE__, __LINE__); return fail(TTUP_EHIP); } } while (0)
+    VP_CHECK(hipMalloc((void**)&n->weights, total * 4));
+    VP_CHECK(hipMemcpy(n->weights, (const char*)blob + 40, total * 4, hipMemcpyHostToDevice));
+    const float* p = n->weights;
+    size_t k = 0;
+    auto next = [&]() { const float* r = p; p += sizes[k++]; return r; };
+    n->pos = next(); n->patch_w = next(); n->patch_b = next();
+    for (int i = 0; i < DEPTH; ++i) {
+        Block& b = n->blk[i];
+        b.n1w = next(); b.n1b = next(); b.qkvw = next(); b.qkvb = next(); b.projw = next(); b.projb = next();
+        b.n2w = next(); b.n2b = next(); b.fc1w = next(); b.fc1b = next(); b.fc2w = next(); b.fc2b = next();
+    }
+    n->lnw = next(); n->lnb = next();
+    n->dc_w[0] = next(); n->dc_b[0] = next(); n->dc_w[1] = next(); n->dc_b[1] = next();
+    n->fin_w = next(); n->fin_b = next();
+    const size_t M = (size_t)n->micro * ntok;
+    VP_CHECK(hipMalloc((void**)&n->x, M * DIM * 4));
+    VP_CHECK(hipMalloc((void**)&n->stats, M * 2 * 4));
+    VP_CHECK(hipMalloc((void**)&n->qkv, M * 3 * DIM * 4));
+    VP_CHECK(hipMalloc((void**)&n->att, M * DIM * 4));
+    VP_CHECK(hipMalloc((void**)&n->hid, M * MLP * 4));          // also deconv 1's output (M * 4 * DEC <= M * MLP)
+    VP_CHECK(hipMalloc((void**)&n->d2, M * 16 * DEC * 4));
+    VP_CHECK(hipMalloc((void**)&n->heat, M * 16 * out_ch * 4));
+    n->ws_bytes = ttup_refine_workspace_bytes(n->micro * out_ch, height / 4, width / 4);
+    VP_CHECK(hipMalloc(&n->ws, n->ws_bytes));
+#undef VP_CHECK
+    *out = n;
+    return TTUP_OK;
+}
+
+extern "C" void ttup_vitpose_destroy(ttup_vitpose* net) {
+    if (net) vitpose_free(net);
+}
+
+extern "C" int ttup_vitpose_micro_batch(ttup_vitpose* net) { return net ? net->micro : -1; }
+
+template <int AM>
+static int launch_gemm(const GemmArgs& a, hipStream_t st) {
+    TTUP_REQUIRE(a.N % BN == 0 && a.K % BK == 0, TTUP_EINVAL, "vitpose gemm: N %d / K %d not multiples of %d / %d", a.N, a.K, BN, BK);
+    hipLaunchKernelGGL(gemm_kernel<AM>, dim3(cdiv(a.M, BM), a.N / BN), dim3(256), 0, st, a);
+    TTUP_LAUNCH_CHECK();
+    return TTUP_OK;
+}
+
+
+#define VP_RC(expr) do { int _rc = (expr); if (_rc != TTUP_OK) return _rc; } while (0)
+
+// one micro-batch of nb samples: x (nb, in_ch, H, W) -> heat (nb, out_ch, H/4, W/4)
+static int vitpose_run(ttup_vitpose* n, const float* x_in, int nb, float* heat, hipStream_t st) {
+    const int M = nb * n->ntok;
+    auto args = [&](const float* a, const float* w, const float* bias, float* out, int N, int K, int flags) {
+        GemmArgs g = {};
+        g.a = a; g.w = w; g.bias = bias; g.out = out; g.M = M; g.N = N; g.K = K; g.flags = flags;
+        return g;
+    };
+    // (a) patch embedding + bias + pos_embed[1:] + pos_embed[:1]  (vit.py:222, :366)
+    GemmArgs g = args(x_in, n->patch_w, n->patch_b, n->x, DIM, n->in_ch * 256, E_POS);
+    g.cin = n->in_ch; g.ih = n->H; g.iw = n->W; g.pos = n->pos; g.ntok = n->ntok;
+    VP_RC(launch_gemm<A_PATCH>(g, st));
+    const int ln_grid = cdiv(M, 4);
+    for (int i = 0; i < DEPTH; ++i) {
+        const Block& b = n->blk[i];
+        // x = x + proj(attn(norm1(x)))
+        hipLaunchKernelGGL(ln_stats_kernel, dim3(ln_grid), dim3(256), 0, st, n->x, M, n->stats);
+        TTUP_LAUNCH_CHECK();
+        g = args(n->x, b.qkvw, b.qkvb, n->qkv, 3 * DIM, DIM, 0);
+        g.ln_g = b.n1w; g.ln_b = b.n1b; g.stats = n->stats;
+        VP_RC(launch_gemm<A_LN>(g, st));
+        hipLaunchKernelGGL(attention_kernel, dim3(cdiv(n->ntok, AQ), HEADS, nb), dim3(256), 0, st, n->qkv, n->ntok,
+                           1.0f / sqrtf((float)HD), n->att);
+        TTUP_LAUNCH_CHECK();
+        g = args(n->att, b.projw, b.projb, n->x, DIM, DIM, E_RESID);
+        g.res = n->x;
+        VP_RC(launch_gemm<A_DENSE>(g, st));
+        // x = x + fc2(gelu(fc1(norm2(x))))
+        hipLaunchKernelGGL(ln_stats_kernel, dim3(ln_grid), dim3(256), 0, st, n->x, M, n->stats);
+        TTUP_LAUNCH_CHECK();
+        g = args(n->x, b.fc1w, b.fc1b, n->hid, MLP, DIM, E_GELU);
+        g.ln_g = b.n2w; g.ln_b = b.n2b; g.stats = n->stats;
+        VP_RC(launch_gemm<A_LN>(g, st));
+        g = args(n->hid, b.fc2w, b.fc2b, n->x, DIM, MLP, E_RESID);
+        g.res = n->x;
+        VP_RC(launch_gemm<A_DENSE>(g, st));
+    }
+    // last_norm: materialised once (deconv 1 gathers every token four times per phase)
+    hipLaunchKernelGGL(ln_stats_kernel, dim3(ln_grid), dim3(256), 0, st, n->x, M, n->stats);
+    TTUP_LAUNCH_CHECK();
+    {
+        GemmArgs d = args(n->x, nullptr, nullptr, n->att, DIM, DIM, 0);
+        d.ln_g = n->lnw; d.ln_b = n->lnb; d.stats = n->stats;
+        hipLaunchKernelGGL(ln_apply_kernel, dim3(cdiv(M * (DIM / 4), 256)), dim3(256), 0, st, d);
+        TTUP_LAUNCH_CHECK();
+    }
+    // (d) deconvolutions: four 2x2 phase GEMMs each, BN folded, ReLU; NHWC (nb, hp, wp, 384) -> (nb, 2hp, 2wp, 256) -> (nb, 4hp, 4wp, 256)
+    const float* din = n->att;
+    float* douts[2] = {n->hid, n->d2};
+    int h = n->hp, w = n->wp, cin = DIM;
+    for (int l = 0; l < 2; ++l) {
+        for (int ph = 0; ph < 4; ++ph) {
+            GemmArgs d = args(din, n->dc_w[l] + (size_t)ph * DEC * 4 * cin, n->dc_b[l], douts[l], DEC, 4 * cin, E_RELU);
+            d.M = nb * h * w; d.cin = cin; d.ih = h; d.iw = w; d.py = ph >> 1; d.px = ph & 1;
+            VP_RC(launch_gemm<A_DECONV>(d, st));
+        }
+        din = douts[l]; h *= 2; w *= 2; cin = DEC;
+    }
+    const long long npix = (long long)nb * h * w;
+    hipLaunchKernelGGL(conv1x1_kernel, dim3((unsigned)((npix + 63) / 64)), dim3(256), 0, st, n->d2, npix, h * w, n->fin_w, n->fin_b,
+                       n->out_ch, heat);
+    TTUP_LAUNCH_CHECK();
+    return TTUP_OK;
+}
+
+extern "C" int ttup_vitpose_forward(ttup_vitpose* net, const float* x_dev, int batch, float* heat_dev, int64_t* argmax_dev,
+                                    float* win_dev, void* stream) {
+    TTUP_REQUIRE(net && x_dev, TTUP_EINVAL, "ttup_vitpose_forward: null handle or input");
+    TTUP_REQUIRE(batch >= 0 && batch <= net->max_batch, TTUP_EINVAL, "ttup_vitpose_forward: batch %d outside 0..%d", batch, net->max_batch);
+    TTUP_REQUIRE((argmax_dev == nullptr) == (win_dev == nullptr), TTUP_EINVAL, "ttup_vitpose_forward: argmax and window outputs go together");
+    TTUP_REQUIRE(((uintptr_t)x_dev & 15) == 0, TTUP_EINVAL, "ttup_vitpose_forward: input must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const int hh = net->H / 4, ww = net->W / 4, co = net->out_ch;
+    const size_t in_per = (size_t)net->in_ch * net->H * net->W, heat_per = (size_t)co * hh * ww;
+    for (int b0 = 0; b0 < batch; b0 += net->micro) {
+        const int nb = batch - b0 < net->micro ? batch - b0 : net->micro;
+        float* heat = heat_dev ? heat_dev + b0 * heat_per : net->heat;
+        VP_RC(vitpose_run(net, x_dev + b0 * in_per, nb, heat, st));
+        if (argmax_dev)
+            VP_RC(refine_argmax(heat, nb * co, hh, ww, (long long*)argmax_dev + (size_t)b0 * co, win_dev + (size_t)b0 * co * 9, net->ws,
+                                net->ws_bytes, st));
+    }
+    return TTUP_OK;
+}
+#include "no_packed_fp32_end.h"

@@ -6,7 +6,7 @@ Differences forced by the environment (documented in DESIGN.md):
     inference_balldetection/<name>/model.pt, inference_uplifting/ours/model.pt) or from the folder the reference
     unpacks that zip into under the torch hub directory; when neither exists the constructors raise the reference's
     RuntimeError unless ``TTUP_SYNTHETIC_WEIGHTS=1`` asks for the seeded generators in ``weights.py`` (with a warning);
-  * only the in-tree WASB/HRNet detector is built; 'segformerpp_*' needs the un-vendored
+  * the in-tree WASB/HRNet and ViTPose-small ('vitpose') detectors are built; 'segformerpp_*' needs the un-vendored
     KieDani/SegformerPlusPlus hub repo and raises NotImplementedError;
   * table detection uses the in-tree HRNet ('hrnet'); when a detector's primary SegFormer++ model is unavailable the
     auxiliary in-tree model stands in for both sides of the two-detector agreement filter.
@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, calib, glue, refine, uplift, wasb, weights
+from . import _lib, calib, glue, refine, uplift, vitpose, wasb, weights
 
 HEIGHT, WIDTH = 1080, 1920
 KEYPOINT_VISIBLE = 1
@@ -52,8 +52,12 @@ def _load_ball_checkpoint(model_name):
     path = os.path.join(_weights_dir(), 'inference_balldetection', model_name, 'model.pt')
     if _weights_dir() and os.path.exists(path):
         sd, info = weights.load_checkpoint_state_dict(path)
-        return sd, tuple(info.get('image_resolution', wasb.RESOLUTIONS['wasb'])), int(info.get('in_frames', 3))
+        default = vitpose.RESOLUTIONS['vitpose'] if model_name == 'vitpose' else wasb.RESOLUTIONS['wasb']
+        return sd, tuple(info.get('image_resolution', default)), int(info.get('in_frames', 3))
     _synthetic_or_raise("BallDetector('%s')" % model_name, path if _weights_dir() else '')
+    if model_name == 'vitpose':
+        res = vitpose.RESOLUTIONS['vitpose']
+        return weights.random_vitpose_state_dict(int(os.environ.get('TTUP_SEED', '0')), in_ch=9, out_ch=1, resolution=res), res, 3
     return weights.random_wasb_state_dict(int(os.environ.get('TTUP_SEED', '0')), planted=True), wasb.RESOLUTIONS['wasb'], 3
 
 
@@ -189,10 +193,13 @@ class _CertifiedDetector:
 
 
 class BallDetector(_CertifiedDetector):
+    def __new__(cls, model_name='segformerpp_b2', *a, **k):
+        return super().__new__(ViTPoseBallDetector if cls is BallDetector and model_name == 'vitpose' else cls)
+
     def __init__(self, model_name='segformerpp_b2', max_batch=32, dtype='bf16', lanes=0):
-        if 'segformerpp' in model_name or model_name == 'vitpose':
+        if 'segformerpp' in model_name:
             raise NotImplementedError("detector '%s' depends on code that is not vendored in the reference "
-                                      "(KieDani/SegformerPlusPlus / mmcv); only 'wasb' is built" % model_name)
+                                      "(KieDani/SegformerPlusPlus); only 'wasb' and 'vitpose' are built" % model_name)
         _lib.require_gpu()
         self.device = torch.device('cuda')
         self.resolution = (WIDTH, HEIGHT)
@@ -249,8 +256,11 @@ def _load_table_checkpoint(model_name):
     path = os.path.join(_weights_dir(), 'inference_tabledetection', model_name, 'model.pt')
     if _weights_dir() and os.path.exists(path):
         sd, info = weights.load_checkpoint_state_dict(path)
-        return sd, tuple(info.get('image_resolution', (1280, 704)))
+        return sd, tuple(info.get('image_resolution', vitpose.RESOLUTIONS['vitpose'] if model_name == 'vitpose' else (1280, 704)))
     _synthetic_or_raise("TableDetector('%s')" % model_name, path if _weights_dir() else '')
+    if model_name == 'vitpose':
+        res = vitpose.RESOLUTIONS['vitpose']
+        return weights.random_vitpose_state_dict(int(os.environ.get('TTUP_SEED', '0')) + 1, in_ch=3, out_ch=13, resolution=res), res
     # seeded stand-in: a planted path to every keypoint head, so the heatmaps are PEAKED like a trained detector's (one dominant
     # maximum per keypoint map; on pure noise weights every map is a field of near-ties and the certified argmax degrades to the
     # full-frame fp32 path -- TTUP_TABLE_NOISE_WEIGHTS=1 selects that regime)
@@ -261,9 +271,12 @@ def _load_table_checkpoint(model_name):
 class TableDetector(_CertifiedDetector):
     NO_CERTIFY_ENV = ('TTUP_NO_CERTIFY', 'TTUP_NO_TABLE_CERTIFY')
 
+    def __new__(cls, model_name='segformerpp_b2', *a, **k):
+        return super().__new__(ViTPoseTableDetector if cls is TableDetector and model_name == 'vitpose' else cls)
+
     def __init__(self, model_name='segformerpp_b2', max_batch=8, dtype='bf16', lanes=0):
-        if 'segformerpp' in model_name or model_name == 'vitpose':
-            raise NotImplementedError("detector '%s' depends on code that is not vendored in the reference; only 'hrnet' is built" % model_name)
+        if 'segformerpp' in model_name:
+            raise NotImplementedError("detector '%s' depends on code that is not vendored in the reference; only 'hrnet' and 'vitpose' are built" % model_name)
         _lib.require_gpu()
         self.device = torch.device('cuda')
         self.resolution = (WIDTH, HEIGHT)
@@ -310,6 +323,96 @@ class TableDetector(_CertifiedDetector):
 
     def filter_trajectory(self, table_keypoints, table_keypoints_aux):
         return glue.filter_trajectory_table(table_keypoints, table_keypoints_aux)
+
+
+class ViTPoseBallDetector(BallDetector):
+    """BallDetector('vitpose'): the reference's ViTPose-small ball detector (balldetection/models/vitpose.py, in_frames 3,
+    1152x640, heatmaps at a quarter of that).  It runs the uncertified fp32 path (csrc/vitpose.hip): there is no bf16 ViTPose to
+    certify, so the peaks come from fp32 heatmaps like the reference's and none of the certified-argmax machinery applies."""
+
+    def __init__(self, model_name='vitpose', max_batch=32, dtype='f32', lanes=0):
+        _lib.require_gpu()
+        self.device = torch.device('cuda')
+        self.resolution = (WIDTH, HEIGHT)
+        sd, res, in_frames = _load_ball_checkpoint(model_name)
+        self.model = vitpose.ViTPoseNet(sd, in_ch=3 * in_frames, out_ch=1, resolution=res, max_batch=max_batch)
+        self.model_resolution = res
+        self.max_batch = max_batch
+
+    def _peaks(self, x):
+        w, h = self.model_resolution
+        heat, idx, win = self.model.forward(x, want_heatmap=True, want_peaks=True)
+        # argmax + 3x3 Gaussian refine, table variant (interface.py:113-116), scaled by the heatmap size
+        pos = refine.refine_windows_device(idx, win, h // 4, w // 4, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
+        return pos, heat
+
+    def predict(self, images):
+        """images: list (length B) of [prev, curr, next] BGR uint8 HWC arrays.
+        Returns (pred_pos (B,3) float64 [x, y, confidence] in 1920x1080 px, preds (B,1,H/4,W/4) float32)."""
+        w, h = self.model_resolution
+        pred_pos, preds = [], []
+        for b0 in range(0, len(images), self.max_batch):
+            xs = [wasb.preprocess_triples(torch.from_numpy(np.stack([np.asarray(i) for i in imgs])).to(self.device), (w, h))
+                  for imgs in images[b0:b0 + self.max_batch]]
+            pos, heat = self._peaks(torch.cat(xs))
+            pred_pos.append(pos.cpu().numpy())
+            preds.append(heat.cpu().numpy())
+        if not pred_pos:
+            return np.zeros((0, 3)), np.zeros((0, 1, h // 4, w // 4), np.float32)
+        return np.concatenate(pred_pos, axis=0), np.concatenate(preds, axis=0)
+
+    def predict_clip(self, images):
+        """images = list of N BGR uint8 HWC frames -> pred_pos (N-2, 3), the values `predict` returns for the triples
+        (images[i-1], images[i], images[i+1]); every frame is uploaded once and no heatmap comes back to the host."""
+        n = len(images)
+        if n < 3:
+            return np.zeros((0, 3))
+        w, h = self.model_resolution
+        out = []
+        for t0 in range(0, n - 2, self.max_batch):
+            fr = torch.from_numpy(np.stack([np.asarray(i) for i in images[t0:t0 + self.max_batch + 2]])).to(self.device)
+            out.append(self._peaks(wasb.preprocess_triples(fr, (w, h)))[0].cpu().numpy())
+        return np.concatenate(out, axis=0)
+
+
+class ViTPoseTableDetector(TableDetector):
+    """TableDetector('vitpose'): the reference's ViTPose-small table-keypoint detector (tabledetection/models/vitpose.py, 13
+    heatmaps at a quarter of 1152x640).  Uncertified fp32 path, for the reason ViTPoseBallDetector gives."""
+
+    def __init__(self, model_name='vitpose', max_batch=8, dtype='f32', lanes=0):
+        _lib.require_gpu()
+        self.device = torch.device('cuda')
+        self.resolution = (WIDTH, HEIGHT)
+        self.KEYPOINT_VISIBLE = KEYPOINT_VISIBLE
+        sd, res = _load_table_checkpoint(model_name)
+        self.model = vitpose.ViTPoseNet(sd, in_ch=3, out_ch=13, resolution=res, max_batch=max_batch)
+        self.model_resolution = res
+        self.max_batch = max_batch
+
+    def _keypoints(self, images, want_heatmap):
+        w, h = self.model_resolution
+        pred_pos, preds = [], []
+        for b0 in range(0, len(images), self.max_batch):
+            fr = torch.from_numpy(np.stack([np.asarray(i) for i in images[b0:b0 + self.max_batch]])).to(self.device)
+            heat, idx, win = self.model.forward(wasb.preprocess_frames(fr, (w, h)), want_heatmap=want_heatmap, want_peaks=True)
+            pos = refine.refine_windows_device(idx, win, h // 4, w // 4, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
+            pred_pos.append(pos.cpu().numpy().reshape(-1, 13, 3))
+            if want_heatmap:
+                preds.append(heat.cpu().numpy()[:, None])
+        return pred_pos, preds
+
+    def predict(self, images):
+        """images: list (length B) of BGR uint8 HWC frames -> (pred_pos (B,13,3) float64, preds (B,1,13,H/4,W/4) float32)."""
+        w, h = self.model_resolution
+        pred_pos, preds = self._keypoints(images, True)
+        if not pred_pos:
+            return np.zeros((0, 13, 3)), np.zeros((0, 1, 13, h // 4, w // 4), np.float32)
+        return np.concatenate(pred_pos, axis=0), np.concatenate(preds, axis=0)
+
+    def predict_keypoints(self, images):
+        """`predict` without the heatmaps: (B,13,3) keypoints only."""
+        pred_pos, _ = self._keypoints(images, False)
+        return np.concatenate(pred_pos, axis=0) if pred_pos else np.zeros((0, 13, 3))
 
 
 class UpliftingModel:

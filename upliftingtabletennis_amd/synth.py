@@ -102,3 +102,15 @@ def synth_trajectories(b, t, seed=0, pad=1, fps_choices=(50.0, 60.0, 120.0)):
         times[i, :t] = (np.arange(t) / fps).astype(np.float32)
         mask[i, :t] = 1.0
     return ball, table, mask, times
+
+
+def vitpose_inputs(seed, b, c, h, w, amp=4.0, sigma=2.0, noise=0.5):
+    """(b,c,h,w) float32 detector inputs in the normalised range (noise plus one bright Gaussian blob per sample, on every
+    channel) and the (b,2) blob centres (x, y): seeded test inputs of the ViTPose fixtures (tools/make_goldens_vitpose.py)."""
+    rng = np.random.default_rng(seed)
+    x = (rng.standard_normal((b, c, h, w)) * noise).astype(np.float32)
+    cen = np.stack([rng.uniform(8, w - 8, b), rng.uniform(8, h - 8, b)], 1)
+    gy, gx = np.meshgrid(np.arange(h), np.arange(w), indexing='ij')
+    for i in range(b):
+        x[i] += (amp * np.exp(-((gx - cen[i, 0]) ** 2 + (gy - cen[i, 1]) ** 2) / (2 * sigma ** 2))).astype(np.float32)
+    return x, cen

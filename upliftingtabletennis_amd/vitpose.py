@@ -1,0 +1,72 @@
+"""ViTPose-small detector behind ``self.model(x)`` for model_name 'vitpose' (balldetection/models/vitpose.py,
+tabledetection/models/vitpose.py; factories balldetection/train.py:263-265, tabledetection/train.py:218-220).
+
+The forward runs in libttup.so (csrc/vitpose.hip) in fp32 arithmetic; this class only owns the handle and the torch-side buffers.
+``forward(x) -> (heatmaps (B, C_out, H/4, W/4) float32, None)``, as the reference wrapper returns ``(seg_out, None)``.
+"""
+import ctypes
+
+import torch
+
+from . import _lib, weights
+
+RESOLUTIONS = {'vitpose': weights.VITPOSE_RESOLUTION}      # (width, height): balldetection/config.py:82, tabledetection/config.py:76
+
+
+class ViTPoseNet:
+    """``in_ch`` 9 (ball: three frames) or 3 (table); ``out_ch`` 1 (ball) or 13 (table keypoints).  ``resolution`` is (W, H)."""
+
+    def __init__(self, state_dict, in_ch=9, out_ch=1, resolution=weights.VITPOSE_RESOLUTION, max_batch=32, micro_batch=0,
+                 device='cuda:0'):
+        _lib.require_gpu()
+        self.device = torch.device(device)
+        self.W, self.H = int(resolution[0]), int(resolution[1])
+        self.IN_CH, self.OUT_CH = int(in_ch), int(out_ch)
+        self.max_batch = int(max_batch)
+        self.dtype = 'f32'
+        self._lib = _lib.load()
+        blob = weights.pack_vitpose_blob(state_dict, in_ch=self.IN_CH, out_ch=self.OUT_CH)
+        self._handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttup_vitpose_create(blob, len(blob), self.H, self.W, self.max_batch, int(micro_batch), self.IN_CH, self.OUT_CH,
+                                               ctypes.byref(self._handle))
+        _lib.check(rc)
+        self.micro_batch = self._lib.ttup_vitpose_micro_batch(self._handle)
+
+    def eval(self):
+        return self
+
+    def to(self, *a, **k):
+        return self
+
+    def __del__(self):
+        h, self._handle = getattr(self, '_handle', None), None
+        if h:
+            self._lib.ttup_vitpose_destroy(h)
+
+    def forward(self, x, want_heatmap=True, want_peaks=False):
+        """x (B, in_ch, H, W) float -> (heat or None, None), or with want_peaks (heat or None, argmax (B*C_out,) int64 flat index
+        into each (H/4, W/4) map, windows (B*C_out, 9) float32 zero-padded 3x3 around it)."""
+        if x.dim() != 4 or x.shape[1] != self.IN_CH or x.shape[2] != self.H or x.shape[3] != self.W:
+            raise ValueError('expected input (B,%d,%d,%d), got %s' % (self.IN_CH, self.H, self.W, tuple(x.shape)))
+        x = x.to(self.device, torch.float32).contiguous()
+        b, k, h, w = x.shape[0], self.OUT_CH, self.H // 4, self.W // 4
+        heats, idxs, wins = [], [], []
+        for b0 in range(0, b, self.max_batch):
+            xb = x[b0:b0 + self.max_batch]
+            nb = xb.shape[0]
+            heat = torch.empty((nb, k, h, w), dtype=torch.float32, device=self.device) if want_heatmap else None
+            idx = torch.empty((nb * k,), dtype=torch.int64, device=self.device) if want_peaks else None
+            win = torch.empty((nb * k, 9), dtype=torch.float32, device=self.device) if want_peaks else None
+            with torch.cuda.device(self.device):
+                rc = self._lib.ttup_vitpose_forward(self._handle, _lib.ptr(xb), nb, _lib.ptr(heat), _lib.ptr(idx), _lib.ptr(win), _lib.stream_ptr())
+            _lib.check(rc)
+            heats.append(heat); idxs.append(idx); wins.append(win)
+        heat = (torch.cat(heats) if heats else torch.empty((0, k, h, w), dtype=torch.float32, device=self.device)) if want_heatmap else None
+        if want_peaks:
+            if not idxs:
+                return heat, torch.empty((0,), dtype=torch.int64, device=self.device), torch.empty((0, 9), dtype=torch.float32, device=self.device)
+            return heat, torch.cat(idxs), torch.cat(wins)
+        return heat, None
+
+    __call__ = forward
