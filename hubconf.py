@@ -3,7 +3,9 @@
 
 The reference's default detector 'segformerpp_b2' lives in an un-vendored hub repo (KieDani/SegformerPlusPlus) and is
 not built here: the default call raises the documented NotImplementedError naming the in-tree alternative
-('wasb' / 'hrnet'); ``full_pipeline()`` uses the in-tree detectors on both sides of the agreement filter."""
+('wasb' / 'hrnet').  ``full_pipeline()`` runs the in-tree WASB / HRNet detectors as the primaries; without an aux detector each
+primary also fills the aux side of its agreement filter.  ``full_pipeline_two_detectors()`` (an addition; ``full_pipeline`` keeps
+the reference's signature) puts ViTPose-small there, so that the filters compare two different detectors as the reference's do."""
 dependencies = ['torch', 'numpy']
 
 import os  # noqa: E402
@@ -25,8 +27,16 @@ def table_detection(model_name='segformerpp_b2', **kwargs):
 
 
 def full_pipeline():
-    """Loads the end-to-end pipeline (ball + table detection, refine, uplift)."""
+    """Loads the end-to-end pipeline (ball + table detection, refine, uplift).  The WASB / HRNet primaries fill both sides of each
+    agreement filter; see full_pipeline_two_detectors."""
     return TableTennisPipeline()
+
+
+def full_pipeline_two_detectors(ball_aux='vitpose', table_aux='vitpose'):
+    """`full_pipeline` with a second detector in the agreement filters, as the reference runs them.  ball_aux / table_aux: 'vitpose'
+    (ViTPose-small) or None (the WASB / HRNet primary on both sides: nothing is rejected for disagreement); 'segformerpp_*' raises
+    NotImplementedError, anything else ValueError."""
+    return TableTennisPipeline(ball_aux=ball_aux, table_aux=table_aux)
 
 
 def download_example_images(local_folder='example_images'):

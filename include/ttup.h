@@ -225,6 +225,11 @@ int  ttup_vitpose_micro_batch(ttup_vitpose* net);
  * window around it (both or neither). */
 int  ttup_vitpose_forward(ttup_vitpose* net, const float* x_dev, int batch, float* heat_dev, int64_t* argmax_dev,
                           float* win_dev, void* stream);
+/* frames_dev: n_frames BGR uint8 (src_h,src_w,3) HWC frames on the device, any size.  Samples: n_frames - 2 triples (t, t+1, t+2)
+ * for a 9-channel handle, n_frames frames for a 3-channel one (at most max_batch).  Outputs as ttup_vitpose_forward, bit-identical
+ * to it on ttup_preprocess_triples / ttup_preprocess_frames of the same frames; each frame is pre-processed once. */
+int  ttup_vitpose_forward_frames(ttup_vitpose* net, const uint8_t* frames_dev, int n_frames, int src_h, int src_w, float* heat_dev,
+                                 int64_t* argmax_dev, float* win_dev, void* stream);
 
 /* ---------------------------------------------------------------- a3/a4: heatmap argmax + refine
  * Replaces extract_position_torch_gaussian (ball: helper_balldetection.py:29-110, called at

@@ -69,6 +69,7 @@ SIGNATURES = {
     'ttup_vitpose_destroy': (None, [_vp]),
     'ttup_vitpose_micro_batch': (_i, [_vp]),
     'ttup_vitpose_forward': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    'ttup_vitpose_forward_frames': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

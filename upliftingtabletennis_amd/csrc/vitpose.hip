@@ -15,7 +15,9 @@
 //                          A_LN     the same through LayerNorm (row mean / rstd from ln_stats_kernel, gain + bias per k): the
 //                                   LN prologue of qkv and fc1;
 //                          A_PATCH  implicit im2col of the Conv2d(k16, s16, p2) patch embedding on the NCHW input;
-//                          A_DECONV implicit 2x2 gather of one output phase of ConvTranspose2d(k4, s2, p1) on NHWC input.
+//                          A_DECONV implicit 2x2 gather of one output phase of ConvTranspose2d(k4, s2, p1) on NHWC input;
+//                          A_PATCH_FRAMES  A_PATCH on per-frame records (3, H, W): channel c of sample b is channel c % 3 of
+//                                   record b + c / 3, so consecutive triples share their frames' records (forward_frames).
 //                        Epilogue: + bias, then GELU (erf) | + residual | + pos_embed[1+tok] + pos_embed[0] | ReLU; rows go to
 //                        a row-major output or, for a deconv phase, to pixel (2y+py, 2x+px) of the NHWC output.
 //   ln_stats_kernel      one wave per token: mean and 1/sqrt(var + 1e-6) of 384 values (two-pass, in registers).
@@ -42,11 +44,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int DIM = 384, HEADS = 12, HD = 32, MLP = 1536, DEC = 256, DEPTH = 12;
 constexpr int BM = 64, BN = 64, BK = 32, LDS_STRIDE = BK + 4;
 
-enum { A_DENSE = 0, A_LN = 1, A_PATCH = 2, A_DECONV = 3 };
+enum { A_DENSE = 0, A_LN = 1, A_PATCH = 2, A_DECONV = 3, A_PATCH_FRAMES = 4 };
 enum { E_GELU = 1, E_RESID = 2, E_POS = 4, E_RELU = 8 };
 
 struct GemmArgs {
-    const float* a;          // A_DENSE / A_LN: (M, K) row-major; A_PATCH: NCHW input; A_DECONV: NHWC input
+    const float* a;          // A_DENSE / A_LN: (M, K) row-major; A_PATCH: NCHW input; A_DECONV: NHWC input; A_PATCH_FRAMES: (n, 3, H, W)
     const float* w;          // (N, K)
     const float* bias;       // (N)
     const float* ln_g;       // A_LN: (K) gain, bias
@@ -80,7 +82,7 @@ __device__ __forceinline__ f32x4 load_a4(const GemmArgs& p, int m, int k) {
             v.w = (v.w - mu) * rs * g.w + b.w;
         }
         return v;
-    } else if (AM == A_PATCH) {
+    } else if (AM == A_PATCH || AM == A_PATCH_FRAMES) {
         const int hp = p.ih >> 4, wp = p.iw >> 4, per = hp * wp;
         const int b = m / per, t = m - b * per, ty = t / wp, tx = t - ty * wp;
         const int c = k >> 8, ky = (k >> 4) & 15, kx = k & 15;
@@ -88,7 +90,8 @@ __device__ __forceinline__ f32x4 load_a4(const GemmArgs& p, int m, int k) {
         // each wholly on one side of a border (x even, W even)
         const int y = 16 * ty - 2 + ky, x = 16 * tx - 2 + kx;
         if (y < 0 || y >= p.ih) return z;
-        const float* r = p.a + (((size_t)b * p.cin + c) * p.ih + y) * p.iw;
+        const size_t plane = AM == A_PATCH ? (size_t)b * p.cin + c : (size_t)(b + c / 3) * 3 + c % 3;
+        const float* r = p.a + (plane * p.ih + y) * p.iw;
         if (x >= 0 && x < p.iw) { const float2 u = *(const float2*)(r + x); z.x = u.x; z.y = u.y; }
         if (x + 2 >= 0 && x + 2 < p.iw) { const float2 u = *(const float2*)(r + x + 2); z.z = u.x; z.w = u.y; }
         return z;
@@ -348,13 +351,14 @@ struct ttup_vitpose {
     const float *pos, *patch_w, *patch_b, *lnw, *lnb, *dc_w[2], *dc_b[2], *fin_w, *fin_b;
     Block blk[DEPTH];
     float *x = nullptr, *stats = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *d2 = nullptr, *heat = nullptr;
+    float* frames = nullptr;                    // forward_frames: fp32 (3, H, W) records of one micro-batch's frames
     void* ws = nullptr;
     size_t ws_bytes = 0;
 };
 
 static void vitpose_free(ttup_vitpose* n) {
     for (void* p : {(void*)n->weights, (void*)n->x, (void*)n->stats, (void*)n->qkv, (void*)n->att, (void*)n->hid, (void*)n->d2,
-                    (void*)n->heat, n->ws})
+                    (void*)n->heat, (void*)n->frames, n->ws})
         if (p) (void)hipFree(p);
     delete n;
 }
@@ -416,6 +420,8 @@ extern "C" int ttup_vitpose_create(const void* blob, size_t blob_bytes, int heig
     VP_CHECK(hipMalloc((void**)&n->hid, M * MLP * 4));          // also deconv 1's output (M * 4 * DEC <= M * MLP)
     VP_CHECK(hipMalloc((void**)&n->d2, M * 16 * DEC * 4));
     VP_CHECK(hipMalloc((void**)&n->heat, M * 16 * out_ch * 4));
+    if (in_ch % 3 == 0)          // one micro-batch of samples spans micro + in_ch / 3 - 1 frames
+        VP_CHECK(hipMalloc((void**)&n->frames, (size_t)(n->micro + in_ch / 3 - 1) * 3 * height * width * 4));
     n->ws_bytes = ttup_refine_workspace_bytes(n->micro * out_ch, height / 4, width / 4);
     VP_CHECK(hipMalloc(&n->ws, n->ws_bytes));
 #undef VP_CHECK
@@ -440,8 +446,9 @@ static int launch_gemm(const GemmArgs& a, hipStream_t st) {
 
 #define VP_RC(expr) do { int _rc = (expr); if (_rc != TTUP_OK) return _rc; } while (0)
 
-// one micro-batch of nb samples: x (nb, in_ch, H, W) -> heat (nb, out_ch, H/4, W/4)
-static int vitpose_run(ttup_vitpose* n, const float* x_in, int nb, float* heat, hipStream_t st) {
+// one micro-batch of nb samples: x (nb, in_ch, H, W) -> heat (nb, out_ch, H/4, W/4); with from_frames x holds the samples'
+// per-frame records instead (A_PATCH_FRAMES)
+static int vitpose_run(ttup_vitpose* n, const float* x_in, int nb, float* heat, hipStream_t st, bool from_frames = false) {
     const int M = nb * n->ntok;
     auto args = [&](const float* a, const float* w, const float* bias, float* out, int N, int K, int flags) {
         GemmArgs g = {};
@@ -451,7 +458,7 @@ static int vitpose_run(ttup_vitpose* n, const float* x_in, int nb, float* heat, 
     // (a) patch embedding + bias + pos_embed[1:] + pos_embed[:1]  (vit.py:222, :366)
     GemmArgs g = args(x_in, n->patch_w, n->patch_b, n->x, DIM, n->in_ch * 256, E_POS);
     g.cin = n->in_ch; g.ih = n->H; g.iw = n->W; g.pos = n->pos; g.ntok = n->ntok;
-    VP_RC(launch_gemm<A_PATCH>(g, st));
+    VP_RC(from_frames ? launch_gemm<A_PATCH_FRAMES>(g, st) : launch_gemm<A_PATCH>(g, st));
     const int ln_grid = cdiv(M, 4);
     for (int i = 0; i < DEPTH; ++i) {
         const Block& b = n->blk[i];
@@ -518,6 +525,37 @@ extern "C" int ttup_vitpose_forward(ttup_vitpose* net, const float* x_dev, int b
         const int nb = batch - b0 < net->micro ? batch - b0 : net->micro;
         float* heat = heat_dev ? heat_dev + b0 * heat_per : net->heat;
         VP_RC(vitpose_run(net, x_dev + b0 * in_per, nb, heat, st));
+        if (argmax_dev)
+            VP_RC(refine_argmax(heat, nb * co, hh, ww, (long long*)argmax_dev + (size_t)b0 * co, win_dev + (size_t)b0 * co * 9, net->ws,
+                                net->ws_bytes, st));
+    }
+    return TTUP_OK;
+}
+
+// n_frames BGR uint8 HWC frames (device, any size) -> the outputs of ttup_vitpose_forward on ttup_preprocess_triples (in_ch 9) or
+// ttup_preprocess_frames (in_ch 3) of them, bit for bit: each micro-batch's frames are pre-processed once into fp32 records (the
+// same launch_preprocess) and the patch embedding gathers its triples from them.
+extern "C" int ttup_vitpose_forward_frames(ttup_vitpose* net, const uint8_t* frames_dev, int n_frames, int src_h, int src_w,
+                                           float* heat_dev, int64_t* argmax_dev, float* win_dev, void* stream) {
+    TTUP_REQUIRE(net && frames_dev, TTUP_EINVAL, "ttup_vitpose_forward_frames: null handle or frames");
+    TTUP_REQUIRE(net->frames, TTUP_EINVAL, "ttup_vitpose_forward_frames: in_ch %d is not a whole number of BGR frames", net->in_ch);
+    TTUP_REQUIRE(src_h > 0 && src_w > 0, TTUP_EINVAL, "ttup_vitpose_forward_frames: bad frame size %dx%d", src_h, src_w);
+    const int nf = net->in_ch / 3;
+    TTUP_REQUIRE(n_frames >= nf, TTUP_EINVAL, "ttup_vitpose_forward_frames: %d frames, a %d-channel sample needs at least %d", n_frames,
+                 net->in_ch, nf);
+    const int batch = n_frames - nf + 1;
+    TTUP_REQUIRE(batch <= net->max_batch, TTUP_EINVAL, "ttup_vitpose_forward_frames: %d samples, the handle takes at most %d", batch, net->max_batch);
+    TTUP_REQUIRE((argmax_dev == nullptr) == (win_dev == nullptr), TTUP_EINVAL, "ttup_vitpose_forward_frames: argmax and window outputs go together");
+    hipStream_t st = (hipStream_t)stream;
+    const int hh = net->H / 4, ww = net->W / 4, co = net->out_ch;
+    const size_t heat_per = (size_t)co * hh * ww;
+    for (int b0 = 0; b0 < batch; b0 += net->micro) {
+        const int nb = batch - b0 < net->micro ? batch - b0 : net->micro;
+        // records of frames b0 .. b0 + nb + nf - 2 (<= micro + nf - 1 of them: the workspace)
+        VP_RC(launch_preprocess(frames_dev, n_frames, src_h, src_w, net->H, net->W, net->frames, TTUP_LAYOUT_NCHW_F32, TTUP_DTYPE_F32, b0,
+                                nb + nf - 1, 1, st));
+        float* heat = heat_dev ? heat_dev + b0 * heat_per : net->heat;
+        VP_RC(vitpose_run(net, net->frames, nb, heat, st, true));
         if (argmax_dev)
             VP_RC(refine_argmax(heat, nb * co, hh, ww, (long long*)argmax_dev + (size_t)b0 * co, win_dev + (size_t)b0 * co * 9, net->ws,
                                 net->ws_bytes, st));

@@ -8,8 +8,9 @@ Differences forced by the environment (documented in DESIGN.md):
     RuntimeError unless ``TTUP_SYNTHETIC_WEIGHTS=1`` asks for the seeded generators in ``weights.py`` (with a warning);
   * the in-tree WASB/HRNet and ViTPose-small ('vitpose') detectors are built; 'segformerpp_*' needs the un-vendored
     KieDani/SegformerPlusPlus hub repo and raises NotImplementedError;
-  * table detection uses the in-tree HRNet ('hrnet'); when a detector's primary SegFormer++ model is unavailable the
-    auxiliary in-tree model stands in for both sides of the two-detector agreement filter.
+  * table detection uses the in-tree HRNet ('hrnet'); the pipeline's primaries are WASB / HRNet (the reference's SegFormer++
+    primaries are unavailable), and its aux slots hold ViTPose-small (`TableTennisPipeline(ball_aux='vitpose',
+    table_aux='vitpose')`) or, by default, the primary itself -- which then stands in for both sides of the agreement filter.
 Quirks kept on purpose: BGR frames are fed to the detector as they come (interface.py:96,104-110); the
 *table* variant of the refine is used on the hub surface (interface.py:116); visibility is always 1.
 """
@@ -340,11 +341,8 @@ class ViTPoseBallDetector(BallDetector):
         self.max_batch = max_batch
 
     def _peaks(self, x):
-        w, h = self.model_resolution
         heat, idx, win = self.model.forward(x, want_heatmap=True, want_peaks=True)
-        # argmax + 3x3 Gaussian refine, table variant (interface.py:113-116), scaled by the heatmap size
-        pos = refine.refine_windows_device(idx, win, h // 4, w // 4, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
-        return pos, heat
+        return self._refine(idx, win), heat
 
     def predict(self, images):
         """images: list (length B) of [prev, curr, next] BGR uint8 HWC arrays.
@@ -367,12 +365,15 @@ class ViTPoseBallDetector(BallDetector):
         n = len(images)
         if n < 3:
             return np.zeros((0, 3))
-        w, h = self.model_resolution
         out = []
         for t0 in range(0, n - 2, self.max_batch):
             fr = torch.from_numpy(np.stack([np.asarray(i) for i in images[t0:t0 + self.max_batch + 2]])).to(self.device)
-            out.append(self._peaks(wasb.preprocess_triples(fr, (w, h)))[0].cpu().numpy())
+            out.append(self._refine(*self.model.forward_frames(fr)[1:]).cpu().numpy())
         return np.concatenate(out, axis=0)
+
+    def _refine(self, idx, win):
+        w, h = self.model_resolution
+        return refine.refine_windows_device(idx, win, h // 4, w // 4, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
 
 
 class ViTPoseTableDetector(TableDetector):
@@ -390,16 +391,19 @@ class ViTPoseTableDetector(TableDetector):
         self.max_batch = max_batch
 
     def _keypoints(self, images, want_heatmap):
-        w, h = self.model_resolution
         pred_pos, preds = [], []
         for b0 in range(0, len(images), self.max_batch):
             fr = torch.from_numpy(np.stack([np.asarray(i) for i in images[b0:b0 + self.max_batch]])).to(self.device)
-            heat, idx, win = self.model.forward(wasb.preprocess_frames(fr, (w, h)), want_heatmap=want_heatmap, want_peaks=True)
-            pos = refine.refine_windows_device(idx, win, h // 4, w // 4, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
-            pred_pos.append(pos.cpu().numpy().reshape(-1, 13, 3))
+            heat, idx, win = self.model.forward_frames(fr, want_heatmap=want_heatmap)
+            pred_pos.append(self._refine(idx, win).cpu().numpy().reshape(-1, 13, 3))
             if want_heatmap:
                 preds.append(heat.cpu().numpy()[:, None])
         return pred_pos, preds
+
+    def _refine(self, idx, win):
+        # argmax + 3x3 Gaussian refine, table variant (interface.py:113-116), scaled by the heatmap size
+        w, h = self.model_resolution
+        return refine.refine_windows_device(idx, win, h // 4, w // 4, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
 
     def predict(self, images):
         """images: list (length B) of BGR uint8 HWC frames -> (pred_pos (B,13,3) float64, preds (B,1,13,H/4,W/4) float32)."""
@@ -473,8 +477,22 @@ class UpliftingModel:
         return pred_rotation_local.squeeze(0), pred_position.squeeze(0)
 
 
+def _aux_class(name, vit_cls, what):
+    """The detector class an aux slot name selects: None (share the primary), 'vitpose', or the un-vendored 'segformerpp_*'."""
+    if name is None or name == 'vitpose':
+        return None if name is None else vit_cls
+    if isinstance(name, str) and 'segformerpp' in name:
+        raise NotImplementedError("%s '%s' depends on code that is not vendored in the reference; only 'vitpose' (or None) is built" % (what, name))
+    raise ValueError("%s must be None or 'vitpose', got %r" % (what, name))
+
+
 class TableTennisPipeline:
-    def __init__(self, max_batch=32):
+    def __init__(self, max_batch=32, ball_aux=None, table_aux=None):
+        """ball_aux / table_aux: the second detector of each agreement filter (interface.py:254-289 runs two per frame).  None: the
+        primary stands in for both sides (the filters then keep every detection the primary makes); 'vitpose': ViTPose-small, fed
+        from the same single upload of the clip.  The primaries stay WASB / HRNet, and the filters keep the primaries' positions."""
+        ball_cls = _aux_class(ball_aux, ViTPoseBallDetector, 'ball_aux')
+        table_cls = _aux_class(table_aux, ViTPoseTableDetector, 'table_aux')
         _lib.require_gpu()
         self.device = torch.device('cuda')
         self.CHUNK = int(os.environ.get('TTUP_HUB_CHUNK', self.CHUNK))
@@ -486,9 +504,10 @@ class TableTennisPipeline:
         # 808-811; GPU_MAX_HW_QUEUES=8 with one lane each: 843)
         lanes = int(os.environ.get('TTUP_HUB_LANES', '1'))
         self.ball_detector = BallDetector(model_name='wasb', max_batch=max(max_batch, self.CHUNK_LONG), lanes=lanes)
-        self.ball_detector_aux = self.ball_detector       # the primary SegFormer++ detector is not available offline
         self.table_detector = TableDetector(model_name='hrnet', max_batch=max(16, self.CHUNK_LONG), lanes=lanes)
-        self.table_detector_aux = self.table_detector
+        # the reference's primary SegFormer++ detectors are not available offline: without an aux detector the primary fills both slots
+        self.ball_detector_aux = ball_cls('vitpose', max_batch=max(max_batch, self.CHUNK_LONG)) if ball_cls else self.ball_detector
+        self.table_detector_aux = table_cls('vitpose', max_batch=max(16, self.CHUNK_LONG)) if table_cls else self.table_detector
         # the overlapped clip path runs both detectors side by side: the table detector goes first on the GPU, so that its
         # host-side consumer (the DBSCAN keypoint filter) overlaps with the rest of the ball detector
         self.table_detector.model.set_priority(True)
@@ -509,12 +528,16 @@ class TableTennisPipeline:
     CHUNK_LONG = 64     # ... of clips of at least four chunks, after their first chunk: a detector call drains at its end, so long clips take fewer, larger calls (256 frames: 868 -> see DESIGN.md 11)
     FIRST = 24          # frames of the first chunk (a short first chunk -- 8 frames -- was measured 5 ms SLOWER per clip: its one-micro-batch calls run at half the batched rate)
 
-    def _clip_detections(self, images, want_table, table_consumer=None):
+    def _clip_detections(self, images, want_table, table_consumer=None, return_aux=False):
         """Ball positions (N-2,3) and table keypoints ((N,13,3), or what `table_consumer` makes of them) of one clip with everything overlapped: the frames are staged in
         pinned memory and uploaded ONCE in chunks on a copy stream; while chunk k+1 is staged and copied, the table detector
         runs on chunk k on its own stream and the ball detector on the triples whose three frames are already resident on a
-        third; the host blocks only at the end.  Same values as `predict_clip` / `predict_keypoints` (same kernels per frame)."""
+        third; the host blocks only at the end.  Same values as `predict_clip` / `predict_keypoints` (same kernels per frame).
+        ViTPose aux detectors run on a third stream from the same upload; `table_consumer` then gets (keypoints, aux keypoints).
+        return_aux: (pos, kp, pos_aux, kp_aux), the aux values raw (the primary's where the primary fills the aux slot)."""
         n, dev = len(images), self.device
+        ba = self.ball_detector_aux if isinstance(self.ball_detector_aux, ViTPoseBallDetector) else None
+        ta = self.table_detector_aux if want_table and isinstance(self.table_detector_aux, ViTPoseTableDetector) else None
         import time as _time
         tr = self.__dict__.get('_trace')          # tools/hub_trace.py: host time stamps (ms since the call) of the clip path's stages
         t00 = _time.perf_counter()
@@ -535,6 +558,8 @@ class TableTennisPipeline:
         if self._pinned[0].shape[1:] != (h0, w0, 3):
             self._pinned = [torch.empty((CP, h0, w0, 3), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
             self._pin_free = [None, None]
+        if (ba is not None or ta is not None) and 'aux' not in st:
+            st['aux'] = torch.cuda.Stream(dev)          # the ViTPose passes (the long pole): the HRNet streams run beside them
         cur = torch.cuda.current_stream(dev)
         for s in st.values():
             s.wait_stream(cur)
@@ -545,7 +570,8 @@ class TableTennisPipeline:
         bounds = [0, F0] + list(range(F0 + C, n, C)) + ([n] if n > F0 else [])
         bounds = sorted(set(bounds))
         ball_out, table_out, ball_calls, table_calls = [], [], [], []
-        t_next = 0                        # first triple not yet submitted
+        ball_aux_out, table_aux_out, kpa_host, ev_ta = [], [], None, None
+        t_next = a_next = 0               # first triple not yet submitted (primary, aux)
         ev = None
         for ci, (c0, c1) in enumerate(zip(bounds[:-1], bounds[1:])):
             pin = self._pinned[ci % 2]
@@ -585,9 +611,24 @@ class TableTennisPipeline:
                     info = bd.model.certify_info() if bd.model.certified else None
                     ball_calls.append((t_next, nt, idx, win, status, info, bd.model.eps if bd.model.certified else None))
                 t_next += nt
+            if ba is not None or ta is not None:
+                with torch.cuda.stream(st['aux']):
+                    st['aux'].wait_event(ev)
+                    if ta is not None:
+                        table_aux_out.append(ta._refine(*ta.model.forward_frames(frames[c0:c1])[1:]))
+                        if c1 == n:           # the aux keypoints go to the host ahead of the last ball pass: the keypoint filter overlaps it
+                            kpa_dev = torch.cat(table_aux_out).reshape(-1, 13, 3)
+                            kpa_host = torch.empty(kpa_dev.shape, dtype=kpa_dev.dtype, pin_memory=True)
+                            kpa_host.copy_(kpa_dev, non_blocking=True)
+                            ev_ta = torch.cuda.Event(); ev_ta.record()
+                    if ba is not None and a_next < c1 - 2:
+                        ball_aux_out.append(ba._refine(*ba.model.forward_frames(frames[a_next:c1])[1:]))
+                        a_next = c1 - 2
         uploaded = [ev]
         mark('all calls enqueued')
         frames.record_stream(st['ball']); frames.record_stream(st['table'])
+        if ba is not None or ta is not None:
+            frames.record_stream(st['aux'])
         # eps audit of the certified argmax: a random triple of the clip on the fp32 twin, on its own stream next to the detectors
         audit = None
         picks = bd._audit_picks(n - 2)
@@ -629,7 +670,14 @@ class TableTennisPipeline:
                     pos = refine.refine_windows_device(c['idx'].reshape(-1), c['win'].reshape(-1, 9), th, tw, td.resolution[0], td.resolution[1], _lib.REFINE_TABLE)
                     kp_np[c['f0']:c['f1']] = pos.cpu().numpy().reshape(-1, 13, 3)
             mark('table calls settled')
-            kp = table_consumer(kp_np) if table_consumer is not None else kp_np.copy()
+            if ta is not None:
+                ev_ta.synchronize()
+                mark('aux table keypoints on the host')
+                kp_aux = kpa_host.numpy().copy()
+                kp = table_consumer(kp_np, kp_aux) if table_consumer is not None else kp_np.copy()
+            else:
+                kp_aux = kp_np.copy() if return_aux else None
+                kp = table_consumer(kp_np) if table_consumer is not None else kp_np.copy()
             mark('keypoint filter done')
         for s in st.values():
             cur.wait_stream(s)
@@ -640,7 +688,10 @@ class TableTennisPipeline:
             ball_out.append(refine.refine_windows_device(c['idx'], c['win'], bh, bw, bd.resolution[0], bd.resolution[1], _lib.REFINE_TABLE))
         pos = torch.cat(ball_out).cpu().numpy() if ball_out else np.zeros((0, 3))
         mark('ball calls settled, positions on the host')
-        return pos, kp
+        if not return_aux:
+            return pos, kp
+        pos_aux = (torch.cat(ball_aux_out).cpu().numpy() if ball_aux_out else np.zeros((0, 3))) if ba is not None else pos
+        return pos, kp, pos_aux, (kp_aux if want_table else None)
 
     STAGE_THREADS = 4
 
@@ -661,13 +712,16 @@ class TableTennisPipeline:
         list(pool.map(lambda k: np.copyto(dst[k - c0], images[k]), range(c0, c1)))
 
     def _predict(self, images, fps, table_keypoints):
-        overlapped = (self.ball_detector_aux is self.ball_detector and self.table_detector_aux is self.table_detector and len(images) >= 3
+        # the overlapped clip path feeds an aux detector only when it is ViTPose (or the primary itself)
+        overlapped = ((self.ball_detector_aux is self.ball_detector or isinstance(self.ball_detector_aux, ViTPoseBallDetector))
+                      and (self.table_detector_aux is self.table_detector or isinstance(self.table_detector_aux, ViTPoseTableDetector))
+                      and len(images) >= 3
                       and self.table_detector.max_batch >= self.CHUNK_LONG and self.ball_detector.max_batch >= self.CHUNK_LONG
                       and os.environ.get('TTUP_HUB_SERIAL') != '1')
         if overlapped:
-            ball_positions, kp = self._clip_detections(images, want_table=table_keypoints is None,
-                                                       table_consumer=lambda k: self.table_detector_aux.filter_trajectory(k, k))
-            ball_positions_aux = ball_positions
+            ball_positions, kp, ball_positions_aux, _ = self._clip_detections(
+                images, want_table=table_keypoints is None, return_aux=True,
+                table_consumer=lambda k, k_aux=None: self.table_detector_aux.filter_trajectory(k, k if k_aux is None else k_aux))
             if table_keypoints is None:
                 table_keypoints = kp
         else:

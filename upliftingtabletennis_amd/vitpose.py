@@ -3,6 +3,7 @@ tabledetection/models/vitpose.py; factories balldetection/train.py:263-265, tabl
 
 The forward runs in libttup.so (csrc/vitpose.hip) in fp32 arithmetic; this class only owns the handle and the torch-side buffers.
 ``forward(x) -> (heatmaps (B, C_out, H/4, W/4) float32, None)``, as the reference wrapper returns ``(seg_out, None)``.
+``forward_frames(frames_u8)`` takes the uint8 frames themselves (the hub's single upload) and gives the same peaks bit for bit.
 """
 import ctypes
 
@@ -68,5 +69,32 @@ class ViTPoseNet:
                 return heat, torch.empty((0,), dtype=torch.int64, device=self.device), torch.empty((0, 9), dtype=torch.float32, device=self.device)
             return heat, torch.cat(idxs), torch.cat(wins)
         return heat, None
+
+    def forward_frames(self, frames_u8, want_heatmap=False):
+        """(N, h, w, 3) uint8 BGR device frames (any h, w; a slice of a larger tensor is fine) -> (heat or None, argmax (S*C_out,) int64,
+        windows (S*C_out, 9) float32) of the S = N - 2 triples (in_ch 9) or N frames (in_ch 3): the values `forward` gives on
+        wasb.preprocess_triples / preprocess_frames of the same frames, with every frame pre-processed once.  Split at max_batch
+        samples (consecutive calls share in_ch / 3 - 1 frames)."""
+        if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3:
+            raise ValueError('frames must be a uint8 (N,h,w,3) tensor')
+        nf = self.IN_CH // 3
+        if self.IN_CH != 3 * nf:
+            raise ValueError('a %d-channel handle does not take BGR frames' % self.IN_CH)
+        frames_u8 = frames_u8.to(self.device).contiguous()
+        n, fh, fw = frames_u8.shape[0], frames_u8.shape[1], frames_u8.shape[2]
+        if n < nf:
+            raise ValueError('%d frames: a %d-channel sample needs at least %d' % (n, self.IN_CH, nf))
+        s, k = n - nf + 1, self.OUT_CH
+        heat = torch.empty((s, k, self.H // 4, self.W // 4), dtype=torch.float32, device=self.device) if want_heatmap else None
+        idx = torch.empty((s * k,), dtype=torch.int64, device=self.device)
+        win = torch.empty((s * k, 9), dtype=torch.float32, device=self.device)
+        for b0 in range(0, s, self.max_batch):
+            nb = min(self.max_batch, s - b0)
+            with torch.cuda.device(self.device):
+                rc = self._lib.ttup_vitpose_forward_frames(self._handle, _lib.ptr(frames_u8[b0:b0 + nb + nf - 1]), nb + nf - 1, fh, fw,
+                                                           _lib.ptr(heat[b0:b0 + nb]) if want_heatmap else None, _lib.ptr(idx[b0 * k:]),
+                                                           _lib.ptr(win[b0 * k:]), _lib.stream_ptr())
+            _lib.check(rc)
+        return heat, idx, win
 
     __call__ = forward
