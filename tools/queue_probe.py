@@ -36,11 +36,11 @@ torch.cuda.synchronize()
 fps = bench.TRIPLES * steps / (time.perf_counter() - t0)
 
 w = pipe.worker
-named = [('submit0', w._sub['streams'][0]), ('submit1', w._sub['streams'][1])]
+named = [('submit0', w.submit_streams()['streams'][0]), ('submit1', w.submit_streams()['streams'][1])]
 ints = w.net.internal_streams()
 named += [('lane%d' % k, s) for k, s in enumerate(ints[:-1])] + [('crops', ints[-1])]
-if getattr(w.net, '_audit_stream', None) is not None:
-    named.append(('audit', w.net._audit_stream))
+if w.cert.audit_stream is not None:
+    named.append(('audit', w.cert.audit_stream))
 named.append(('default', torch.cuda.default_stream(dev)))
 CYC = 20_000_000
 

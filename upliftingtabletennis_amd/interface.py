@@ -76,124 +76,54 @@ def _load_uplift_checkpoint():
     return weights.random_uplift_state_dict(int(os.environ.get('TTUP_SEED', '0')), 'large'), 'large', 'global'
 
 
-class _CertifiedDetector:
-    """What the two detectors share: the certified argmax (csrc/certify.hip) of a bf16 handle -- first estimate of the error bound
-    eps on the first input, the running audit, widening + re-certification, repair of over-budget heatmaps on the fp32 twin.
-    `self.model` is a wasb.WASBNet (one heatmap per triple) or a wasb.MyHRNet (13 keypoint heatmaps per frame)."""
-    AUDIT_EVERY = 256          # samples per audited sample (see _audit_picks)
+class _HubDetector:
+    """What BallDetector and TableDetector share: `cert`, the certified argmax of their bf16 handle -- a wasb.EpsAudit, where the
+    protocol lives: eps measured on the first input, one sample per 256 audited after it; None when certification is off -- and the
+    detector calls that go through it."""
     NO_CERTIFY_ENV = ('TTUP_NO_CERTIFY',)
 
-    def _calibrate(self, frames=None, x=None):
-        """A first estimate of the bf16 path's error bound eps is measured on the first input this detector sees, against the fp32
-        path; the audits (`_audit_picks`, the crops' candidate errors) keep checking it on later inputs and widen it when one comes
-        within the safety factor.  Every returned index is the fp32 argmax as long as eps bounds the frame's error."""
-        m = self.model
-        if m.certified or m.dtype != 'bf16' or any(os.environ.get(k) == '1' for k in self.NO_CERTIFY_ENV):
-            return
-        exact = os.environ.get('TTUP_EXACT_WINDOWS') == '1'
-        if frames is None:
-            n = min(2, x.shape[0])
-            hb = m._heat(x[:n])
-            twin = m._twin()
-            err = max(float(wasb.max_abs_diff(hb[k], twin._heat(x[k:k + 1])[0]).item()) for k in range(n))
-            m.set_certify(m.HEADROOM * err, exact_windows=exact)
-            m.audit_state = dict(audited_frames=n, max_err_seen=err, widened=0)
-        else:
-            m.calibrate(frames, n=4, exact_windows=exact)
+    def _init_cert(self):
+        off = self.model.dtype != 'bf16' or any(os.environ.get(k) == '1' for k in self.NO_CERTIFY_ENV)
+        self.cert = None if off else wasb.EpsAudit(self.model, every=0 if os.environ.get('TTUP_NO_AUDIT') == '1' else 256, seed=0)
 
-    def _audit_picks(self, n_samples):
-        """One random sample per AUDIT_EVERY samples this detector has processed is re-run on the fp32 twin (eps audit)."""
-        if not self.model.certified or n_samples <= 0 or os.environ.get('TTUP_NO_AUDIT') == '1':
-            return []
-        rng = self.__dict__.setdefault('_audit_rng', np.random.default_rng(0))
-        self._since_audit = self.__dict__.get('_since_audit', 0) + n_samples
-        picks = []
-        while self._since_audit >= self.AUDIT_EVERY:
-            self._since_audit -= self.AUDIT_EVERY
-            picks.append(int(rng.integers(n_samples)))
-        return picks
+    @property
+    def AUDIT_EVERY(self):
+        """Samples per audited sample."""
+        return self.cert.every
+
+    @AUDIT_EVERY.setter
+    def AUDIT_EVERY(self, every):
+        self.cert.every = self.cert.every_fast = int(every)
+
+    def _calibrate(self, frames_u8=None, x=None):
+        """First eps, on the first input this detector sees (a uint8 clip or a float input); a no-op after it."""
+        if self.cert is not None and not self.model.certified:
+            self.model.calibrate(frames_u8, n=4 if x is None else 2, exact_windows=os.environ.get('TTUP_EXACT_WINDOWS') == '1', x=x)
 
     def _certified_forward(self, x):
-        """(heat, idx, win) of the float input x (the `self.model(x)` seam of `predict`): peaks from the certified argmax -- the fp32
-        index the reference's torch.argmax returns -- under an audited eps."""
-        m = self.model
+        """(heat, idx, win) of the float input x (the `self.model(x)` seam of `predict`): the certified argmax -- the fp32 index the
+        reference's torch.argmax returns -- or, with certification off, the handle's own."""
         self._calibrate(x=x)
-        picks = self._audit_picks(x.shape[0])
-        while True:
-            heat, idx, win = wasb.WASBNet.forward(m, x, want_heatmap=True, want_peaks=True)
-            if not m.certified:
-                return heat, idx, win
-            status, info = m.certify_status(idx.shape[0]), m.certify_info()          # (masked status: the float entry re-runs the whole chunk on a widening)
-            err = m.note_error(m.decode_info(info.cpu().numpy())[1])
-            for t in picks:        # eps audit: the bf16 heatmaps of a random sample against the fp32 twin
-                err = max(err, m.note_error(float(wasb.max_abs_diff(heat[t], m._twin()._heat(x[t:t + 1])[0]).item()), 1))
-            picks = []
-            if m.eps_violated(err):
-                m.widen_eps(err)
-                continue
-            m.fix_uncertified(idx, win, x=x, status=status)
-            return heat, idx, win
+        if self.cert is None:
+            return wasb.WASBNet.forward(self.model, x, want_heatmap=True, want_peaks=True)
+        c = self.cert.run(x=x)
+        return c.heat, c.idx, c.win
 
     def _certified_peaks(self, fr):
-        """(idx, win) of the samples of the uint8 device clip `fr` (one forward call), certified under an audited eps."""
-        m = self.model
-        picks = self._audit_picks(fr.shape[0] - (m.NF - 1))
-        while True:
-            audit = m.audit_async(fr, picks) if picks else None
-            eps_used = m.eps if m.certified else None
-            _, idx, win = m.forward_frames(fr, want_heatmap=False)
-            if not m.certified:
-                return idx, win
-            status, info = m.certify_status(idx.shape[0], raw=True), m.certify_info()
-            err = m.note_error(m.decode_info(info.cpu().numpy())[1])
-            if audit is not None:
-                err = max(err, m.audit_result(audit))
-            picks = []
-            st = status.cpu().numpy()
-            if m.eps_violated(err):
-                m.widen_eps(err)
-                todo = m.recertify_subset(idx, win, st, eps_used, fr)       # only the heatmaps whose guard band is not empty
-                if todo is None:
-                    continue                                              # eps grew past the guard factor: the whole call again
-            m.fix_uncertified(idx, win, frames_u8=fr, status=st)
-            return idx, win
+        """(idx, win) of the samples of the uint8 device clip `fr` (one forward call), certified like `_certified_forward`."""
+        if self.cert is None:
+            return self.model.forward_frames(fr)[1:]
+        c = self.cert.run(fr)
+        return c.idx, c.win
 
-    def _settle_calls(self, calls, frames, audit=None):
-        """Host-side second half of certified forward calls that were only ENQUEUED (the overlapped clip path): `calls` = list of
-        dicts {f0, f1 (frame range of the call's input), idx, win, status (flags, host or device), info, eps}.  Folds the calls'
-        candidate errors and the audit into eps, re-certifies the heatmaps certified under a stale eps, repairs over-budget heatmaps
-        on the fp32 twin.  Returns the set of call positions whose idx / win changed (idx / win are updated in place, or replaced in
-        the dict when a whole call was run again)."""
-        m = self.model
-        changed = set()
-        if not m.certified or not calls:
-            return changed
-        err = m.note_error(max(m.decode_info(np.asarray(c['info'].cpu() if torch.is_tensor(c['info']) else c['info']))[1] for c in calls))
-        if audit is not None:
-            err = max(err, m.audit_result(audit))
-        if m.eps_violated(err):
-            m.widen_eps(err)
-        for k, c in enumerate(calls):
-            st = c['status'].cpu().numpy() if torch.is_tensor(c['status']) else np.array(c['status'])
-            fr = frames[c['f0']:c['f1']]
-            if c['eps'] < m.eps:
-                # an audit found eps too small: the heatmaps of this call whose guard band is not empty are run again under the
-                # widened eps; the whole call only when eps grew past the guard factor (audited, blocking; rare)
-                todo = m.recertify_subset(c['idx'], c['win'], st, c['eps'], fr)
-                if todo is None:
-                    c['idx'], c['win'] = self._certified_peaks(fr)
-                    changed.add(k)
-                    continue
-                if todo.size:
-                    changed.add(k)          # (st[todo] holds the re-runs' own status now: settled, 0 or 1)
-            if ((st & 3) == 2).any():
-                # rare: crop budget exceeded -> those samples on the full-frame fp32 path (with the call's own status)
-                m.fix_uncertified(c['idx'], c['win'], frames_u8=fr, status=st)
-                changed.add(k)
-        return changed
+    def _enqueue(self, frames_u8, f0, f1):
+        """One call on frames_u8[f0:f1], enqueued on the current stream (the overlapped clip path) -> wasb.CertCall."""
+        if self.cert is not None:
+            return self.cert.enqueue(frames_u8, f0, f1)
+        return wasb.CertCall(f0, f1, *self.model.forward_frames(frames_u8[f0:f1])[1:])
 
 
-class BallDetector(_CertifiedDetector):
+class BallDetector(_HubDetector):
     def __new__(cls, model_name='segformerpp_b2', *a, **k):
         return super().__new__(ViTPoseBallDetector if cls is BallDetector and model_name == 'vitpose' else cls)
 
@@ -207,6 +137,7 @@ class BallDetector(_CertifiedDetector):
         sd, res, in_frames = _load_ball_checkpoint(model_name)
         self.model = wasb.get_model(model_name, in_frames=in_frames, resolution=res, pretraining=False, state_dict=sd,
                                     max_batch=max_batch, dtype=dtype, lanes=lanes)
+        self._init_cert()
         self.model_resolution = res
         self.max_batch = max_batch
 
@@ -243,7 +174,7 @@ class BallDetector(_CertifiedDetector):
         step = self.max_batch                      # triples per call; consecutive calls overlap by two frames
         for t0 in range(0, n - 2, step):
             fr = torch.from_numpy(np.stack([np.asarray(i) for i in images[t0:t0 + step + 2]])).to(self.device)
-            self._calibrate(frames=fr)
+            self._calibrate(fr)
             idx, win = self._certified_peaks(fr)
             out.append(refine.refine_windows_device(idx, win, h, w, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE).cpu().numpy())
         return np.concatenate(out, axis=0)
@@ -269,7 +200,7 @@ def _load_table_checkpoint(model_name):
     return weights.random_wasb_state_dict(int(os.environ.get('TTUP_SEED', '0')) + 1, planted=not noise, in_ch=3, head_out=13, plant_all_heads=not noise), (1280, 704)
 
 
-class TableDetector(_CertifiedDetector):
+class TableDetector(_HubDetector):
     NO_CERTIFY_ENV = ('TTUP_NO_CERTIFY', 'TTUP_NO_TABLE_CERTIFY')
 
     def __new__(cls, model_name='segformerpp_b2', *a, **k):
@@ -284,6 +215,7 @@ class TableDetector(_CertifiedDetector):
         self.KEYPOINT_VISIBLE = KEYPOINT_VISIBLE
         sd, res = _load_table_checkpoint(model_name)
         self.model = wasb.get_table_model(model_name, resolution=res, pretraining=False, state_dict=sd, max_batch=max_batch, dtype=dtype, lanes=lanes)
+        self._init_cert()
         self.model_resolution = res
         self.max_batch = max_batch
 
@@ -312,7 +244,7 @@ class TableDetector(_CertifiedDetector):
         out = []
         for b0 in range(0, len(images), self.max_batch):
             fr = torch.from_numpy(np.stack([np.asarray(i) for i in images[b0:b0 + self.max_batch]])).to(self.device)
-            self._calibrate(frames=fr)
+            self._calibrate(fr)
             idx, win = self._certified_peaks(fr)
             pos = refine.refine_windows_device(idx.reshape(-1), win.reshape(-1, 9), h, w, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
             out.append(pos.cpu().numpy().reshape(-1, 13, 3))
@@ -513,6 +445,9 @@ class TableTennisPipeline:
         self.table_detector.model.set_priority(True)
         self.uplifting_model = UpliftingModel()
         self.KEYPOINT_VISIBLE = KEYPOINT_VISIBLE
+        # the overlapped clip path's streams, pinned staging buffers (created on first use) and staging threads; _trace: a list to
+        # collect host time stamps of its stages in (tools/hub_trace.py)
+        self._streams = self._pinned = self._pin_free = self._stage_pool = self._trace = None
 
     def predict(self, images, fps):
         """images: list of BGR frames of one rally; fps: frame rate (interface.py:265-289).
@@ -539,7 +474,7 @@ class TableTennisPipeline:
         ba = self.ball_detector_aux if isinstance(self.ball_detector_aux, ViTPoseBallDetector) else None
         ta = self.table_detector_aux if want_table and isinstance(self.table_detector_aux, ViTPoseTableDetector) else None
         import time as _time
-        tr = self.__dict__.get('_trace')          # tools/hub_trace.py: host time stamps (ms since the call) of the clip path's stages
+        tr = self._trace          # tools/hub_trace.py: host time stamps (ms since the call) of the clip path's stages
         t00 = _time.perf_counter()
         mark = (lambda name: tr.append((name, (_time.perf_counter() - t00) * 1e3))) if tr is not None else (lambda name: None)
         C = self.CHUNK if n < 4 * self.CHUNK else self.CHUNK_LONG
@@ -549,13 +484,11 @@ class TableTennisPipeline:
         bw, bh = bd.model_resolution
         tw, th = td.model_resolution
         frames = torch.empty((n, h0, w0, 3), dtype=torch.uint8, device=dev)
-        st = self.__dict__.setdefault('_streams', None)
-        if st is None:
-            st = self._streams = {k: torch.cuda.Stream(dev) for k in ('ball', 'table')}
-            st['copy'] = st['table']          # uploads ride on the table stream (chunk k+1 behind the table pass of chunk k): one stream fewer
-            self._pinned = [torch.empty((CP, h0, w0, 3), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-            self._pin_free = [None, None]
-        if self._pinned[0].shape[1:] != (h0, w0, 3):
+        if self._streams is None:
+            self._streams = {k: torch.cuda.Stream(dev) for k in ('ball', 'table')}
+            self._streams['copy'] = self._streams['table']          # uploads ride on the table stream (chunk k+1 behind the table pass of chunk k): one stream fewer
+        st = self._streams
+        if self._pinned is None or self._pinned[0].shape[1:] != (h0, w0, 3):
             self._pinned = [torch.empty((CP, h0, w0, 3), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
             self._pin_free = [None, None]
         if (ba is not None or ta is not None) and 'aux' not in st:
@@ -585,31 +518,24 @@ class TableTennisPipeline:
             self._pin_free[ci % 2] = ev
             if ci == 0:
                 torch.cuda.current_stream(dev).wait_event(ev)
-                bd._calibrate(frames=frames[:c1]) if c1 >= 3 else None        # certified argmax: once per detector
+                if c1 >= 3:          # certified argmax: eps calibrated once per detector
+                    bd._calibrate(frames[:c1])
                 if want_table:
-                    td._calibrate(frames=frames[:c1])
+                    td._calibrate(frames[:c1])
             if want_table:
                 with torch.cuda.stream(st['table']):
                     st['table'].wait_event(ev)
-                    tm = td.model
-                    _, idx, win = tm.forward_frames(frames[c0:c1], want_heatmap=False)
-                    # status / info of THIS call, copied right behind it (per-call slot); the keypoints are refined at once from what
-                    # the call returned -- settled below, after the stream has drained, and refined again only where a repair changed them
-                    table_calls.append({'f0': c0, 'f1': c1, 'idx': idx, 'win': win, 'eps': tm.eps if tm.certified else None,
-                                        'status': tm.certify_status(idx.shape[0], raw=True) if tm.certified else None,
-                                        'info': tm.certify_info() if tm.certified else None})
-                    table_out.append(refine.refine_windows_device(idx.reshape(-1), win.reshape(-1, 9), th, tw, td.resolution[0], td.resolution[1], _lib.REFINE_TABLE))
+                    # the keypoints are refined at once from what the call returned -- settled below, after the stream has drained, and
+                    # refined again only where a re-certification or repair changed them
+                    table_calls.append(td._enqueue(frames, c0, c1))
+                    table_out.append(refine.refine_windows_device(table_calls[-1].idx.reshape(-1), table_calls[-1].win.reshape(-1, 9), th, tw,
+                                                                  td.resolution[0], td.resolution[1], _lib.REFINE_TABLE))
             # triples t need frames t..t+2: everything up to c1-3 can go now
             while t_next < c1 - 2:
                 nt = min(bd.max_batch, c1 - 2 - t_next)
                 with torch.cuda.stream(st['ball']):
                     st['ball'].wait_event(ev)
-                    fr = frames[t_next:t_next + nt + 2]
-                    _, idx, win = bd.model.forward_frames(fr, want_heatmap=False)
-                    # status / info of THIS call, copied right behind it (the handle's per-call slot flips with the next call)
-                    status = bd.model.certify_status(nt, raw=True) if bd.model.certified else None
-                    info = bd.model.certify_info() if bd.model.certified else None
-                    ball_calls.append((t_next, nt, idx, win, status, info, bd.model.eps if bd.model.certified else None))
+                    ball_calls.append(bd._enqueue(frames, t_next, t_next + nt + 2))
                 t_next += nt
             if ba is not None or ta is not None:
                 with torch.cuda.stream(st['aux']):
@@ -624,34 +550,33 @@ class TableTennisPipeline:
                     if ba is not None and a_next < c1 - 2:
                         ball_aux_out.append(ba._refine(*ba.model.forward_frames(frames[a_next:c1])[1:]))
                         a_next = c1 - 2
-        uploaded = [ev]
         mark('all calls enqueued')
         frames.record_stream(st['ball']); frames.record_stream(st['table'])
         if ba is not None or ta is not None:
             frames.record_stream(st['aux'])
         # eps audit of the certified argmax: a random triple of the clip on the fp32 twin, on its own stream next to the detectors
         audit = None
-        picks = bd._audit_picks(n - 2)
+        picks = bd.cert.picks(n - 2) if bd.cert is not None else []
         if picks:
-            cur.wait_event(uploaded[-1])
-            audit = bd.model.audit_async(frames, picks)
+            cur.wait_event(ev)
+            audit = bd.cert.audit(picks, frames)
         kp = None
         if want_table:
             # the table detector (high-priority streams) finishes first: its keypoints come back and the host-side DBSCAN filter
             # runs while the ball detector is still busy on the GPU
             t_audit = None
-            t_picks = td._audit_picks(n)
+            t_picks = td.cert.picks(n) if td.cert is not None else []
             if t_picks:
-                cur.wait_event(uploaded[-1])
-                t_audit = td.model.audit_async(frames, t_picks)
-            cert = td.model.certified and bool(table_calls)
+                cur.wait_event(ev)
+                t_audit = td.cert.audit(t_picks, frames)
+            cert = td.cert is not None and bool(table_calls)
             with torch.cuda.stream(st['table']):
                 kp_dev = torch.cat(table_out).reshape(-1, 13, 3)
                 kp_host = torch.empty(kp_dev.shape, dtype=kp_dev.dtype, pin_memory=True)
                 kp_host.copy_(kp_dev, non_blocking=True)
                 if cert:          # the calls' status flags and crop / error info in one copy each
-                    st_dev = torch.cat([c['status'] for c in table_calls])
-                    in_dev = torch.stack([c['info'] for c in table_calls])
+                    st_dev = torch.cat([c.status for c in table_calls])
+                    in_dev = torch.stack([c.info for c in table_calls])
                     st_host = torch.empty(st_dev.shape, dtype=st_dev.dtype, pin_memory=True); st_host.copy_(st_dev, non_blocking=True)
                     in_host = torch.empty(in_dev.shape, dtype=in_dev.dtype, pin_memory=True); in_host.copy_(in_dev, non_blocking=True)
                 ev_t = torch.cuda.Event(); ev_t.record()
@@ -661,14 +586,15 @@ class TableTennisPipeline:
             if cert:
                 o = 0
                 for k, c in enumerate(table_calls):
-                    nmap = c['idx'].shape[0]
-                    c['status'], c['info'] = st_host.numpy()[o:o + nmap], in_host.numpy()[k]
+                    nmap = c.idx.shape[0]
+                    c.status, c.info = st_host.numpy()[o:o + nmap], in_host.numpy()[k]
                     o += nmap
                 cur.wait_stream(st['table'])
-                for k in sorted(td._settle_calls(table_calls, frames, t_audit)):          # rare: re-certified / repaired calls are refined again
+                # rare: re-certified / repaired calls are refined again (a call run again whole is a new, counted call: `EpsAudit.run`)
+                for k in sorted(td.cert.settle(table_calls, frames, audit=t_audit, rerun=lambda c: td.cert.run(frames[c.f0:c.f1]))):
                     c = table_calls[k]
-                    pos = refine.refine_windows_device(c['idx'].reshape(-1), c['win'].reshape(-1, 9), th, tw, td.resolution[0], td.resolution[1], _lib.REFINE_TABLE)
-                    kp_np[c['f0']:c['f1']] = pos.cpu().numpy().reshape(-1, 13, 3)
+                    pos = refine.refine_windows_device(c.idx.reshape(-1), c.win.reshape(-1, 9), th, tw, td.resolution[0], td.resolution[1], _lib.REFINE_TABLE)
+                    kp_np[c.f0:c.f1] = pos.cpu().numpy().reshape(-1, 13, 3)
             mark('table calls settled')
             if ta is not None:
                 ev_ta.synchronize()
@@ -681,11 +607,10 @@ class TableTennisPipeline:
             mark('keypoint filter done')
         for s in st.values():
             cur.wait_stream(s)
-        calls = [{'f0': t0, 'f1': t0 + nt + 2, 'idx': idx, 'win': win, 'status': status, 'info': info, 'eps': eps_used}
-                 for (t0, nt, idx, win, status, info, eps_used) in ball_calls]
-        bd._settle_calls(calls, frames, audit)
-        for c in calls:
-            ball_out.append(refine.refine_windows_device(c['idx'], c['win'], bh, bw, bd.resolution[0], bd.resolution[1], _lib.REFINE_TABLE))
+        if bd.cert is not None:
+            bd.cert.settle(ball_calls, frames, audit=audit, rerun=lambda c: bd.cert.run(frames[c.f0:c.f1]))
+        for c in ball_calls:
+            ball_out.append(refine.refine_windows_device(c.idx, c.win, bh, bw, bd.resolution[0], bd.resolution[1], _lib.REFINE_TABLE))
         pos = torch.cat(ball_out).cpu().numpy() if ball_out else np.zeros((0, 3))
         mark('ball calls settled, positions on the host')
         if not return_aux:
@@ -705,11 +630,10 @@ class TableTennisPipeline:
             for k in range(c0, c1):
                 np.copyto(dst[k - c0], images[k])
             return
-        pool = self.__dict__.get('_stage_pool')
-        if pool is None:
+        if self._stage_pool is None:
             import concurrent.futures
-            pool = self._stage_pool = concurrent.futures.ThreadPoolExecutor(max_workers=self.STAGE_THREADS)
-        list(pool.map(lambda k: np.copyto(dst[k - c0], images[k]), range(c0, c1)))
+            self._stage_pool = concurrent.futures.ThreadPoolExecutor(max_workers=self.STAGE_THREADS)
+        list(self._stage_pool.map(lambda k: np.copyto(dst[k - c0], images[k]), range(c0, c1)))
 
     def _predict(self, images, fps, table_keypoints):
         # the overlapped clip path feeds an aux detector only when it is ViTPose (or the primary itself)

@@ -9,6 +9,8 @@ float32 -- a few KB per stream, latency-bound on any xGMI topology (``gather_rec
 import numpy as np
 import torch
 
+from . import wasb
+
 TRAJ_LEN_DEFAULT = 32
 
 
@@ -100,18 +102,14 @@ class StreamWorker:
     """Per-GPU worker: owns one CNN handle, one uplift handle, and runs whole clips through the path.
     Raises RuntimeError without a HIP device (no CPU fallback).
 
-    Certified argmax (`certify=True`, bf16): eps -- the bound on |bf16 heatmap - fp32 heatmap| the certification rests on -- is
-    estimated on the first clip and then AUDITED while the worker runs: one random triple per `audit_every` triples (per
-    `audit_every_fast` until eps has stood for `audit_settle_clips` clips in a row) is re-run on
-    the fp32 twin on a side stream, and every fp32 crop the certification computes anyway reports the error at its candidates.
-    eps is 1.5 times the largest error seen so far (calibration frames, audits); a new maximum widens it, and of the clips certified
-    under the old value only the heatmaps whose guard band (pixels between 2 eps and 2.5 eps below the maximum) is not empty are
-    run again -- the whole clip only when eps grows by more than a quarter at once.  `audit` reports the counts; `audit_every=0` switches the side-stream audit off."""
+    Certified argmax (`certify=True`, bf16): eps is calibrated on the first clip and audited while the worker runs by `cert`
+    (wasb.EpsAudit, where the protocol is described); `audit` reports the counts, `audit_every=0` switches the strip audit off.  The
+    worker adds its own policy: audit crops, the crop budget, the margin log, its streams and pinned buffers."""
 
     def __init__(self, device, wasb_state_dict, uplift_state_dict, net_wh=(1280, 704), max_triples=256, uplift_size='large',
                  traj_len=TRAJ_LEN_DEFAULT, seq_len=50, dtype='bf16', certify=True, audit_every=256, audit_seed=0, exact_windows=False,
                  audit_every_fast=64, audit_settle_clips=8, audit_crops_every=16):
-        from . import glue, refine, uplift, wasb, _lib
+        from . import glue, refine, uplift, _lib
         _lib.require_gpu()
         self._glue, self._refine, self._uplift, self._lib = glue, refine, uplift, _lib
         self.device = torch.device(device)
@@ -125,32 +123,44 @@ class StreamWorker:
         # certified argmax (the fp32 path's indices from the bf16 path, csrc/certify.hip): calibrated on the first clip seen
         self.certify = bool(certify) and dtype == 'bf16'
         self.exact_windows = bool(exact_windows)
-        self.certify_eps = None
-        self.fp32_reruns = 0
-        self.recertified_clips = 0
-        self.recertified_heatmaps = 0
-        # Side-stream audit rate (triples per audited triple), ADAPTIVE: `audit_every_fast` while the bound is still moving -- until
-        # `audit_settle_clips` consecutive clips have passed without a widening of eps -- and `audit_every` afterwards; a widening
-        # drops back to the fast rate.  New content is where a too-small eps is found (the soaks widen within the first clips of a
-        # content change and not again), so the audits are spent there.  `audit['audited_share']` = audited / processed triples.
+        # Strip audit rate, ADAPTIVE: `audit_every_fast` until `audit_settle_clips` clips in a row passed without a widening, then
+        # `audit_every`.  New content is where a too-small eps is found (the soaks widen within the first clips of a content change).
         self.audit_every = int(audit_every)
         self.audit_every_fast = min(int(audit_every_fast), self.audit_every) if int(audit_every_fast) > 0 else self.audit_every
         self.audit_settle_clips = int(audit_settle_clips)
-        self._quiet_clips = 0
-        self.frames_seen = 0
+        self.cert = wasb.EpsAudit(self.net, every=self.audit_every if self.certify else 0, every_fast=self.audit_every_fast,
+                                  settle_clips=self.audit_settle_clips, seed=audit_seed)
         # Audit crops (round 6): one single-candidate heatmap per `audit_crops_every` triples gets an fp32 crop although its index is
         # already certain; the crop reports |bf16 - fp32| at the winner.  The strip audit sees every pixel of a quarter-width strip of
         # one triple per 64-256; this sees ONE pixel -- the one the detection rests on -- of one triple per 16, at 0.1 ms each
-        # (1.3 % of a step).  The phase is drawn per clip.  0 = off.
+        # (1.3 % of a step).  The phase is drawn per pass.  0 = off.
         self.audit_crops_every = int(audit_crops_every)
         self.audit_crop_frames = 0
-        self.widen_sources = {'strip': 0, 'candidates': 0}
-        self._since_audit = 0
-        self._rng = np.random.default_rng(audit_seed)
-        self._rng_crops = np.random.default_rng(audit_seed + 1)          # (its own stream: tests replace _rng to steer the strip audit)
+        self._rng_crops = np.random.default_rng(audit_seed + 1)
+        self._crop_hist = []          # crops asked for by the last passes (`_size_crop_budget`)
         # measurement (bench.py `ambiguous_share`): when set to a list, every collected clip appends the fp32 top-2 margins of its
         # heatmaps (`WASBNet.certify_margins`: +inf for single-candidate heatmaps)
         self.margin_log = None
+        self._sub = None              # submit's two alternating streams (`submit_streams`)
+        self._side = None             # collect's uplift stream
+        self._pin_pool = {}           # pinned host buffers of the clips in flight (`_pinned`)
+
+    @property
+    def certify_eps(self):
+        """eps of the certified argmax (the handle's): None until calibrated, or with certify off."""
+        return self.cert.eps
+
+    @certify_eps.setter
+    def certify_eps(self, eps):          # (a widening by hand, e.g. `worker.certify_eps = worker.net.widen_eps(err)`)
+        if eps != self.cert.eps:
+            self.net.set_certify(eps)
+
+    # the strip audit's pick rng and its quiet-clip count live in `cert` (tests steer them through the worker)
+    _rng = property(lambda self: self.cert.rng, lambda self, rng: setattr(self.cert, 'rng', rng))
+    _quiet_clips = property(lambda self: self.cert.quiet, lambda self, n: setattr(self.cert, 'quiet', n))
+    fp32_reruns = property(lambda self: self.cert.fp32_reruns)
+    recertified_clips = property(lambda self: self.cert.recertified_calls)
+    recertified_heatmaps = property(lambda self: self.cert.recertified_heatmaps)
 
     def record_spec(self):
         """Capacities of the per-clip records (`gather_records(..., spec=...)`: one collective per step)."""
@@ -160,7 +170,7 @@ class StreamWorker:
     @property
     def audit(self):
         """{'audited_frames', 'max_err_seen', 'widened', 'eps', 'max_err_over_eps', 'recertified_clips'} of the certified argmax."""
-        a = dict(getattr(self.net, 'audit_state', None) or dict(audited_frames=0, max_err_seen=0.0, widened=0))
+        a = dict(self.net.audit_state)
         a['eps'] = self.certify_eps
         a['max_err_over_eps'] = (a['max_err_seen'] / self.certify_eps) if self.certify_eps else None
         a['recertified_clips'] = self.recertified_clips
@@ -168,106 +178,69 @@ class StreamWorker:
         # what the side-stream audit has covered: audited triples (calibration frames included) / triples processed.  A frame whose
         # error exceeds eps while no audited frame's does is missed with probability 1 - (the audit rate at that time) by the strip
         # audit (the candidate-level audit still sees it when it needs a crop): the guarantee is statistical and this is its rate
-        a['frames_seen'] = self.frames_seen
+        a['frames_seen'] = self.cert.seen
         # strip audits (every pixel of a strip of the triple, calibration frames included) + audit crops (the winner's pixel of the triple)
         a['audit_crop_frames'] = self.audit_crop_frames
-        a['strip_audited_share'] = (a['audited_frames'] / self.frames_seen) if self.frames_seen else None
-        a['audited_share'] = ((a['audited_frames'] + self.audit_crop_frames) / self.frames_seen) if self.frames_seen else None
+        a['strip_audited_share'] = (a['audited_frames'] / a['frames_seen']) if a['frames_seen'] else None
+        a['audited_share'] = ((a['audited_frames'] + self.audit_crop_frames) / a['frames_seen']) if a['frames_seen'] else None
         a['audit_every_now'] = self.audit_rate()
-        a['quiet_clips'] = self._quiet_clips
-        a['widen_sources'] = dict(self.widen_sources)
+        a['quiet_clips'] = self.cert.quiet
+        a['widen_sources'] = dict(self.cert.widen_sources)
         return a
 
     def audit_rate(self):
         """Triples per audited triple right now (0 = side-stream audit off)."""
-        if not self.certify or self.audit_every <= 0:
-            return 0
-        return self.audit_every_fast if self._quiet_clips < self.audit_settle_clips else self.audit_every
+        return self.cert.rate()
 
     def detect(self, frames_u8):
         """(N,h,w,3) uint8 on the device -> (N-2,3) float64 [x, y, visibility] in 1920x1080 px (table-variant refine,
         like interface.py:116)."""
-        return self._detect(frames_u8)[0]
+        return self._detect_blocking(frames_u8)
 
-    def _calibrated(self, frames_u8):
-        if self.certify and self.certify_eps is None:
-            self.certify_eps = self.net.calibrate(frames_u8, n=8, exact_windows=self.exact_windows)
-        return self.certify_eps
+    def _xyv(self, idx, win):
+        return self._refine.refine_windows_device(idx, win, self.net_h, self.net_w, 1920, 1080, self._lib.REFINE_TABLE)
 
-    def _start_audit(self, frames_u8, rerun=False):
-        """Enqueue the side-stream audit of this clip (if one is due) next to its detector pass; None otherwise.  rerun=True: the clip
-        has been counted (and its audit drawn) already -- a re-run after eps widened past the guard factor is the same triples again."""
-        if rerun:
-            return None
-        picks = self._pick_audits(frames_u8.shape[0] - 2)
-        return self.net.audit_async(frames_u8, picks) if picks else None
-
-    def _detect(self, frames_u8):
-        self._calibrated(frames_u8)
+    def _pass(self, frames_u8, counted=False):
+        """Enqueue one detector pass over a clip -> (xyv, wasb.CertCall, audit ticket or None): the clip's strip audit on a side stream
+        and its audit crops, then the forward with its status / info behind it (`EpsAudit.enqueue`).  counted=True: a whole-clip re-run
+        after eps grew past the guard factor -- the same triples again, so they are not counted and no strip audit is drawn a second
+        time (a new crop phase is)."""
+        n = frames_u8.shape[0] - 2
+        if self.certify and not self.net.certified:
+            self.net.calibrate(frames_u8, n=8, exact_windows=self.exact_windows)
+        audit = None if counted else self.cert.audit(self.cert.picks(n), frames_u8)
         if self.certify and self.audit_crops_every > 0:
             every = self.audit_crops_every
             phase = int(self._rng_crops.integers(every))
             self.net.certify_audit_crops(every, phase)
-            n = int(frames_u8.shape[0]) - 2
-            if not self.__dict__.get('_rerun_pass', False):
+            if not counted:
                 self.audit_crop_frames += len(range((-phase) % every, n, every))          # frames f < n with (f + phase) % every == 0
-        _, idx, win = self.net.forward_frames(frames_u8, want_heatmap=False)
-        xyv = self._refine.refine_windows_device(idx, win, self.net_h, self.net_w, 1920, 1080, self._lib.REFINE_TABLE)
-        # status and info belong to THIS call: both are copied right behind it in stream order, before another call can flip the
-        # handle's per-call slot
-        status = self.net.certify_status(idx.shape[0], raw=True) if self.certify else None          # bit 2 = guard band not empty
-        info = self.net.certify_info() if self.certify else None
-        self._last_margin = self.net.certify_margins(idx.shape[0]) if self.certify and self.margin_log is not None else None
-        return xyv, idx, win, status, info
+        if self.certify:
+            self._size_crop_budget()
+        call = self.cert.enqueue(frames_u8)
+        return self._xyv(call.idx, call.win), call, audit
 
-    def _pick_audits(self, n_triples):
-        """Indices of the triples of a clip that the side-stream audit re-runs on the fp32 twin: one per `audit_every` triples."""
-        self.frames_seen += max(0, int(n_triples))
-        every = self.audit_rate()
-        if every <= 0 or n_triples <= 0:
-            return []
-        self._since_audit += n_triples
-        picks = []
-        while self._since_audit >= every:
-            self._since_audit -= every
-            picks.append(int(self._rng.integers(n_triples)))
-        return picks
+    def _size_crop_budget(self):
+        """Crop budget of the next pass (it sizes the number of fp32 passes a call provisions; an unused pass still costs its launches):
+        one and a half times the most any of the last eight passes asked for (+ slack) -- content that alternates between easy and hard
+        clips keeps the hard clips' budget (twice the LAST clip's count sent 40 % of a hard clip that followed an easy one to the
+        full-frame fp32 path); clips that outgrow it are flagged and repaired.  Before the first pass has settled: the handle's default."""
+        if self._crop_hist:
+            self.net.certify_budget(3 * max(self._crop_hist) // 2 + 16)
 
-    def _repair(self, frames_u8, xyv, idx, win, status_host):
-        """Rare slow path: heatmaps the certified argmax could not settle inside its crop budget are re-run on the full-frame
-        fp32 handle, so that every detection comes from the fp32 argmax.  `status_host` is the status of the call that produced
-        idx / win (not of whatever the handle ran last)."""
-        bad = np.nonzero((status_host & 3) == 2)[0]
-        if bad.size == 0:
-            return xyv
-        self.fp32_reruns += self.net.fix_uncertified(idx, win, frames_u8=frames_u8, status=status_host)
-        sel = torch.as_tensor(bad, device=self.device)
-        xyv[sel] = self._refine.refine_windows_device(idx[sel], win[sel], self.net_h, self.net_w, 1920, 1080, self._lib.REFINE_TABLE)
-        return xyv
+    def _settle(self, call, frames_u8, audit):
+        """`EpsAudit.settle` of one pass -> True when its indices / windows changed.  A whole-clip re-run is a counted `_detect_blocking`."""
+        self._crop_hist = (self._crop_hist + [self.net.decode_info(call.info)[0]])[-8:]
+        rerun = lambda c: wasb.CertCall(c.f0, c.f1, *self._detect_blocking(frames_u8, full=True, counted=True)[1:])          # noqa: E731
+        return bool(self.cert.settle([call], frames_u8, audit=audit, rerun=rerun))
 
-    def _after_clip(self, n_crops, cand_err, audit_ticket):
-        """Fold a finished clip's evidence into the eps audit and size the crop budget of the clips to come.  Returns True when eps
-        had to be widened (clips certified under a smaller eps must be re-run)."""
-        net = self.net
-        err = net.note_error(cand_err)
-        strip_err = net.audit_result(audit_ticket) if audit_ticket is not None else 0.0
-        source = 'strip' if strip_err > err else 'candidates'
-        err = max(err, strip_err)
-        widened = False
-        if net.eps_violated(err):
-            self.certify_eps = net.widen_eps(err)
-            widened = True
-            self.__dict__.setdefault('widen_sources', {'strip': 0, 'candidates': 0})[source] += 1
-        self._quiet_clips = 0 if widened else self.__dict__.get('_quiet_clips', 0) + 1
-        # crop budget of the next clips (it sizes the number of fp32 passes a call provisions; an unused pass still costs its launches):
-        # one and a half times the most any of the last eight clips asked for (+ slack) -- content that alternates between easy and
-        # hard clips keeps the hard clips' budget (twice the LAST clip's count sent 40 % of a hard clip that followed an easy one to
-        # the full-frame fp32 path); clips that outgrow it are flagged and repaired
-        hist = self.__dict__.setdefault('_crop_hist', [])
-        hist.append(int(n_crops))
-        del hist[:-8]
-        net.certify_budget(3 * max(hist) // 2 + 16)
-        return widened
+    def _detect_blocking(self, frames_u8, full=False, counted=False):
+        """One clip start to finish, blocking: (xyv device tensor) whose every index is certified under the current eps; full=True:
+        (xyv, idx, win, host status 0/1/2) of the pass that produced it.  counted=True: see `_pass`."""
+        xyv, call, audit = self._pass(frames_u8, counted)
+        if call.status is not None and self._settle(call, frames_u8, audit):
+            xyv = self._xyv(call.idx, call.win)
+        return (xyv, call.idx, call.win, None if call.status is None else call.status & 3) if full else xyv
 
     def uplift_segments(self, positions, table_px, fps):
         """Cut the detections into rallies of `traj_len` frames, filter / normalise / pad each like the reference
@@ -283,46 +256,6 @@ class StreamWorker:
         rot, p3 = self.up(torch.cat(balls), torch.cat(tables), mask, torch.cat(times))
         spin = self._uplift.transform_rotationaxes(rot, p3)
         return spin, p3, mask.sum(1).to(torch.int64).to(self.device)
-
-    def _recertify(self, frames_u8, xyv, idx, win, status_host, eps_used):
-        """The clip was certified under `eps_used` and eps has grown since.  Heatmaps with an empty guard band keep their result; the
-        others are run again under the current eps (`WASBNet.recertify_subset`).  Returns the updated xyv, or None when eps grew
-        past the guard factor and the whole clip has to be run again."""
-        todo = self.net.recertify_subset(idx, win, status_host, eps_used, frames_u8)
-        if todo is None:
-            return None
-        self.recertified_heatmaps += int(todo.size)
-        if todo.size:
-            sel = torch.as_tensor(todo, device=self.device)
-            xyv[sel] = self._refine.refine_windows_device(idx[sel], win[sel], self.net_h, self.net_w, 1920, 1080, self._lib.REFINE_TABLE)
-            # (status_host[todo] now holds the re-runs' own status: 0 = single candidate under the current eps, 1 = fp32 values)
-        return xyv
-
-    def _detect_blocking(self, frames_u8, full=False, counted=False):
-        """One clip, start to finish, with the audit folded in: (xyv device tensor) whose every index is certified under the
-        current eps; full=True: (xyv, idx, win, host status 0/1/2) of the pass that produced it.  Loops only when an audit widens
-        eps past the guard factor (eps only grows)."""
-        rerun = bool(counted)          # counted=True: the clip went through submit() already (frames_seen, audits)
-        while True:
-            eps_used = self._calibrated(frames_u8)
-            ticket = self._start_audit(frames_u8, rerun)
-            self._rerun_pass = rerun
-            rerun = True
-            xyv, idx, win, status, info = self._detect(frames_u8)
-            if status is None:
-                self._rerun_pass = False
-                return (xyv, idx, win, None) if full else xyv
-            n_crops, cand_err = self.net.decode_info(info.cpu().numpy())
-            st = status.cpu().numpy()
-            if self._after_clip(n_crops, cand_err, ticket) or eps_used < self.certify_eps:
-                out = self._recertify(frames_u8, xyv, idx, win, st, eps_used)
-                if out is None:
-                    self.recertified_clips += 1
-                    continue
-                xyv = out
-            xyv = self._repair(frames_u8, xyv, idx, win, st)
-            self._rerun_pass = False
-            return (xyv, idx, win, st & 3) if full else xyv
 
     def process_clip(self, frames_u8, table_px, fps):
         xyv = self._detect_blocking(frames_u8)
@@ -346,16 +279,14 @@ class StreamWorker:
     def submit_streams(self):
         """The two alternating streams `submit` issues clips on (created on first use; callers that are about to create other
         streams -- a process group -- call this first so that the worker's stream-to-queue mapping does not depend on them)."""
-        subs = self.__dict__.setdefault('_sub', None)
-        if subs is None:
-            subs = self._sub = {'streams': [torch.cuda.Stream(self.device), torch.cuda.Stream(self.device)], 'next': 0}
-        return subs
+        if self._sub is None:
+            self._sub = {'streams': [torch.cuda.Stream(self.device), torch.cuda.Stream(self.device)], 'next': 0}
+        return self._sub
 
     def _pinned(self, key, like):
         """A pinned host buffer shaped like `like` from the worker's pool (returned to it by collect): any number of clips may be
         in flight between submit and collect."""
-        pool = self.__dict__.setdefault('_pin_pool', {})
-        free = pool.setdefault((key, tuple(like.shape), like.dtype), [])
+        free = self._pin_pool.setdefault((key, tuple(like.shape), like.dtype), [])
         return free.pop() if free else torch.empty(like.shape, dtype=like.dtype, pin_memory=True)
 
     def _unpin(self, key, buf):
@@ -363,73 +294,62 @@ class StreamWorker:
             self._pin_pool[(key, tuple(buf.shape), buf.dtype)].append(buf)
 
     def _submit(self, frames_u8, sub):
-        eps_used = self._calibrated(frames_u8)
-        audit = self._start_audit(frames_u8)          # side stream: shares the GPU with this clip's detector pass
-        xyv, idx, win, status, info = self._detect(frames_u8)
+        xyv, call, audit = self._pass(frames_u8)          # (the strip audit shares the GPU with this clip's detector pass)
+        margin = self.net.certify_margins(call.idx.shape[0]) if call.status is not None and self.margin_log is not None else None
+        dev = [xyv, call.idx, call.win, frames_u8]
         host = self._pinned('xyv', xyv)
         host.copy_(xyv, non_blocking=True)
-        st_host = info_host = None
-        if status is not None:
-            st_host = self._pinned('status', status)
-            st_host.copy_(status, non_blocking=True)
-            info_host = self._pinned('info', info)
-            info_host.copy_(info, non_blocking=True)
-        mg_host = None
-        if self._last_margin is not None:
-            mg_host = self._pinned('margin', self._last_margin)
-            mg_host.copy_(self._last_margin, non_blocking=True)
-            self._last_margin.record_stream(sub)
+        st_host = info_host = mg_host = None
+        if call.status is not None:
+            dev += [call.status, call.info]
+            st_host = self._pinned('status', call.status)
+            st_host.copy_(call.status, non_blocking=True)
+            info_host = self._pinned('info', call.info)
+            info_host.copy_(call.info, non_blocking=True)
+            call.status, call.info = st_host, info_host
+        if margin is not None:
+            mg_host = self._pinned('margin', margin)
+            mg_host.copy_(margin, non_blocking=True)
+            margin.record_stream(sub)
         done = torch.cuda.Event()
         done.record()
-        for t in (xyv, idx, win, frames_u8) + ((status, info) if status is not None else ()):
+        for t in dev:
             t.record_stream(sub)
-        return {'margin': mg_host, 'xyv': xyv, 'host': host, 'done': done, 'frames': frames_u8, 'idx': idx, 'win': win, 'status': st_host, 'info': info_host,
-                'stream': sub, 'audit': audit, 'eps': eps_used}
+        return {'call': call, 'margin': mg_host, 'xyv': xyv, 'host': host, 'done': done, 'frames': frames_u8, 'idx': call.idx, 'win': call.win,
+                'status': st_host, 'info': info_host, 'stream': sub, 'audit': audit}
 
     def collect(self, ticket, table_px, fps):
         ticket['done'].synchronize()
         torch.cuda.current_stream(self.device).wait_stream(ticket['stream'])
-        rerun_status = None
-        if ticket.get('status') is not None:
-            n_crops, cand_err = self.net.decode_info(ticket['info'].numpy())
-            widened = self._after_clip(n_crops, cand_err, ticket.get('audit'))
-            st = ticket['status'].numpy()
-            if widened or ticket['eps'] < self.certify_eps:
-                # this clip was certified under an eps that an audit has since found too small: the heatmaps whose guard band is
-                # not empty are run again (a few per clip); the whole clip only when eps grew past the guard factor (blocking; rare)
-                out = self._recertify(ticket['frames'], ticket['xyv'], ticket['idx'], ticket['win'], st, ticket['eps'])
-                if out is None:
-                    self.recertified_clips += 1
-                    # the ticket then describes the pass that produced its detections (indices, windows, status), not the stale one
-                    out, ticket['idx'], ticket['win'], rerun_status = self._detect_blocking(ticket['frames'], full=True, counted=True)
-                    st = None
-                ticket['xyv'] = out
+        call = ticket['call']
+        status_host = None
+        if call.status is not None:
+            # a clip certified under an eps that an audit has since found too small is re-certified here (wasb.EpsAudit.settle); the
+            # ticket then describes the pass that produced its detections (indices, windows, status), not the stale one
+            if self._settle(call, ticket['frames'], ticket['audit']):
+                ticket['xyv'] = self._xyv(call.idx, call.win)
                 ticket['host'].copy_(ticket['xyv'])
-            if st is not None and ((st & 3) == 2).any():
-                ticket['xyv'] = self._repair(ticket['frames'], ticket['xyv'], ticket['idx'], ticket['win'], st)
-                ticket['host'].copy_(ticket['xyv'])
+            ticket['idx'], ticket['win'] = call.idx, call.win
+            status_host = call.status & 3          # 0 / 1 / 2 (guard bit dropped)
         # the uplift (about a hundred small launches for a handful of trajectories) runs on a side stream, so it shares
         # the GPU with the detector of the clip submitted in the meantime instead of queueing behind it
-        side = self.__dict__.get('_side')
-        if side is None:
-            side = self._side = torch.cuda.Stream(self.device)
-        with torch.cuda.stream(side):
+        if self._side is None:
+            self._side = torch.cuda.Stream(self.device)
+        with torch.cuda.stream(self._side):
             spin, p3, nvalid = self.uplift_segments(ticket['host'].numpy(), table_px, fps)
-        side.synchronize()
+        self._side.synchronize()
         # the results were allocated under the side stream and are consumed on the caller's stream (gather_records, RCCL,
         # user code): tell the caching allocator, so their blocks are not handed to the next clip's side-stream uplift
         # while reads queued on the caller's stream are still pending
         cur = torch.cuda.current_stream(self.device)
         for t in (spin, p3, nvalid):
             t.record_stream(cur)
-        status_host = None if ticket.get('status') is None else (ticket['status'].numpy() & 3)          # 0 / 1 / 2 (guard bit dropped)
-        if status_host is not None and rerun_status is not None:
-            status_host = rerun_status
         if ticket.get('margin') is not None and self.margin_log is not None:
             self.margin_log.append(ticket['margin'].numpy().copy())
         for k in ('host', 'status', 'info', 'margin'):
             self._unpin('xyv' if k == 'host' else k, ticket.get(k))
             ticket[k] = None
+        ticket['call'] = None          # (its status viewed a pinned buffer that is back in the pool)
         ticket['status_host'] = status_host
         return {'xyv': ticket['xyv'], 'spin': spin, 'pos3d': p3, 'n_valid': nvalid, 'status': status_host}
 
@@ -446,9 +366,9 @@ class StreamWorker:
         ints = self.net.internal_streams()
         n_lanes = len(ints) - (1 if self.net.certified else 0)
         named += [('lane%d' % k, s) for k, s in enumerate(ints[:n_lanes])] + [('crops', s) for s in ints[n_lanes:]]
-        if getattr(self.net, '_audit_stream', None) is not None:
-            named.append(('audit', self.net._audit_stream))
-        if self.__dict__.get('_side') is not None:
+        if self.cert.audit_stream is not None:
+            named.append(('audit', self.cert.audit_stream))
+        if self._side is not None:
             named.append(('uplift', self._side))
         named.append(('default', torch.cuda.default_stream(dev)))
 

@@ -6,6 +6,7 @@ loader inference/inference_balldetection.py:40-61.  The forward runs in libttup.
 csrc/conv.hip); this class only owns the handle and the torch-side buffers.
 """
 import ctypes
+import dataclasses
 
 import numpy as np
 import torch
@@ -28,11 +29,12 @@ class WASBNet:
         self.max_batch = int(max_batch)
         self.dtype = dtype
         self._lib = _lib.load()
-        self._state_dict = state_dict            # kept for the fp32 twin of the certified argmax (calibrate / fix_uncertified)
-        self._f32_twin = None
-        self._bf16_twin = None
+        self._state_dict = state_dict            # kept for the other handles of the certified argmax (twins, strips, re-runs)
+        self._f32_twin = self._bf16_twin = self._strip_twins = self._recert = None
         self.certified = False
+        self.eps = None
         self.exact_windows = False
+        self.audit_state = dict(audited_frames=0, max_err_seen=0.0, widened=0)          # (calibration + audits: `note_error`)
         blob = weights.pack_wasb_blob(state_dict, in_ch=self.IN_CH, head_out=self.HEAD_OUT)
         self._handle = ctypes.c_void_p()
         with torch.cuda.device(self.device):
@@ -103,8 +105,7 @@ class WASBNet:
 
     # ---- certified argmax (csrc/certify.hip): the fp32 path's argmax indices from the bf16 path, GIVEN an error bound eps
     # The guarantee is conditional: an index is the fp32 argmax whenever |bf16 heatmap - fp32 heatmap| <= eps on that frame.  eps is
-    # an empirical bound -- measured (`calibrate`), then audited for as long as the handle runs (`audit_async` / the candidate-level
-    # error the crops give for free, `certify_info`) and widened when an audit comes within the safety factor of it.
+    # an empirical bound, measured and then audited for as long as the handle runs: `EpsAudit` (below) drives these primitives.
     SAFETY = 1.5           # an observed error within this factor of eps triggers a widening (and a re-run of the affected work)
     HEADROOM = 1.5         # eps is set to this factor times the largest error seen (= SAFETY: every new maximum widens eps -- which is cheap:
                            # only the heatmaps whose guard band is not empty are run again, `recertify_subset`)
@@ -119,13 +120,13 @@ class WASBNet:
         if exact_windows is not None:
             self.exact_windows = bool(exact_windows)
         if self.certified:
-            _lib.check(self._lib.ttup_wasb_certify_exact_windows(self._handle, 1 if getattr(self, 'exact_windows', False) else 0))
-            if getattr(self, 'exact_windows', False):
+            _lib.check(self._lib.ttup_wasb_certify_exact_windows(self._handle, 1 if self.exact_windows else 0))
+            if self.exact_windows:
                 self.certify_budget(2 * self.max_batch)
 
     def certify_audit_crops(self, every, phase=0):
         """Audit crops of the forwards that follow: of the frames f with (f + phase) % every == 0, one single-candidate heatmap gets an
-        fp32 crop as well, which reports |bf16 - fp32| at the winner (`certify_info` / `note_error`).  every = 0: off (default)."""
+        fp32 crop as well, which reports |bf16 - fp32| at the winner (`certify_info`, folded into eps by `EpsAudit.settle`).  every = 0: off (default)."""
         _lib.check(self._lib.ttup_wasb_certify_audit_crops(self._handle, int(every), int(phase)))
 
     def _make(self, resolution=None, max_batch=1, dtype='bf16'):
@@ -154,7 +155,7 @@ class WASBNet:
         """A one-sample bf16 handle with the same weights: the audit re-computes the production path's heatmap of a frame on its own
         buffers (the kernels are per-tile deterministic: same values as the batched handle, asserted in the tests), so it never
         touches the production handle's lanes or its per-call certification state."""
-        if getattr(self, '_bf16_twin', None) is None:
+        if self._bf16_twin is None:
             self._bf16_twin = self._make(dtype='bf16')
         return self._bf16_twin
 
@@ -178,57 +179,37 @@ class WASBNet:
             return max_abs_diff(hb[0], hf[0], out=out, accumulate=accumulate)
         S = self.AUDIT_STRIP
         xs = slice_columns(self._pre(fr), x0, S)
-        tw = self.__dict__.get('_strip_twins')
-        if tw is None:
+        if self._strip_twins is None:
             res = (S, self.H)
-            tw = self._strip_twins = (self._make(res, dtype='bf16'), self._make(res, dtype='f32'))
+            self._strip_twins = (self._make(res, dtype='bf16'), self._make(res, dtype='f32'))
+        tw = self._strip_twins
         c0 = 0 if x0 == 0 else self.AUDIT_MARGIN
         c1 = S if x0 + S >= self.W else S - self.AUDIT_MARGIN
         return max_abs_diff(tw[0]._heat(xs)[0], tw[1]._heat(xs)[0], cols=(c0, c1), out=out, accumulate=accumulate)
 
-    def calibrate(self, frames_u8, n=8, safety=None, crop=0, max_crops_per_map=0, exact_windows=None):
-        """First estimate of eps: HEADROOM * the largest bf16-vs-fp32 heatmap error on `n` triples spread over `frames_u8` (uint8
-        (N,h,w,3) device tensor).  Enables the certified argmax and returns eps.  The estimate is then kept honest by the audits."""
-        safety = self.HEADROOM if safety is None else safety
-        frames_u8 = frames_u8.to(self.device)
-        nt = frames_u8.shape[0] - (self.NF - 1)
-        n = max(1, min(n, nt))
-        picks = sorted(set(int(round(k * (nt - 1) / max(1, n - 1))) for k in range(n))) if n > 1 else [0]
-        err = max(float(self.heatmap_error(frames_u8, t).item()) for t in picks)
-        self.set_certify(safety * err, crop, max_crops_per_map, exact_windows)
-        self.audit_state = dict(audited_frames=len(picks), max_err_seen=err, widened=0)
+    def calibrate(self, frames_u8=None, n=8, exact_windows=None, x=None):
+        """First estimate of eps: HEADROOM x the largest bf16-vs-fp32 heatmap error on `n` samples spread over the uint8 (N,h,w,3) clip
+        `frames_u8`, or on the first `n` samples of the float input `x` (against this handle's own heatmaps).  The samples count as
+        audited.  Enables the certified argmax and returns eps; `EpsAudit` keeps it honest from then on."""
+        if x is not None:
+            picks = range(min(n, x.shape[0]))
+            hb = self._heat(x[:len(picks)])
+            twin = self._twin()
+            err = max(float(max_abs_diff(hb[k], twin._heat(x[k:k + 1])[0]).item()) for k in picks)
+        else:
+            frames_u8 = frames_u8.to(self.device)
+            nt = frames_u8.shape[0] - (self.NF - 1)
+            n = max(1, min(n, nt))
+            picks = sorted(set(int(round(k * (nt - 1) / max(1, n - 1))) for k in range(n))) if n > 1 else [0]
+            err = max(float(self.heatmap_error(frames_u8, t).item()) for t in picks)
+        self.set_certify(self.HEADROOM * err, exact_windows=exact_windows)
+        self.note_error(err, len(picks))
         return self.eps
 
-    def audit_async(self, frames_u8, picks):
-        """Re-run the triples `picks` of the clip on the bf16 audit twin and the fp32 twin on a side stream (behind everything the
-        current stream has enqueued) and leave max |bf16 - fp32| in pinned host memory.  Returns a ticket for `audit_result`."""
-        st = getattr(self, '_audit_stream', None)
-        if st is None:
-            st = self._audit_stream = torch.cuda.Stream(self.device)
-        st.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(st):
-            rng = self.__dict__.setdefault('_audit_rng', np.random.default_rng(12345))
-            err = torch.empty((1,), dtype=torch.float32, device=self.device)
-            for k, t in enumerate(picks):          # the running maximum lives in `err` (the library's kernel folds each sample in)
-                x0 = 8 * int(rng.integers(0, max(1, (self.W - self.AUDIT_STRIP) // 8 + 1)))
-                self.heatmap_error(frames_u8, int(t), x0, out=err, accumulate=k > 0)
-            host = torch.empty((1,), dtype=torch.float32, pin_memory=True)
-            host.copy_(err, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-        frames_u8.record_stream(st)
-        return {'host': host, 'event': ev, 'n': len(picks)}
-
-    def audit_result(self, ticket):
-        """Wait for an audit and fold it into `audit_state`.  Returns the error it measured."""
-        ticket['event'].synchronize()
-        err = float(ticket['host'][0])
-        return self.note_error(err, ticket['n'])
-
     def note_error(self, err, n_frames=0):
-        a = self.__dict__.setdefault('audit_state', dict(audited_frames=0, max_err_seen=0.0, widened=0))
-        a['audited_frames'] += n_frames
-        a['max_err_seen'] = max(a['max_err_seen'], err)
+        """Fold an observed |bf16 - fp32| error (and the number of samples it covers) into `audit_state`.  Returns err."""
+        self.audit_state['audited_frames'] += n_frames
+        self.audit_state['max_err_seen'] = max(self.audit_state['max_err_seen'], err)
         return err
 
     def eps_violated(self, err):
@@ -275,8 +256,9 @@ class WASBNet:
         return info
 
     @staticmethod
-    def decode_info(info_host):
-        a = np.asarray(info_host, dtype=np.int32)
+    def decode_info(info):
+        """`certify_info` (device or host) -> (n_crops, max_candidate_err)."""
+        a = np.asarray(_host(info), dtype=np.int32)
         return int(a[0]), float(a[1:2].view(np.float32)[0])
 
     def certify_stats(self, reset=False):
@@ -298,7 +280,7 @@ class WASBNet:
             raise ValueError('fix_uncertified covers one forward call of at most max_batch=%d samples' % self.max_batch)
         if status is None:
             status = self.certify_status(idx.shape[0])
-        st = (status.cpu().numpy() if torch.is_tensor(status) else np.asarray(status)) & 3
+        st = _host(status) & 3
         bad = np.nonzero(st == 2)[0]
         samples = np.unique(bad // K)
         if samples.size:
@@ -322,7 +304,7 @@ class WASBNet:
         SUBSET_MAX_SHARE of the heatmaps are guarded)."""
         if self.eps > eps_used * self.GUARD * (1 - 1e-6):
             return None
-        st = status_raw.cpu().numpy() if torch.is_tensor(status_raw) else np.asarray(status_raw)
+        st = _host(status_raw)
         todo = np.nonzero((st & 4) != 0)[0]
         if todo.size == 0:
             return todo
@@ -331,10 +313,10 @@ class WASBNet:
         # a one-sample certified handle of its own (same weights, same per-tile arithmetic as the production handle: its bf16
         # heatmaps are bit-identical, tests/test_certify_audit_gpu.py): the re-runs never touch the production handle's lanes or its
         # per-call certification slots, which a clip in flight may still be using
-        h = self.__dict__.get('_recert')
-        if h is None:
-            h = self._recert = self._make(dtype='bf16')
-            h._f32_twin = self._twin()
+        if self._recert is None:
+            self._recert = self._make(dtype='bf16')
+            self._recert._f32_twin = self._twin()
+        h = self._recert
         if not h.certified or h.eps != self.eps or h.exact_windows != self.exact_windows:
             h.set_certify(self.eps, exact_windows=self.exact_windows)
             # a one-sample handle defaults to ONE crop per call; a re-run frame may plan up to 8 per heatmap / 16 per frame, and what
@@ -345,8 +327,7 @@ class WASBNet:
             t = int(t)
             fr = frames_u8[t:t + self.NF]
             _, i1, w1 = h.forward_frames(fr, want_heatmap=False)
-            s1 = h.certify_status(K)
-            s1 = (s1.cpu().numpy() if torch.is_tensor(s1) else np.asarray(s1)) & 3
+            s1 = h.certify_status(K).cpu().numpy() & 3
             h.fix_uncertified(i1, w1, frames_u8=fr, status=s1)
             for m in todo[todo // K == t]:
                 idx[int(m)] = i1[int(m) - t * K]
@@ -374,6 +355,175 @@ class WASBNet:
         with torch.cuda.device(self.device):
             _lib.check(self._lib.ttup_wasb_read_tap(self._handle, name.encode(), batch, _lib.ptr(out), ctypes.byref(c), ctypes.byref(h), ctypes.byref(w), _lib.stream_ptr()))
         return out
+
+
+def _host(a):
+    """A status / info array on the host: device tensors are copied, host tensors and arrays are viewed."""
+    return a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+
+@dataclasses.dataclass
+class CertCall:
+    """One forward call of the certified argmax (`EpsAudit.enqueue`) on the input range f0:f1 (frames of a uint8 clip, or samples of a
+    float input), its peaks (updated in place by `settle`), raw status flags and info (device tensors, host arrays once settled; None
+    when the handle is not certified), the eps it ran under and, for a float input, its heatmaps."""
+    f0: int
+    f1: int
+    idx: torch.Tensor
+    win: torch.Tensor
+    status: object = None
+    info: object = None
+    eps_used: float = None
+    heat: torch.Tensor = None
+
+
+class EpsAudit:
+    """The host protocol of the certified argmax for one bf16 handle, which keeps its empirical eps honest after `WASBNet.calibrate`:
+      1. `enqueue`: a forward call, its status flags and info copied right behind it (the handle's per-call slot flips with its next call).
+      2. `picks` / `audit`: one sample per `rate()` samples re-run in both precisions -- `every_fast` until eps has stood for
+         `settle_clips` settles in a row, then `every`.  Every fp32 crop of a call reports the error at its candidates for free.
+      3. `settle`: fold those errors into eps (the handle's `audit_state`), widen it when one comes within SAFETY of it, re-run the
+         guarded heatmaps of calls certified under a smaller eps (`recertify_subset`) -- the whole call past the guard factor, or on
+         any widening for a float input -- and repair heatmaps over the crop budget on the fp32 twin (`fix_uncertified`)."""
+
+    def __init__(self, net, every=256, every_fast=None, settle_clips=0, seed=0):
+        self.net = net
+        self.every = int(every)
+        self.every_fast = self.every if every_fast is None else int(every_fast)
+        self.settle_clips = int(settle_clips)
+        self.seen = 0                  # samples counted by `picks`
+        self.quiet = 0                 # settles in a row without a widening
+        self.widen_sources = {'strip': 0, 'candidates': 0}
+        self.recertified_calls = 0     # whole calls run again
+        self.recertified_heatmaps = 0  # guarded heatmaps run again
+        self.fp32_reruns = 0           # samples repaired on the full-frame fp32 path
+        self.rng = np.random.default_rng(seed)              # which samples are audited
+        self.strip_rng = np.random.default_rng(12345)       # where an audit's strip lies
+        self.audit_stream = None
+        self._since = 0
+
+    @property
+    def eps(self):
+        """The bound the handle certifies under; None until calibrated."""
+        return self.net.eps if self.net.certified else None
+
+    def rate(self):
+        """Samples per audited sample right now (0: no audits)."""
+        if self.every <= 0:
+            return 0
+        return self.every_fast if self.quiet < self.settle_clips else self.every
+
+    def picks(self, n):
+        """Count the n samples of a call's input; returns those of them that the audit re-runs: one per `rate()` samples."""
+        self.seen += max(0, int(n))
+        every = self.rate()
+        if every <= 0 or n <= 0:
+            return []
+        self._since += n
+        out = []
+        while self._since >= every:
+            self._since -= every
+            out.append(int(self.rng.integers(n)))
+        return out
+
+    def audit(self, picks, frames_u8=None, x=None, heat=None):
+        """Enqueue the audit of the samples `picks` -> a ticket for `settle` (None without picks).  A uint8 clip: each sample's heatmap
+        re-computed on the one-sample bf16 audit twin and the fp32 twin over a quarter-width strip at a random column, on a side stream
+        behind everything the current stream has enqueued (enqueue it ahead of the call).  A float input: the call's own heatmaps
+        `heat` against the fp32 twin, on the current stream."""
+        if not picks:
+            return None
+        net = self.net
+        if x is not None:
+            err = torch.empty((1,), dtype=torch.float32, device=net.device)
+            for k, t in enumerate(picks):
+                max_abs_diff(heat[t], net._twin()._heat(x[t:t + 1])[0], out=err, accumulate=k > 0)
+            return self._ticket(err, len(picks))
+        if self.audit_stream is None:
+            self.audit_stream = torch.cuda.Stream(net.device)
+        st = self.audit_stream
+        st.wait_stream(torch.cuda.current_stream(net.device))
+        with torch.cuda.stream(st):
+            err = torch.empty((1,), dtype=torch.float32, device=net.device)
+            for k, t in enumerate(picks):          # the running maximum lives in `err` (the library's kernel folds each sample in)
+                x0 = 8 * int(self.strip_rng.integers(0, max(1, (net.W - net.AUDIT_STRIP) // 8 + 1)))
+                net.heatmap_error(frames_u8, int(t), x0, out=err, accumulate=k > 0)
+            ticket = self._ticket(err, len(picks))
+        frames_u8.record_stream(st)
+        return ticket
+
+    @staticmethod
+    def _ticket(err, n):
+        """max |bf16 - fp32| of n audited samples, copied to pinned host memory behind the audit on the current stream."""
+        host = torch.empty((1,), dtype=torch.float32, pin_memory=True)
+        host.copy_(err, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return {'host': host, 'event': ev, 'n': n}
+
+    def enqueue(self, frames_u8=None, f0=0, f1=None, x=None):
+        """Enqueue one forward call on the current stream -> CertCall: the samples of the uint8 clip frames_u8[f0:f1] (no heatmaps), or
+        of the float input x (with heatmaps).  Status flags and info are copied right behind it (not on an uncertified handle)."""
+        net, eps = self.net, self.eps
+        if x is None:
+            heat, idx, win = net.forward_frames(frames_u8[f0:f1], want_heatmap=False)
+        else:
+            heat, idx, win = WASBNet.forward(net, x, want_heatmap=True, want_peaks=True)
+        if not net.certified:
+            return CertCall(f0, f1, idx, win, heat=heat)
+        return CertCall(f0, f1, idx, win, net.certify_status(idx.shape[0], raw=True), net.certify_info(), eps, heat)
+
+    def run(self, frames_u8=None, x=None, counted=False):
+        """One call start to finish (blocking): audit, enqueue, settle -> its CertCall.  `settle` runs the whole call again through this
+        method with counted=True: its samples are not counted, and no audit drawn, a second time."""
+        n = x.shape[0] if x is not None else frames_u8.shape[0] - (self.net.NF - 1)
+        picks = [] if counted else self.picks(n)
+        audit = self.audit(picks, frames_u8) if x is None else None
+        call = self.enqueue(frames_u8, x=x)
+        if x is not None:
+            audit = self.audit(picks, x=x, heat=call.heat)
+        self.settle([call], frames_u8, x=x, audit=audit, rerun=lambda c: self.run(frames_u8, x, counted=True))
+        return call
+
+    def settle(self, calls, frames_u8=None, x=None, audit=None, rerun=None):
+        """The host half of enqueued calls on one input (the uint8 clip `frames_u8`, or one call on the float input `x`), once their
+        status and info are on the host or their stream has drained; `audit`: a ticket of `audit`.  In this order: fold the calls'
+        candidate errors and the audit into eps; widen it if one comes within SAFETY of it; re-certify each call whose eps_used is now
+        stale -- or, if eps grew past the guard factor, replace its peaks and status by those of `rerun(call)`, a new certified call on
+        the same input; repair its status-2 heatmaps on the fp32 twin.  Returns the positions of the calls whose idx / win changed."""
+        changed = set()
+        if not calls:
+            return changed
+        net = self.net
+        cand = net.note_error(max(net.decode_info(c.info)[1] for c in calls))
+        strip = 0.0
+        if audit is not None:
+            audit['event'].synchronize()
+            strip = net.note_error(float(audit['host'][0]), audit['n'])
+        err = max(cand, strip)
+        widened = net.eps_violated(err)
+        if widened:
+            net.widen_eps(err)
+            self.widen_sources['strip' if strip > cand else 'candidates'] += 1
+        self.quiet = 0 if widened else self.quiet + 1
+        for k, c in enumerate(calls):
+            c.status = _host(c.status)
+            fr = frames_u8[c.f0:c.f1] if frames_u8 is not None else None
+            if c.eps_used < net.eps:
+                todo = net.recertify_subset(c.idx, c.win, c.status, c.eps_used, fr) if x is None else None
+                if todo is None:
+                    self.recertified_calls += 1
+                    new = rerun(c)
+                    c.idx, c.win, c.status, c.heat = new.idx, new.win, new.status, new.heat
+                    changed.add(k)
+                    continue
+                self.recertified_heatmaps += int(todo.size)
+                if todo.size:
+                    changed.add(k)          # (c.status[todo] holds the re-runs' own status now: 0 or 1)
+            if ((c.status & 3) == 2).any():
+                self.fp32_reruns += net.fix_uncertified(c.idx, c.win, frames_u8=fr, x=x, status=c.status)
+                changed.add(k)
+        return changed
 
 
 class MyHRNet(WASBNet):
