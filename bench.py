@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: frames/s end-to-end (detect + refine + uplift) on synthetic 1280x720 video.
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--ops-json FILE]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full [--ops-json FILE]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A step = one pass of the hot path over one stream batch that is already resident in HBM:
@@ -15,10 +15,13 @@ before this process touches the GPU) and relays rank 0's line; under `torch.dist
 Every rank processes its own stream (independent units); the only collective is the final gather of
 the per-frame (x,y,v) records and the per-trajectory (spin, positions) records.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (the CNN kernel with the largest total
-time per micro-batch, HIP-event timed inside this process in graph order), `cpu_baseline` (the CPU oracle timed on a
-bounded sample) and, at N=1, the driver-timed extras for BASELINE configs 2, 3 and 5 (`cnn_only_fps`,
-`uplift_only_traj_s`, `trajgen_traj_s`).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does what the headline needs and nothing else:
+set-up, W warm-up steps, the K timed steps, the --dump-outputs records and the line.  `--full` adds the rest to the same line:
+`cpu_baseline` (the CPU oracle timed on a bounded sample, run before this process touches the GPU), `roofline` (the CNN graph,
+HIP-event timed inside this process in graph order, with the heatmap rooflines and the device's measured peaks), at N=1 the
+other legs (`e2e_from_host_fps`, the weight / content / parity regimes and the driver-timed extras for BASELINE configs 1, 2, 3
+and 5: `cnn_only_fps`, `uplift_only_traj_s`, `trajgen_traj_s`, ...) and at N>1 every rank's stream -> hardware-queue grouping
+(`stream_queue_groups`).  --no-cpu-baseline / --no-roofline / --no-extras leave a part of --full out.
 """
 import argparse
 import json
@@ -51,15 +54,20 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)          # (the driver's own flags: --steps 20 --warmup 5)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also run the CPU baseline, the roofline, the other legs (N=1) and the queue probes (N>1)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip the roofline')
     ap.add_argument('--no-certify', action='store_true', help='plain bf16 argmax (no fp32 re-evaluation of near-ties)')
-    ap.add_argument('--no-extras', action='store_true', help='skip the config 2/3/5 legs (cnn-only, uplift-only, generator)')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the other legs (from-host, regimes, configs 1/2/3/5)')
     ap.add_argument('--dump-outputs', metavar='DIR', help='write the records of the last timed step (all ranks, rank order) as DIR/<key>.npy')
-    ap.add_argument('--ops-json', metavar='FILE', help='write the per-op timings behind `roofline` to FILE (nothing is written into the source tree)')
+    ap.add_argument('--ops-json', metavar='FILE', help='with --full: write the per-op timings behind `roofline` to FILE (nothing is written into the source tree)')
     a = ap.parse_args()
     if a.steps < 1:
         ap.error('--steps must be at least 1')
+    if a.ops_json and not a.full:
+        ap.error('--ops-json writes the roofline\'s per-op timings: it needs --full')
+    if not a.full:          # a plain run: set-up, warm-up, timed steps, --dump-outputs and the line, nothing else
+        a.no_cpu_baseline = a.no_roofline = a.no_extras = True
     return a
 
 
@@ -738,7 +746,7 @@ def spawn_ranks(a):
         port = sk.getsockname()[1]
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(a.gpus), '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.abspath(__file__), '--gpus', str(a.gpus), '--steps', str(a.steps), '--warmup', str(a.warmup)]
-    cmd += ['--no-cpu-baseline'] * a.no_cpu_baseline + ['--no-roofline'] * a.no_roofline + ['--no-extras'] * a.no_extras + ['--no-certify'] * a.no_certify
+    cmd += ['--full'] * a.full + ['--no-cpu-baseline'] * a.no_cpu_baseline + ['--no-roofline'] * a.no_roofline + ['--no-extras'] * a.no_extras + ['--no-certify'] * a.no_certify
     if a.dump_outputs:
         cmd += ['--dump-outputs', os.path.abspath(a.dump_outputs)]
     if a.ops_json:
@@ -821,13 +829,15 @@ def main():
     dist = None
     collective = None
     pre_init_q = None
+    probe_queues = (a.full and world > 1) or os.environ.get('TTUP_BENCH_QUEUE_PROBE') == '1'
     if world > 1:
         # the worker's stream -> hardware-queue grouping BEFORE the process group exists (RCCL creates streams of its own): compared
         # with the grouping after the timed region, `queue_mapping_changed` in the line says whether the collective's streams moved it
-        try:
-            pre_init_q = pipe.worker.queue_groups()
-        except Exception as e:
-            pre_init_q = 'probe failed: %r' % (e,)
+        if probe_queues:
+            try:
+                pre_init_q = pipe.worker.queue_groups()
+            except Exception as e:
+                pre_init_q = 'probe failed: %r' % (e,)
         import torch.distributed as dist
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         if backend == 'nccl':
@@ -897,7 +907,7 @@ def main():
     # GPU in a dry run would disturb each other's probes): the single-GPU mapping is the best one seen and every
     # rank should have it -- an N-GPU line then says so itself
     queue_groups = None
-    if dist is not None or os.environ.get('TTUP_BENCH_QUEUE_PROBE') == '1':
+    if probe_queues:
         mine_q = None
         for r in range(world):
             if r == rank:

@@ -183,6 +183,16 @@ def test_bench_refuses_zero_steps():
     assert r.returncode == 2 and '--steps' in r.stderr and not r.stdout.strip()
 
 
+def test_bench_refuses_ops_json_without_full(tmp_path):
+    """`--ops-json` writes the per-op timings behind `roofline`, which only a `--full` run measures: without --full it is refused
+    before anything runs, and nothing is written."""
+    import subprocess
+    import sys
+    ops = tmp_path / 'ops.json'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--ops-json', str(ops)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and '--full' in r.stderr and not r.stdout.strip() and not ops.exists()
+
+
 def test_blob_layout_roundtrip():
     sd = weights.random_wasb_state_dict(3)
     blob = weights.pack_wasb_blob(sd)

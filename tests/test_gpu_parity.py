@@ -891,6 +891,27 @@ def test_bench_two_rank_flow_on_one_gpu():
     assert abs(rec['value'] - 2 * 256 * 2 / (rec['ms_per_step'] * 2 / 1e3)) / rec['value'] < 1e-3
 
 
+def test_bench_plain_run_prints_the_headline_alone(tmp_path):
+    """A plain `python bench.py --gpus 1` does what its headline needs and nothing else: set-up, warm-up, the timed steps, the
+    --dump-outputs records and ONE line.  What --full adds (CPU baseline, roofline, the other legs, queue probes) is not in it."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'TTUP_BENCH_QUEUE_PROBE')}
+    dump = tmp_path / 'outputs'
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--dump-outputs', str(dump)],
+                         env=env, cwd=root, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec['n_gpus'] == 1 and rec['steps'] == 2 and rec['warmup'] == 1 and rec['unit'] == 'frames/s' and rec['higher_is_better'] is True and rec['dtype'] == 'bf16'
+    assert abs(rec['value'] - 256 * 2 / (rec['ms_per_step'] * 2 / 1e3)) / rec['value'] < 1e-3
+    moved = {'cpu_baseline', 'cpu_baseline_b4', 'roofline', 'roofline_heatmap', 'peaks_measured', 'e2e_from_host_fps', 'cnn_only_fps',
+             'noise_weights_fps', 'exact_windows_fps', 'varied_content_fps', 'uplift_only_traj_s', 'hub_clip_fps', 'trajgen_traj_s', 'stream_queue_groups'}
+    assert not moved & set(rec), sorted(moved & set(rec))
+    assert sorted(f.name for f in dump.iterdir()) == ['n_valid.npy', 'pos3d.npy', 'spin.npy', 'xyv.npy']
+
+
 def test_bench_spawns_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no torch.distributed environment: the parent starts the two ranks itself (before it
     touches the GPU) and relays rank 0's line.  Same dry-run transport as above (two ranks share this box's GPU, gloo)."""
@@ -899,7 +920,7 @@ def test_bench_spawns_its_own_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     env.update(TTUP_BENCH_SHARE_GPU='1', TTUP_DIST_BACKEND='gloo')
     dump = tmp_path / 'outputs'
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--no-roofline', '--no-cpu-baseline',
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--full', '--no-roofline', '--no-cpu-baseline',
                           '--dump-outputs', str(dump)], env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -938,7 +959,7 @@ def test_bench_four_rank_dry_run_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'OMP_NUM_THREADS')}
     env.update(TTUP_BENCH_SHARE_GPU='1', TTUP_DIST_BACKEND='gloo')
-    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '4', '--steps', '1', '--warmup', '1', '--no-roofline', '--no-cpu-baseline', '--no-extras'],
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '4', '--steps', '1', '--warmup', '1', '--full', '--no-roofline', '--no-cpu-baseline', '--no-extras'],
                          env=env, cwd=root, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -1089,7 +1110,7 @@ def test_bench_two_rank_flow_over_rccl():
         env.update(TTUP_BENCH_SHARE_GPU='1', TTUP_DIST_BACKEND='gloo')
 
     def run(gpus):
-        out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(gpus), '--steps', '6', '--warmup', '3', '--no-roofline',
+        out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', str(gpus), '--steps', '6', '--warmup', '3', '--full', '--no-roofline',
                               '--no-cpu-baseline', '--no-extras'], env=env, cwd=root, capture_output=True, text=True, timeout=1500)
         assert out.returncode == 0, out.stderr[-3000:]
         lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{') and '"metric"' in ln]

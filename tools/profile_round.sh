@@ -10,9 +10,9 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; S=$O/summary
 rm -rf $O; mkdir -p $S
 cd $R
-rocprofv3 --output-format csv --kernel-trace --stats -d $O/kt2 -o kt -- python3 bench.py --no-cpu-baseline --no-extras --steps 4 > $S/${TAG}_bench_lanes2.json 2> $O/kt2.err
+rocprofv3 --output-format csv --kernel-trace --stats -d $O/kt2 -o kt -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 4 > $S/${TAG}_bench_lanes2.json 2> $O/kt2.err
 # one lane and no fp32 crop passes: only the side streams (pre-processing of the next step, refine, uplift) still overlap
-TTUP_LANES=1 rocprofv3 --output-format csv --kernel-trace --stats -d $O/kt1 -o kt -- python3 bench.py --no-cpu-baseline --no-extras --no-certify --steps 4 > $S/${TAG}_bench_lanes1.json 2> $O/kt1.err
+TTUP_LANES=1 rocprofv3 --output-format csv --kernel-trace --stats -d $O/kt1 -o kt -- python3 bench.py --full --no-cpu-baseline --no-extras --no-certify --steps 4 > $S/${TAG}_bench_lanes1.json 2> $O/kt1.err
 rocprofv3 --output-format csv --kernel-trace --stats -d $O/ktu -o kt -- python3 tools/bench_uplift.py > $O/ktu.log 2>&1
 # one micro-batch of the CNN alone on one stream, 20 repeats: nothing else runs, the averages are isolated launch durations
 TTUP_PROF_REPS=20 rocprofv3 --output-format csv --kernel-trace --stats -d $O/ktc -o kt -- python3 tools/prof_cnn.py > $O/ktc.log 2>&1
