@@ -246,11 +246,29 @@ int ttup_refine_windows(const int64_t* argmax_dev, const float* win_dev, int n_m
                         int img_w, int img_h, int variant, double* out_xyv_dev, void* stream);
 
 /* ---------------------------------------------------------------- a6: uplift transformer
- * Replaces MultiStageModel.forward (uplifting/model.py:529-571, 'connectstage', mode 'dynamic',
- * time_rotation 'new') behind `self.model(ball, table, mask, times)` (interface.py:235, inference/utils.py:254).
+ * Replaces the forward of every model uplifting/model.py:574-603 get_model builds -- SingleStageModel (:393-499) and
+ * MultiStageModel (:502-571) -- behind `self.model(ball, table, mask, times)` (interface.py:235, inference/utils.py:254).  The
+ * variant travels in the blob; a blob with variant == 0 and time_rotation == 0 is 'connectstage' / 'dynamic' / 'new', the only
+ * one earlier versions wrote.
  * blob: upliftingtabletennis_amd.weights.pack_uplift_blob:
- *   char magic[8]="TTUPUPL1"; int32 dim, heads, n_pos_layers, n_first_layers, n_second_layers, n_table, 0, 0;
- *   then every tensor of the state_dict (reference order, without embed.* and inv_freq): int32 numel; float data[numel].
+ *   char magic[8]="TTUPUPL1";
+ *   int32 dim, heads, n_pos_layers, n_first_layers, n_second_layers, n_table, variant, time_rotation;
+ *     variant        = name | mode << 4; name: 0 connectstage, 1 multistage, 2 singlestage;
+ *                      mode: 0 dynamic, 1 stacked, 2 originalmethod, 3 free (singlestage only; originalmethod not for singlestage)
+ *     time_rotation  = 0 'new' (RoPE index round(t / 0.002 s)), 1 'old' (index of the token in its sequence)
+ *     n_pos_layers   = 4 for mode dynamic, else 0; n_second_layers = 0 for singlestage (n_first_layers = depth), else 4
+ *   then records, each int32 numel; float data[numel], weights row-major as in the state_dict:
+ *     inv_freq (head_dim/2), cls_token (dim),
+ *     ball_embed fc1.weight (dim x K), fc1.bias, fc2.weight, fc2.bias     K = 2; 41 stacked; 28 originalmethod
+ *     table_embed fc1.weight (dim x 2), fc1.bias, fc2.weight, fc2.bias    mode dynamic only
+ *     n_pos_layers + n_first_layers layers, each: qkv.weight, qkv.bias, proj.weight, mlp1.fc1.weight, .bias, mlp1.fc2.weight, .bias,
+ *                                                 norm1.weight, .bias, norm2.weight, .bias
+ *     position_head fc1.weight, .bias, fc2.weight, .bias, fc3.weight, .bias
+ *     embed fc1.weight (dim x 3), fc1.bias, fc2.weight, fc2.bias          multistage only
+ *     n_second_layers layers
+ *     rotation_head (as position_head)
+ *   This is state_dict order without the per-layer inv_freq, except that `embed` (present in both two-stage models' state dicts,
+ *   read by multistage alone) moves in front of the second stage and singlestage's position head in front of its rotation head.
  */
 int  ttup_uplift_create(const void* blob, size_t blob_bytes, int max_batch, int max_len, ttup_uplift** out);
 void ttup_uplift_destroy(ttup_uplift* net);

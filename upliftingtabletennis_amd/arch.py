@@ -97,26 +97,78 @@ def _head(p, d):
             (p + '.fc3.weight', (3, d // 4)), (p + '.fc3.bias', (3,))]
 
 
+UPLIFT_NAMES = ('connectstage', 'multistage', 'singlestage')          # blob header hdr[6] & 15
+UPLIFT_MODES = ('dynamic', 'stacked', 'originalmethod', 'free')       # blob header hdr[6] >> 4
+UPLIFT_ROTATIONS = ('new', 'old')                                     # blob header hdr[7]
+
+
+def check_uplift_variant(name, size, mode, time_rotation='new'):
+    """Raise what the reference's get_model raises (model.py:574-603, :311, :404): AssertionError for a time_rotation or a mode
+    the named model does not take, ValueError for an unknown name or size."""
+    assert time_rotation in ['old', 'new'], 'time_rotation should be either "old" or "new"'
+    if name not in UPLIFT_NAMES:
+        raise ValueError(f'Unknown model name {name}')
+    if size not in UPLIFT_SIZES:
+        raise ValueError(f'Unknown model size {size}')
+    if name == 'singlestage':
+        assert mode in ['free', 'dynamic', 'stacked'], 'mode should be either "free", "dynamic", "stacked"'
+    else:
+        assert mode in ['dynamic', 'stacked', 'originalmethod'], 'mode should be either "dynamic", "stacked" or "originalmethod"'
+
+
+def uplift_variants():
+    """Every (name, mode, time_rotation) the reference's get_model builds: 18 combinations."""
+    out = []
+    for name in ('singlestage', 'multistage', 'connectstage'):
+        for mode in (('free', 'dynamic', 'stacked') if name == 'singlestage' else ('dynamic', 'stacked', 'originalmethod')):
+            out += [(name, mode, rot) for rot in UPLIFT_ROTATIONS]
+    return out
+
+
+def uplift_embed_width(mode):
+    """Input width of ball_embed.fc1: x, y and, stacked onto every token, the 13 table keypoints with (41) or without (28) visibility."""
+    return {'stacked': 13 * 3 + 2, 'originalmethod': 13 * 2 + 2}.get(mode, 2)
+
+
+def uplift_variant_layers(name, size, mode):
+    """Layer-prefix lists (pos_layers, layers, secondstage); the first is empty unless mode is 'dynamic', the last for
+    'singlestage', whose `layers` are all `depth` layers (model.py:421-424)."""
+    check_uplift_variant(name, size, mode)
+    d, depth, heads = UPLIFT_SIZES[size]
+    p = '' if name == 'singlestage' else 'firststage.'
+    return ([p + 'pos_layers.%d' % i for i in range(N_POS_LAYERS)] if mode == 'dynamic' else [],
+            [p + 'layers.%d' % i for i in range(depth if name == 'singlestage' else depth - N_SECOND)],
+            [] if name == 'singlestage' else ['secondstage.%d' % i for i in range(N_SECOND)])
+
+
+def uplift_variant_schema(name, size, mode):
+    """[(state_dict key, shape)] of get_model(name, size, mode, .) in reference order (time_rotation changes no key)."""
+    d, depth, heads = UPLIFT_SIZES[size]
+    pos, first, second = uplift_variant_layers(name, size, mode)
+    p = '' if name == 'singlestage' else 'firststage.'
+    out = [('cls_token', (1, 1, d))]
+    if name != 'singlestage':
+        out += _mlp_embed('embed', 3, d)                   # read by multistage only, present in connectstage too (model.py:513)
+    out += _mlp_embed(p + 'ball_embed', uplift_embed_width(mode), d)
+    if mode == 'dynamic':
+        out += _mlp_embed(p + 'table_embed', 2, d)
+    for q in pos + first:
+        out += _layer(q, d)
+    if name == 'singlestage':
+        out += _head('rotation_head', d) + _head('position_head', d)
+    else:
+        out += _head('firststage.position_head', d)
+        for q in second:
+            out += _layer(q, d)
+        out += _head('rotation_head', d)
+    return [(k, s if s is not None else (d // heads // 2,)) for k, s in out]
+
+
 def uplift_layers(size='large'):
     """Layer-prefix lists (pos_layers, layers, secondstage) for a 'connectstage' model."""
-    d, depth, heads = UPLIFT_SIZES[size]
-    return (['firststage.pos_layers.%d' % i for i in range(N_POS_LAYERS)],
-            ['firststage.layers.%d' % i for i in range(depth - N_SECOND)],
-            ['secondstage.%d' % i for i in range(N_SECOND)])
+    return uplift_variant_layers('connectstage', size, 'dynamic')
 
 
 def uplift_schema(size='large'):
     """[(state_dict key, shape)] of get_model('connectstage', size, 'dynamic', 'new') in reference order."""
-    d, depth, heads = UPLIFT_SIZES[size]
-    pos, first, second = uplift_layers(size)
-    out = [('cls_token', (1, 1, d))]
-    out += _mlp_embed('embed', 3, d)                       # unused by connectstage but present (model.py:513)
-    out += _mlp_embed('firststage.ball_embed', 2, d)
-    out += _mlp_embed('firststage.table_embed', 2, d)
-    for p in pos + first:
-        out += _layer(p, d)
-    out += _head('firststage.position_head', d)
-    for p in second:
-        out += _layer(p, d)
-    out += _head('rotation_head', d)
-    return [(k, s if s is not None else (d // heads // 2,)) for k, s in out]
+    return uplift_variant_schema('connectstage', size, 'dynamic')

@@ -1,5 +1,6 @@
-// a6/a7: the 2D->3D uplift transformer (reference uplifting/model.py 'connectstage', mode 'dynamic',
-// time_rotation 'new') and the spin frame change (uplifting/helper.py:394-420), fp32 throughout.
+// a6/a7: the 2D->3D uplift transformer (reference uplifting/model.py; the structure below is 'connectstage', mode 'dynamic',
+// time_rotation 'new'; the other variants get_model builds are sequences of the same pieces, see forward_chunk) and the spin
+// frame change (uplifting/helper.py:394-420), fp32 throughout.
 //
 // Structure (all tokens of a chunk of trajectories are processed as flat [tokens][D] arrays):
 //   embed        BallEmbedding / TableEmbedding  model.py:105-158
@@ -1687,6 +1688,103 @@ __global__ void prepend_cls_kernel(const float* x, const float* cls, float* y, i
     const int t = (int)(r % (T + 1)); const long long b = r / (T + 1);
     y[i] = t == 0 ? cls[d] : x[(b * T + (t - 1)) * D + d];
 }
+// y[b, t] = x[b, 1+t] on rows of 3 floats: the position head of 'singlestage' runs over all T+1 rows of every sequence (model.py:495-497)
+__global__ void strip_cls3_kernel(const float* x, float* y, int T, long long total) {
+    const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
+    if (i >= total) return;
+    const int c = (int)(i % 3);
+    const long long r = i / 3;
+    const long long b = r / T; const int t = (int)(r % T);
+    y[i] = x[(b * (T + 1) + 1 + t) * 3 + c];
+}
+// rope[r][i] = (cos, sin)(r * inv_freq[i]): time_rotation 'old' turns by the token's index in the sequence (model.py:73-75)
+__global__ void rope_index_kernel(const float* inv_freq, float2* rope, int half, long long total) {
+    const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
+    if (i >= total) return;
+    const float f = (float)(i / half) * inv_freq[i % half];
+    rope[i] = make_float2(cosf(f), sinf(f));
+}
+// Modes 'stacked' / 'originalmethod' (model.py:345-353): h[b,t] = relu(fc1([ball[b,t], table[b] flattened])), K = 2 + 13*TW with
+// TW = 3 (x, y, visibility) or 2.  The stacked (B,T,K) input is never built: a workgroup serves 32 tokens of ONE trajectory, reduces
+// the table columns of fc1 (and the bias) once into LDS, and adds the two ball columns per token.  wt is fc1.weight transposed [K][D].
+// PER_TOKEN: every output sums its K products in column order instead, bias last (the order of a plain linear layer over the
+// stacked input; TTUP_UPLIFT_STACKED_PER_TOKEN, the cross-check of the summation order).
+constexpr int STACKED_TOKENS = 32;
+template <bool PER_TOKEN>
+__global__ __launch_bounds__(256) void stacked_embed_kernel(const float* __restrict__ ball, const float* __restrict__ table, const float* __restrict__ wt,
+                                                            const float* __restrict__ bias, float* __restrict__ out, int T, int D, int TW) {
+    __shared__ float tab[39];
+    __shared__ float c[256];          // D <= 256 (ttup_uplift_create)
+    const int b = ttup_bid_x(), t0 = ttup_bid_y() * STACKED_TOKENS, tid = ttup_tid_x();
+    const int KT = 13 * TW;
+    if (tid < KT) tab[tid] = table[((size_t)b * 13 + tid / TW) * 3 + tid % TW];
+    __syncthreads();
+    if (!PER_TOKEN) {
+        if (tid < D) {
+            float acc = bias[tid];
+            for (int k = 0; k < KT; ++k) acc = fmaf(tab[k], wt[(size_t)(2 + k) * D + tid], acc);
+            c[tid] = acc;
+        }
+        __syncthreads();
+    }
+    const int nt = T - t0 < STACKED_TOKENS ? T - t0 : STACKED_TOKENS;
+    for (int i = tid; i < nt * D; i += 256) {
+        const int t = t0 + i / D, n = i % D;
+        const float* bp = ball + ((size_t)b * T + t) * 2;
+        float v;
+        if (PER_TOKEN) {
+            v = fmaf(bp[1], wt[D + n], bp[0] * wt[n]);
+            for (int k = 0; k < KT; ++k) v = fmaf(tab[k], wt[(size_t)(2 + k) * D + n], v);
+            v += bias[n];
+        } else v = fmaf(bp[1], wt[D + n], fmaf(bp[0], wt[n], c[n]));
+        out[((size_t)b * T + t) * D + n] = v > 0.f ? v : 0.f;
+    }
+}
+// 'multistage' (model.py:549-560): x[b, 0] = cls, x[b, 1+t] = embed(pos[b, t]) = fc2(relu(fc1(pos))) with fc1 3 -> D, fc2 D -> D.
+// A workgroup serves 16 tokens: the hidden rows go to LDS, then thread (n, half) accumulates 8 tokens of output column n over k
+// (w2t = fc2.weight transposed [D][D]: consecutive n read consecutive words, the hidden values are LDS broadcasts).
+constexpr int EMBED3_TOKENS = 16;
+__global__ __launch_bounds__(256) void embed3_cls_kernel(const float* __restrict__ pos, const float* __restrict__ w1t, const float* __restrict__ b1,
+                                                         const float* __restrict__ w2t, const float* __restrict__ b2, const float* __restrict__ cls,
+                                                         float* __restrict__ x, int T, int D, long long tokens) {
+    __shared__ float h[EMBED3_TOKENS][256];          // D <= 256
+    const int tid = ttup_tid_x();
+    const long long r0 = (long long)ttup_bid_x() * EMBED3_TOKENS;
+    for (int i = tid; i < EMBED3_TOKENS * D; i += 256) {
+        const int j = i / D, n = i % D;
+        const long long r = r0 + j;
+        float v = 0.f;
+        if (r < tokens) {
+            const float* p = pos + r * 3;
+            v = fmaf(p[2], w1t[2 * D + n], fmaf(p[1], w1t[D + n], fmaf(p[0], w1t[n], b1[n])));
+            v = v > 0.f ? v : 0.f;
+        }
+        h[j][n] = v;
+    }
+    __syncthreads();
+    for (int i = tid; i < 2 * D; i += 256) {
+        const int n = i % D, j0 = (i / D) * (EMBED3_TOKENS / 2);
+        float acc[EMBED3_TOKENS / 2];
+#pragma unroll
+        for (int j = 0; j < EMBED3_TOKENS / 2; ++j) acc[j] = b2[n];
+        for (int k = 0; k < D; ++k) {
+            const float w = w2t[(size_t)k * D + n];
+#pragma unroll
+            for (int j = 0; j < EMBED3_TOKENS / 2; ++j) acc[j] = fmaf(h[j0 + j][k], w, acc[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < EMBED3_TOKENS / 2; ++j) {
+            const long long r = r0 + j0 + j;
+            if (r < tokens) x[((r / T) * (T + 1) + 1 + r % T) * D + n] = acc[j];
+        }
+    }
+    // the cls rows of the trajectories that START in this tile
+    for (int j = 0; j < EMBED3_TOKENS; ++j) {
+        const long long r = r0 + j;
+        if (r < tokens && r % T == 0)
+            for (int n = tid; n < D; n += 256) x[(r / T) * (T + 1) * D + n] = cls[n];
+    }
+}
 // masks: mask (B,T) {0,1} -> additive m1 (B,T), m2 (B,T+1) with leading 0; table (B,13,3) -> tmask (B,14), txy (B*13,2)
 __global__ void prepare_kernel(const float* mask, const float* table, float* m1, float* m2, float* tmask, float* txy, int B, int T, int NT, int* flags) {
     const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
@@ -1729,11 +1827,19 @@ __global__ void rotationaxes_kernel(const float* rot, const float* pos, int B, i
 struct Layer { Linear qkv, proj, fc1, fc2; float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr; };
 struct Mlp2 { Linear fc1, fc2; };
 struct Head { Linear fc1, fc2, fc3; };
+// the variant of get_model a blob holds (hdr[6], hdr[7]; include/ttup.h)
+enum { NAME_CONNECT = 0, NAME_MULTI = 1, NAME_SINGLE = 2 };
+enum { MODE_DYNAMIC = 0, MODE_STACKED = 1, MODE_ORIGINAL = 2, MODE_FREE = 3 };
 
 }  // namespace
 
 struct ttup_uplift {
     int D = 0, heads = 0, hd = 0, n_table = 13, max_batch = 0, max_len = 0, chunk = 1;
+    int name = NAME_CONNECT, mode = MODE_DYNAMIC; bool rot_old = false;
+    float *embed_w1t = nullptr, *embed_b1 = nullptr, *embed_w2t = nullptr, *embed_b2 = nullptr;      // 'multistage': embed, weights transposed [K][D]
+    float *stacked_wt = nullptr, *stacked_b = nullptr;                                                // 'stacked' / 'originalmethod': ball_embed.fc1 transposed [K][D]
+    float2* rope_index = nullptr;          // time_rotation 'old': [max_len][hd/2], row = index of the token in its sequence
+    float* pos_rows = nullptr;             // 'singlestage': position head output on all T+1 rows
     std::vector<Layer> pos_layers, layers, second;
     Mlp2 ball_embed, table_embed;
     Head position_head, rotation_head;
@@ -1834,6 +1940,18 @@ int make_linear(ttup_uplift* net, Reader& r, int n, int k, bool has_bias, Linear
     if (rc) return rc;
     if (has_bias) { rc = dev_copy(net, b, &L->b_dev); if (rc) return rc; }
     return TTUP_OK;
+}
+
+// a [n][k] weight record stored transposed [k][n] (+ its bias) for the per-column kernels (stacked_embed_kernel, embed3_cls_kernel)
+int make_linear_t(ttup_uplift* net, Reader& r, int n, int k, float** wt, float** b) {
+    std::vector<float> w, bias;
+    TTUP_REQUIRE(r.take(&w, (size_t)n * k), TTUP_EFORMAT, "uplift blob: bad weight record (%dx%d)", n, k);
+    TTUP_REQUIRE(r.take(&bias, n), TTUP_EFORMAT, "uplift blob: bad bias record (%d)", n);
+    std::vector<float> t((size_t)n * k);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < k; ++j) t[(size_t)j * n + i] = w[(size_t)i * k + j];
+    if (int rc = dev_copy(net, t, wt)) return rc;
+    return dev_copy(net, bias, b);
 }
 
 int make_vec(ttup_uplift* net, Reader& r, int n, float** out) {
@@ -2114,6 +2232,13 @@ int run_head(ttup_uplift* net, const Head& h, const float* x, int ldx, long long
     return run_linear(h.fc3, net->att, D / 4, M, nullptr, nullptr, 0, nullptr, 0, out, 3, st);
 }
 
+// One chunk of trajectories.  Every variant is a sequence of the same pieces (model.py:303-571):
+//   tokens    dynamic: ball_embed (2 -> D -> D), table_embed, table stage;  stacked / originalmethod: stacked_embed_kernel + fc2;
+//             free: ball_embed alone
+//   connectstage  temporal stage (depth-4 layers) -> position head;  cls + tokens   -> spin stage (4 layers) -> rotation head
+//   multistage    temporal stage (depth-4 layers) -> position head;  cls + embed(pos) (embed3_cls_kernel) -> spin stage -> rotation head
+//   singlestage   cls + tokens -> one stage of all `depth` layers -> rotation head on row 0, position head on rows 1..T
+// time_rotation 'old' reads the fixed by-index (cos, sin) table (row stride 0 between sequences) instead of the per-forward one.
 int forward_chunk(ttup_uplift* net, const float* ball, const float* table, const float* mask, const float* times, int B, int T,
                   float* rot, float* pos, hipStream_t st) {
     const int D = net->D, NT = net->n_table, S1 = NT + 1;
@@ -2123,43 +2248,69 @@ int forward_chunk(ttup_uplift* net, const float* ball, const float* table, const
         hipLaunchKernelGGL(prepare_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mask, table, net->m1, net->m2, net->tmask, net->txy, B, T, NT, net->flags_dev);
         TTUP_LAUNCH_CHECK();
     }
-    {
+    const float2* rope = net->rope_index;
+    const int rope_stride = net->rot_old ? 0 : T;
+    if (!net->rot_old) {
         const long long n = (long long)B * T * (net->hd / 2);
         hipLaunchKernelGGL(rope_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, times, net->inv_freq_dev, net->rope, net->hd / 2, n);
         TTUP_LAUNCH_CHECK();
+        rope = net->rope;
     }
     // embeddings
-    if ((rc = run_linear(net->ball_embed.fc1, ball, 2, (long long)B * T, nullptr, nullptr, 1, nullptr, 0, net->h1, D, st))) return rc;
+    if (net->mode == MODE_STACKED || net->mode == MODE_ORIGINAL) {
+        static const bool per_token = getenv("TTUP_UPLIFT_STACKED_PER_TOKEN") != nullptr;          // the other summation order (cross-check)
+        const dim3 grid((unsigned)B, (unsigned)((T + STACKED_TOKENS - 1) / STACKED_TOKENS));
+        const int tw = net->mode == MODE_STACKED ? 3 : 2;
+        if (per_token) hipLaunchKernelGGL(stacked_embed_kernel<true>, grid, dim3(256), 0, st, ball, table, net->stacked_wt, net->stacked_b, net->h1, T, D, tw);
+        else hipLaunchKernelGGL(stacked_embed_kernel<false>, grid, dim3(256), 0, st, ball, table, net->stacked_wt, net->stacked_b, net->h1, T, D, tw);
+        TTUP_LAUNCH_CHECK();
+    } else if ((rc = run_linear(net->ball_embed.fc1, ball, 2, (long long)B * T, nullptr, nullptr, 1, nullptr, 0, net->h1, D, st))) return rc;
     if ((rc = run_linear(net->ball_embed.fc2, net->h1, D, (long long)B * T, nullptr, nullptr, 0, nullptr, 0, net->tok, D, st))) return rc;
-    if ((rc = run_linear(net->table_embed.fc1, net->txy, 2, (long long)B * NT, nullptr, nullptr, 1, nullptr, 0, net->h1, D, st))) return rc;
-    if ((rc = run_linear(net->table_embed.fc2, net->h1, D, (long long)B * NT, nullptr, nullptr, 0, nullptr, 0, net->ttok, D, st))) return rc;
-    // table stage: every (b, t) is a 14-token sequence [ball token, 13 table tokens]; its row 0 replaces the ball token afterwards
-    const long long tok1 = (long long)B * T * S1;
-    static const bool no_token_fusion = getenv("TTUP_UPLIFT_ASSEMBLE") != nullptr;
-    bool fused = false;
-    if (!no_token_fusion) {
-        // stage kernel: reads the two token tensors itself and writes row 0 only (nothing has been launched if it declines)
-        if ((rc = run_stage(net, net->pos_layers, net->stage_pos, net->tok, tok1, B * T, S1, 1, net->tmask, T, net->table_rope, 1, 0, st, net->ttok, T, NT, &fused))) return rc;
+    if (net->mode == MODE_DYNAMIC) {
+        if ((rc = run_linear(net->table_embed.fc1, net->txy, 2, (long long)B * NT, nullptr, nullptr, 1, nullptr, 0, net->h1, D, st))) return rc;
+        if ((rc = run_linear(net->table_embed.fc2, net->h1, D, (long long)B * NT, nullptr, nullptr, 0, nullptr, 0, net->ttok, D, st))) return rc;
+        // table stage: every (b, t) is a 14-token sequence [ball token, 13 table tokens]; its row 0 replaces the ball token afterwards
+        const long long tok1 = (long long)B * T * S1;
+        static const bool no_token_fusion = getenv("TTUP_UPLIFT_ASSEMBLE") != nullptr;
+        bool fused = false;
+        if (!no_token_fusion) {
+            // stage kernel: reads the two token tensors itself and writes row 0 only (nothing has been launched if it declines)
+            if ((rc = run_stage(net, net->pos_layers, net->stage_pos, net->tok, tok1, B * T, S1, 1, net->tmask, T, net->table_rope, 1, 0, st, net->ttok, T, NT, &fused))) return rc;
+        }
+        if (!fused) {
+            const long long total = tok1 * D;
+            hipLaunchKernelGGL(assemble_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, net->tok, net->ttok, net->x, T, NT, D, total);
+            TTUP_LAUNCH_CHECK();
+            if ((rc = run_stage(net, net->pos_layers, net->stage_pos, net->x, tok1, B * T, S1, 1, net->tmask, T, net->table_rope, 1, 0, st))) return rc;
+            const long long total2 = (long long)B * T * D;
+            hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((total2 + 255) / 256)), dim3(256), 0, st, net->x, net->tok, D, S1, total2);
+            TTUP_LAUNCH_CHECK();
+        }
     }
-    if (!fused) {
-        const long long total = tok1 * D;
-        hipLaunchKernelGGL(assemble_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, net->tok, net->ttok, net->x, T, NT, D, total);
-        TTUP_LAUNCH_CHECK();
-        if ((rc = run_stage(net, net->pos_layers, net->stage_pos, net->x, tok1, B * T, S1, 1, net->tmask, T, net->table_rope, 1, 0, st))) return rc;
-        const long long total2 = (long long)B * T * D;
-        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((total2 + 255) / 256)), dim3(256), 0, st, net->x, net->tok, D, S1, total2);
-        TTUP_LAUNCH_CHECK();
+    if (net->name != NAME_SINGLE) {
+        // temporal stage (tok is [B*T][D])
+        if ((rc = run_stage(net, net->layers, net->stage_first, net->tok, (long long)B * T, B, T, 0, net->m1, 1, rope, 1, rope_stride, st))) return rc;
+        if ((rc = run_head(net, net->position_head, net->tok, D, (long long)B * T, pos, st))) return rc;
     }
-    // temporal stage (tok is [B*T][D])
-    if ((rc = run_stage(net, net->layers, net->stage_first, net->tok, (long long)B * T, B, T, 0, net->m1, 1, net->rope, 1, T, st))) return rc;
-    if ((rc = run_head(net, net->position_head, net->tok, D, (long long)B * T, pos, st))) return rc;
-    // spin stage
-    {
+    // cls token in front of every sequence (x is [B*(T+1)][D])
+    if (net->name == NAME_MULTI) {
+        const long long tokens = (long long)B * T;
+        hipLaunchKernelGGL(embed3_cls_kernel, dim3((unsigned)((tokens + EMBED3_TOKENS - 1) / EMBED3_TOKENS)), dim3(256), 0, st,
+                           pos, net->embed_w1t, net->embed_b1, net->embed_w2t, net->embed_b2, net->cls_dev, net->x, T, D, tokens);
+        TTUP_LAUNCH_CHECK();
+    } else {
         const long long total = (long long)B * (T + 1) * D;
         hipLaunchKernelGGL(prepend_cls_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, net->tok, net->cls_dev, net->x, T, D, total);
         TTUP_LAUNCH_CHECK();
     }
-    if ((rc = run_stage(net, net->second, net->stage_second, net->x, (long long)B * (T + 1), B, T + 1, 1, net->m2, 1, net->rope, 1, T, st))) return rc;
+    if (net->name == NAME_SINGLE) {
+        if ((rc = run_stage(net, net->layers, net->stage_first, net->x, (long long)B * (T + 1), B, T + 1, 1, net->m2, 1, rope, 1, rope_stride, st))) return rc;
+        // position head on every row, the cls rows dropped afterwards (3 floats a row; the head's rows must be evenly spaced)
+        if ((rc = run_head(net, net->position_head, net->x, D, (long long)B * (T + 1), net->pos_rows, st))) return rc;
+        const long long total = (long long)B * T * 3;
+        hipLaunchKernelGGL(strip_cls3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, net->pos_rows, pos, T, total);
+        TTUP_LAUNCH_CHECK();
+    } else if ((rc = run_stage(net, net->second, net->stage_second, net->x, (long long)B * (T + 1), B, T + 1, 1, net->m2, 1, rope, 1, rope_stride, st))) return rc;
     // rotation head on the cls rows (row stride (T+1)*D)
     return run_head(net, net->rotation_head, net->x, (T + 1) * D, B, rot, st);
 }
@@ -2178,11 +2329,17 @@ extern "C" int ttup_uplift_create(const void* blob, size_t blob_bytes, int max_b
     std::unique_ptr<ttup_uplift> net(new ttup_uplift);
     net->D = hdr[0]; net->heads = hdr[1]; net->n_table = hdr[5];
     const int n_pos = hdr[2], n_first = hdr[3], n_second = hdr[4];
+    net->name = hdr[6] & 15; net->mode = hdr[6] >> 4; net->rot_old = hdr[7] == 1;
+    TTUP_REQUIRE(hdr[6] >= 0 && net->name <= NAME_SINGLE && net->mode <= MODE_FREE && (hdr[7] == 0 || hdr[7] == 1) &&
+                 (net->mode == MODE_FREE ? net->name == NAME_SINGLE : net->mode != MODE_ORIGINAL || net->name != NAME_SINGLE),
+                 TTUP_EFORMAT, "uplift blob: variant %d / time rotation %d is none that get_model builds", hdr[6], hdr[7]);
     TTUP_REQUIRE(net->D > 0 && net->D % 32 == 0 && net->D <= 256 && net->heads > 0 && net->D % net->heads == 0, TTUP_EFORMAT,
                  "uplift blob: dim %d / heads %d unsupported", net->D, net->heads);
     net->hd = net->D / net->heads;
     TTUP_REQUIRE(net->hd == 8 || net->hd == 16 || net->hd == 24 || net->hd == 32, TTUP_EFORMAT, "uplift blob: head_dim %d unsupported", net->hd);
     TTUP_REQUIRE(net->n_table == 13 && n_pos >= 0 && n_first >= 0 && n_second >= 0 && n_pos + n_first + n_second <= 64, TTUP_EFORMAT, "uplift blob: bad layer counts");
+    TTUP_REQUIRE((n_pos > 0) == (net->mode == MODE_DYNAMIC) && n_first > 0 && (n_second > 0) == (net->name != NAME_SINGLE), TTUP_EFORMAT,
+                 "uplift blob: layer counts %d/%d/%d do not fit variant %d", n_pos, n_first, n_second, hdr[6]);
     net->max_batch = max_batch; net->max_len = max_len;
     Reader r{(const char*)blob + 40, blob_bytes - 40};
     int rc;
@@ -2193,12 +2350,19 @@ extern "C" int ttup_uplift_create(const void* blob, size_t blob_bytes, int max_b
         if ((rc = dev_copy(net.get(), v, &net->inv_freq_dev))) return rc;
     }
     if ((rc = make_vec(net.get(), r, D, &net->cls_dev))) return rc;
-    if ((rc = make_mlp2(net.get(), r, 2, &net->ball_embed))) return rc;
-    if ((rc = make_mlp2(net.get(), r, 2, &net->table_embed))) return rc;
+    if (net->mode == MODE_STACKED || net->mode == MODE_ORIGINAL) {
+        if ((rc = make_linear_t(net.get(), r, D, 2 + net->n_table * (net->mode == MODE_STACKED ? 3 : 2), &net->stacked_wt, &net->stacked_b))) return rc;
+        if ((rc = make_linear(net.get(), r, D, D, true, &net->ball_embed.fc2))) return rc;
+    } else if ((rc = make_mlp2(net.get(), r, 2, &net->ball_embed))) return rc;
+    if (net->mode == MODE_DYNAMIC && (rc = make_mlp2(net.get(), r, 2, &net->table_embed))) return rc;
     net->pos_layers.resize(n_pos); net->layers.resize(n_first); net->second.resize(n_second);
     for (auto& L : net->pos_layers) if ((rc = make_layer(net.get(), r, &L))) return rc;
     for (auto& L : net->layers) if ((rc = make_layer(net.get(), r, &L))) return rc;
     if ((rc = make_head(net.get(), r, &net->position_head))) return rc;
+    if (net->name == NAME_MULTI) {
+        if ((rc = make_linear_t(net.get(), r, D, 3, &net->embed_w1t, &net->embed_b1))) return rc;
+        if ((rc = make_linear_t(net.get(), r, D, D, &net->embed_w2t, &net->embed_b2))) return rc;
+    }
     for (auto& L : net->second) if ((rc = make_layer(net.get(), r, &L))) return rc;
     if ((rc = make_head(net.get(), r, &net->rotation_head))) return rc;
     TTUP_REQUIRE(r.left == 0, TTUP_EFORMAT, "uplift blob: %zu trailing bytes", r.left);
@@ -2213,7 +2377,9 @@ extern "C" int ttup_uplift_create(const void* blob, size_t blob_bytes, int max_b
         if ((rc = dev_alloc(net.get(), (size_t)net->n_table * net->hd, &tr))) return rc;
         net->table_rope = (float2*)tr;
         const long long n = (long long)net->n_table * (net->hd / 2);
-        hipLaunchKernelGGL(rope_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, net->table_times_dev, net->inv_freq_dev, net->table_rope, net->hd / 2, n);
+        // ('new' turns table token n by index round(n/100 / 0.002) = 5n, 'old' by n itself)
+        if (net->rot_old) hipLaunchKernelGGL(rope_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, net->inv_freq_dev, net->table_rope, net->hd / 2, n);
+        else hipLaunchKernelGGL(rope_table_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, net->table_times_dev, net->inv_freq_dev, net->table_rope, net->hd / 2, n);
         TTUP_LAUNCH_CHECK();
     }
     // scratch: chunk of trajectories such that the table stage holds at most ~2M tokens (7 GB of fp32 scratch at D=128)
@@ -2239,6 +2405,15 @@ extern "C" int ttup_uplift_create(const void* blob, size_t blob_bytes, int max_b
     float* fl = nullptr;
     if ((rc = dev_alloc(net.get(), bt * net->hd, &fl))) return rc;
     net->rope = (float2*)fl;
+    if (net->rot_old) {
+        const size_t rows = (size_t)max_len + 64;          // (the attention kernels' padded key tiles stay inside the table)
+        if ((rc = dev_alloc(net.get(), rows * net->hd, &fl))) return rc;
+        net->rope_index = (float2*)fl;
+        const long long n = (long long)rows * (net->hd / 2);
+        hipLaunchKernelGGL(rope_index_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, net->inv_freq_dev, net->rope_index, net->hd / 2, n);
+        TTUP_LAUNCH_CHECK();
+    }
+    if (net->name == NAME_SINGLE && (rc = dev_alloc(net.get(), bt * 3, &net->pos_rows))) return rc;
     if ((rc = dev_alloc(net.get(), 4, &fl))) return rc;
     net->flags_dev = (int*)fl;
     {

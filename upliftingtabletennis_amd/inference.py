@@ -10,7 +10,7 @@ handle's ``max_batch`` instead of 4 frames (frames are independent, the results 
 import numpy as np
 import torch
 
-from . import _lib, refine, uplift
+from . import _lib, refine, uplift, weights
 
 HEIGHT, WIDTH = 1080, 1920          # inference/utils.py:25 (from helper_balldetection)
 
@@ -41,3 +41,22 @@ def process_trajectory_uplifting(uplifting_model, predictions_ball, predictions_
         pred_spin = uplift.transform_rotationaxes(pred_spin, pos3d)
     t_prime = int(torch.as_tensor(mask).sum().item())
     return pred_spin[0].cpu().numpy(), pos3d[0, :t_prime, :].cpu().numpy()
+
+
+def normalize_img_coords(data):
+    """NormalizeImgCoords (uplifting/transformations.py:252-266), the transform ``load_model`` returns: divide by the uplift
+    resolution 2560x1440."""
+    r_img, table_img = data['r_img'], data['table_img']
+    r_img = r_img / np.array([2560, 1440])
+    table_img[..., :2] = table_img[..., :2] / np.array([2560, 1440])
+    data['r_img'], data['table_img'] = r_img, table_img
+    return data
+
+
+def load_uplifting_model(model_path, max_batch=64, max_len=128):
+    """Counterpart of inference/inference_uplifting.py:33-58 ``load_model``: open an uplift checkpoint by path and build the variant
+    its ``additional_info`` names (name, size, tabletoken_mode, time_rotation).  -> (model, transform, transform_mode)."""
+    sd, info = weights.load_checkpoint_state_dict(model_path)
+    model = uplift.get_model(info['name'], info['size'], info['tabletoken_mode'], info['time_rotation'], state_dict=sd,
+                             max_batch=max_batch, max_len=max_len)
+    return model.eval(), normalize_img_coords, info['transform_mode']

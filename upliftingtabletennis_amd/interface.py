@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, calib, glue, refine, uplift, vitpose, wasb, weights
+from . import _lib, calib, glue, inference, refine, uplift, vitpose, wasb, weights
 
 HEIGHT, WIDTH = 1080, 1920
 KEYPOINT_VISIBLE = 1
@@ -352,9 +352,14 @@ class ViTPoseTableDetector(TableDetector):
 
 
 class UpliftingModel:
-    def __init__(self, max_len=128):
+    def __init__(self, max_len=128, model_path=None):
+        """model_path: an uplift checkpoint of any variant the reference's ``load_model`` opens (inference.load_uplifting_model);
+        None: the hub's `ours` slot, which holds the shipped connectstage/dynamic/new configuration."""
         _lib.require_gpu()
         self.device = torch.device('cuda')
+        if model_path is not None:
+            self.model, _, self.transform_mode = inference.load_uplifting_model(model_path, max_batch=64, max_len=max_len)
+            return
         sd, size, self.transform_mode = _load_uplift_checkpoint()
         self.model = uplift.get_model('connectstage', size, 'dynamic', 'new', state_dict=sd, max_batch=64, max_len=max_len)
 

@@ -104,6 +104,19 @@ def synth_trajectories(b, t, seed=0, pad=1, fps_choices=(50.0, 60.0, 120.0)):
     return ball, table, mask, times
 
 
+def ragged_uplift_batch(b, t, seed=0, pad=1):
+    """`synth_trajectories` made ragged the way the uplift fixtures are: the second trajectory cut to half its length, irregular
+    time stamps (dropped frames) on the first, keypoints 3 and 9 of the first table invisible."""
+    ball, table, mask, times = synth_trajectories(b, t, seed=seed, pad=pad)
+    if b > 1:
+        cut = max(3, t // 2)
+        ball[1, cut:] = 0; mask[1, cut:] = 0; times[1, cut:] = 0
+        keep = np.sort(np.random.default_rng(seed).choice(t + 6, t, replace=False))
+        times[0, :t] = (keep / 60.0).astype(np.float32)
+        table[0, 3, 2] = 0; table[0, 9, 2] = 0
+    return ball, table, mask, times
+
+
 def vitpose_inputs(seed, b, c, h, w, amp=4.0, sigma=2.0, noise=0.5):
     """(b,c,h,w) float32 detector inputs in the normalised range (noise plus one bright Gaussian blob per sample, on every
     channel) and the (b,2) blob centres (x, y): seeded test inputs of the ViTPose fixtures (tools/make_goldens_vitpose.py)."""

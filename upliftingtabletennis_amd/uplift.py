@@ -1,6 +1,7 @@
 """a6/a7: drop-in for the uplift network behind ``self.model(ball, table, mask, times) -> (rot, pos)``
 (interface.py:235, inference/utils.py:254) and for ``transform_rotationaxes`` (uplifting/helper.py:394-420).
-Reference model: uplifting/model.py:502-571 built by get_model('connectstage', size, 'dynamic', 'new')."""
+Reference models: everything uplifting/model.py:574-603 ``get_model`` builds -- SingleStageModel (:393-499) and MultiStageModel
+(:502-571, 'multistage' / 'connectstage') with their table-token modes and both RoPE time conventions."""
 import ctypes
 
 import torch
@@ -9,15 +10,18 @@ from . import _lib, arch, weights
 
 
 class MultiStageModel:
-    def __init__(self, state_dict, size='large', max_batch=64, max_len=128, device='cuda:0'):
+    """One native handle for any variant (the class keeps the name of the shipped default's reference class)."""
+
+    def __init__(self, state_dict, size='large', max_batch=64, max_len=128, device='cuda:0', name='connectstage', mode='dynamic', time_rotation='new'):
+        arch.check_uplift_variant(name, size, mode, time_rotation)
         _lib.require_gpu()
         self.device = torch.device(device)
         self.size = size
         self.dim, self.depth, self.heads = arch.UPLIFT_SIZES[size]
         self.max_batch, self.max_len = int(max_batch), int(max_len)
-        self.time_rotation = 'new'
+        self.name, self.mode, self.time_rotation = name, mode, time_rotation
         self._lib = _lib.load()
-        blob = weights.pack_uplift_blob(state_dict, size)
+        blob = weights.pack_uplift_blob(state_dict, size, name, mode, time_rotation)
         self._handle = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(self._lib.ttup_uplift_create(blob, len(blob), self.max_batch, self.max_len, ctypes.byref(self._handle)))
@@ -64,15 +68,12 @@ class MultiStageModel:
 
 
 def get_model(name='connectstage', size='large', mode='dynamic', time_rotation='new', state_dict=None, **kw):
-    """Mirror of uplifting/model.py:574-603 for the shipped configuration."""
-    assert time_rotation in ['old', 'new'], 'time_rotation should be either "old" or "new"'
-    if name != 'connectstage' or mode != 'dynamic' or time_rotation != 'new':
-        raise ValueError('only the shipped configuration connectstage/dynamic/new is built (see DESIGN.md)')
-    if size not in arch.UPLIFT_SIZES:
-        raise ValueError(f'Unknown model size {size}')
+    """Mirror of uplifting/model.py:574-603: every (name, size, mode, time_rotation) the reference builds, and its AssertionError /
+    ValueError for the rest -- raised before the native library is touched."""
+    arch.check_uplift_variant(name, size, mode, time_rotation)
     if state_dict is None:
         raise ValueError('a state_dict is required (no weights can be downloaded offline)')
-    return MultiStageModel(state_dict, size=size, **kw)
+    return MultiStageModel(state_dict, size=size, name=name, mode=mode, time_rotation=time_rotation, **kw)
 
 
 def transform_rotationaxes(rotation, r_gt):

@@ -67,13 +67,15 @@ def random_wasb_state_dict(seed=0, planted=False, in_ch=9, head_out=3, eps=0.2, 
     return sd
 
 
-def random_uplift_state_dict(seed=0, size='large'):
+def random_uplift_state_dict(seed=0, size='large', name='connectstage', mode='dynamic', time_rotation='new'):
     """Seeded uplift-transformer weights (xavier-like scale as model.py:22-28,117-121,178-184,243-249;
-    biases and LayerNorm randomised so that every term is exercised)."""
+    biases and LayerNorm randomised so that every term is exercised) of get_model(name, size, mode, time_rotation).
+    `time_rotation` changes no weight: 'new' and 'old' of one seed are the same state dict."""
+    arch.check_uplift_variant(name, size, mode, time_rotation)
     rng = np.random.default_rng(seed)
     d, depth, heads = arch.UPLIFT_SIZES[size]
     sd = {}
-    for k, shape in arch.uplift_schema(size):
+    for k, shape in arch.uplift_variant_schema(name, size, mode):
         if k.endswith('inv_freq'):
             hd = d // heads
             sd[k] = (1.0 / (10000 ** (np.arange(0, hd, 2, dtype=np.float32) / np.float32(hd)))).astype(np.float32)
@@ -112,19 +114,36 @@ def pack_wasb_blob(state_dict, in_ch=9, head_out=3, prefix='model'):
     return b''.join(parts)
 
 
-def pack_uplift_blob(state_dict, size='large'):
-    """Reference-format state_dict -> bytes for ``ttup_uplift_create``."""
+def pack_uplift_blob(state_dict, size='large', name='connectstage', mode='dynamic', time_rotation='new'):
+    """Reference-format state_dict -> bytes for ``ttup_uplift_create`` (header and record order: include/ttup.h).
+    Raises ValueError naming the first key that is missing, has another variant's shape, or belongs to no layer of this variant."""
+    arch.check_uplift_variant(name, size, mode, time_rotation)
     d, depth, heads = arch.UPLIFT_SIZES[size]
-    pos, first, second = arch.uplift_layers(size)
-    parts = [UPLIFT_MAGIC, struct.pack('<8i', d, heads, len(pos), len(first), len(second), 13, 0, 0)]
+    pos, first, second = arch.uplift_variant_layers(name, size, mode)
+    schema = arch.uplift_variant_schema(name, size, mode)
+    known = {k for k, _ in schema}
+    for k in state_dict:
+        if k not in known:
+            raise ValueError('%s: not a key of uplift variant %s/%s (size %s)' % (k, name, mode, size))
+    for k, shape in schema:
+        if k not in state_dict:
+            raise ValueError('%s: missing from the state dict (uplift variant %s/%s, size %s)' % (k, name, mode, size))
+        if _np(state_dict[k]).shape != tuple(shape):
+            raise ValueError('%s: expected shape %s, got %s' % (k, shape, _np(state_dict[k]).shape))
+    variant = arch.UPLIFT_NAMES.index(name) | arch.UPLIFT_MODES.index(mode) << 4
+    parts = [UPLIFT_MAGIC, struct.pack('<8i', d, heads, len(pos), len(first), len(second), 13, variant, arch.UPLIFT_ROTATIONS.index(time_rotation))]
     inv = _np(state_dict[(pos + first + second)[0] + '.attn.rotary_emb.inv_freq'])   # identical in every layer (model.py:51)
     parts += [struct.pack('<i', inv.size), inv.tobytes()]
-    for k, shape in arch.uplift_schema(size):
-        if k.endswith('inv_freq') or k.startswith('embed.'):
-            continue
+    # records in state_dict order, except: `embed` (read by multistage only) goes in front of the second stage, and singlestage's
+    # position head in front of its rotation head, so that every variant reads ... layers, position head, [embed], second, rotation head
+    body = [(k, shape) for k, shape in schema if not k.endswith('inv_freq') and not k.startswith('embed.')]
+    if name == 'singlestage':
+        body = [e for e in body if not e[0].startswith('rotation_head.')] + [e for e in body if e[0].startswith('rotation_head.')]
+    if name == 'multistage':
+        at = [e[0] for e in body].index(second[0] + '.attn.qkv.weight')
+        body[at:at] = [(k, shape) for k, shape in schema if k.startswith('embed.')]
+    for k, shape in body:
         v = _np(state_dict[k])
-        if v.shape != tuple(shape):
-            raise ValueError('%s: expected shape %s, got %s' % (k, shape, v.shape))
         parts.append(struct.pack('<i', v.size))
         parts.append(v.tobytes())
     return b''.join(parts)
