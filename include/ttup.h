@@ -338,6 +338,35 @@ int ttup_odefit_forward(const double* obs_xy_dev, const double* times_dev, const
 int ttup_odefit_integrate(const double* params_dev, const double* times_dev, const double* cam_dev, int cam_per_traj, int batch, int len,
                           double h_max, double* pos3d_dev, double* px_dev, void* stream);
 
+/* ---------------------------------------------------------------- uplift training samples from generated trajectories (csrc/dataset.hip)
+ * Replaces uplifting/data.py::TableTennisDataset.__getitem__ (:77-166, sample_camera :168-223) and the train transforms of
+ * uplifting/transformations.py::get_transforms (:286-300), in the reference's order, fp64, cast to float32 at the end.
+ * One sample = one (trajectory index, sample seed) pair; sample seed s reproduces `random.seed(s); np.random.seed(s); dataset[i]`
+ * (0 <= s < 2^32, np.random.seed's range).  Call ttup_dataset_seed, then ttup_dataset_build with the same n and workspace.
+ *   rows_dev (R,9) float64 packed trajectories (position, velocity, rotation), offsets_dev (V+1) int64, bounces_dev (V,4),
+ *   n_bounces_dev (V) int32, times_dev (n_times) the shared time labels; mext_dev (V or 1, 4x4), mint_dev (V or 1, 3x3) the stored
+ *   camera ('test' mode; cam_per_traj != 0: one per trajectory; may be null in 'train' mode).
+ *   traj_index_host (n) int64 and seeds_host (n) int64 are HOST arrays (checked before anything is launched).
+ *   mode: 0 train, 1 test (fps 50, stored camera, NormalizeImgCoords only).
+ *   strengths_host[6]: blur_strength, randomize_std, stop_prob, randdet_prob, randmiss_prob, tablemiss_prob.
+ *   transform_mask: bit k switches transform k on (MotionBlur, RandomizeDetections, RandomStop, RandomDetection, RandomMissing,
+ *   TableMissing; bit 6: NormalizeImgCoords, the only one 'test' mode looks at); a cleared bit is the reference's Identity in that
+ *   place (its numpy draws are skipped).
+ *   out32_host / out64_host: HOST arrays of nine DEVICE pointers -- r_img (n,50,2), table_img (n,13,3), mask (n,50), r_world (n,50,3),
+ *   rotation (n,3), times (n,50), bounces (n,1), Mint (n,3,3), Mext (n,4,4) -- float32 / float64; either set may be null, not both.
+ *   diag_dev (n,4) int32: fps, n_frames (before the crop to 50), camera_tries, camera_success (fps -1: bad offsets, zeros written).
+ *   record_dev (n,150) int32 or null (tests): per frame slot the nearest stored sample, the MotionBlur sample, the RandomMissing drop.
+ * ttup_dataset_draws (tests): the next `count` raw MT19937 words of stream `which` (0 CPython random, 1 numpy) of every seeded
+ * sample, out_dev (n,count) uint32; it advances the states, so seed again before a build. */
+size_t ttup_dataset_workspace_bytes(int n);
+int ttup_dataset_seed(const int64_t* seeds_host, int n, void* workspace, size_t workspace_bytes, void* stream);
+int ttup_dataset_draws(void* workspace, size_t workspace_bytes, int n, int which, int count, uint32_t* out_dev, void* stream);
+int ttup_dataset_build(const double* rows_dev, const int64_t* offsets_dev, int64_t n_rows, int n_traj, const double* bounces_dev,
+                       const int* n_bounces_dev, const double* times_dev, int n_times, const double* mext_dev, const double* mint_dev,
+                       int cam_per_traj, const int64_t* traj_index_host, int n, int mode, const double* strengths_host,
+                       unsigned transform_mask, void* const* out32_host, void* const* out64_host, int* diag_dev, int* record_dev,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

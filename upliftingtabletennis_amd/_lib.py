@@ -70,6 +70,10 @@ SIGNATURES = {
     'ttup_vitpose_micro_batch': (_i, [_vp]),
     'ttup_vitpose_forward': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'ttup_vitpose_forward_frames': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'ttup_dataset_workspace_bytes': (_sz, [_i]),
+    'ttup_dataset_seed': (_i, [_vp, _i, _vp, _sz, _vp]),
+    'ttup_dataset_draws': (_i, [_vp, _sz, _i, _i, _i, _vp, _vp]),
+    'ttup_dataset_build': (_i, [_vp, _vp, _c.c_longlong, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _c.c_uint, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None
