@@ -269,6 +269,8 @@ int ttup_refine_windows(const int64_t* argmax_dev, const float* win_dev, int n_m
  *     rotation_head (as position_head)
  *   This is state_dict order without the per-layer inv_freq, except that `embed` (present in both two-stage models' state dicts,
  *   read by multistage alone) moves in front of the second stage and singlestage's position head in front of its rotation head.
+ * A 'connectstage' / 'dynamic' handle also keeps the records as plain fp32 on the device for ttup_uplift_loss_grad (one more copy of
+ * the weights: 0.3 MB small, 1.7 MB base, 8.2 MB large, 18.5 MB huge), whether or not gradients are ever asked for.
  */
 int  ttup_uplift_create(const void* blob, size_t blob_bytes, int max_batch, int max_len, ttup_uplift** out);
 void ttup_uplift_destroy(ttup_uplift* net);
@@ -287,6 +289,31 @@ int ttup_uplift_graph_info(ttup_uplift* net, int* out_host3);
  * of a stage in one launch with the tokens resident on the CU (TTUP_UPLIFT_NO_STAGE=1 switches it off, TTUP_UPLIFT_STAGE_WG caps the
  * launch size it is used for).  *out_host = such launches issued or captured so far. */
 int ttup_uplift_stage_info(ttup_uplift* net, long long* out_host);
+
+/* ---------------------------------------------------------------- uplift training loss and its parameter gradients (csrc/uplift_grad.hip)
+ * Replaces, for one batch, the forward, the loss and `loss.backward()` of uplifting/train.py:121-128 for the configuration the
+ * reference trains, get_model('connectstage', size, 'dynamic', time_rotation):
+ *   loss_rot = sum_b ||pred_rot_b - rot_b||_2,  loss_pos = sum (pred_pos - r_world)^2 mask / sum mask,  loss = loss_rot + loss_pos.
+ * A handle that holds any other variant is refused with TTUP_EINVAL before anything touches a device.  Clipping, the optimizer and
+ * the EMA are not part of it.
+ *
+ * ttup_uplift_grad_layout: the flat gradient buffer holds the tensors of arch.uplift_variant_schema(name, size, mode) in that
+ * order, without the `*.rotary_emb.inv_freq` buffers.  *n_floats = its length, *n_tensors = the number of tensors; offsets_host /
+ * used_host (nullable, `capacity` entries each) receive every tensor's offset and whether it gets a gradient: the four `embed.*`
+ * tensors, which 'connectstage' never reads (`.grad is None` in the reference), are present, written as zeros and marked 0.
+ * ttup_uplift_grad_workspace_bytes: bytes of caller-allocated device scratch for a call with (batch, len); 0 for a null or
+ * unsupported handle.  It grows with min(batch, 262144 / (14 len)) trajectories: larger batches are processed in groups of that size.
+ * ttup_uplift_loss_grad: ball (B,T,2), table (B,13,3), mask (B,T) in {0,1}, times (B,T), r_world (B,T,3), rotation (B,3), all
+ * float32 on the device.  flags bit 0: transform_mode 'local' -- the target spin is first passed through
+ * ttup_transform_rotationaxes(rotation, r_world) (train.py:123-124; no gradient flows into it).  Outputs (device): grad
+ * (n_floats), loss[2] = {loss_rot, loss_pos}, rot (B,3), pos (B,T,3).  len <= 255.  No floating-point atomics: two calls on the
+ * same inputs return the same bits, whatever the handle's max_batch.  A padded time step (mask 0) or an invisible keypoint
+ * contributes exactly zero to every output but its own rows of pos. */
+int    ttup_uplift_grad_layout(ttup_uplift* net, long long* n_floats, int* n_tensors, long long* offsets_host, int* used_host, int capacity);
+size_t ttup_uplift_grad_workspace_bytes(ttup_uplift* net, int batch, int len);
+int    ttup_uplift_loss_grad(ttup_uplift* net, const float* ball_dev, const float* table_dev, const float* mask_dev, const float* times_dev,
+                             const float* r_world_dev, const float* rotation_dev, int batch, int len, int flags, void* workspace,
+                             size_t workspace_bytes, float* grad_dev, float* loss_dev, float* rot_dev, float* pos_dev, void* stream);
 
 /* ---------------------------------------------------------------- a7: spin frame change
  * Replaces transform_rotationaxes (uplifting/helper.py:394-420): rot (B,3), pos (B,T,3) -> out (B,3). */

@@ -29,7 +29,7 @@ GFLOP = {'linear': 2 * N * (384 * 1152 + 384 * 384 + 2 * 384 * 1536) * 12 / 1e9,
          'patch_embed': 2 * N * 384 * 9 * 256 / 1e9,
          'conv1x1': 2 * 16 * N * 256 / 1e9}
 FP32_MFMA_PEAK = 157.3      # TFLOP/s, v_mfma_f32_16x16x4_f32 (1/16 of the bf16 MFMA rate); 155 measured with register-resident loops
-FAMILIES = [('attention', 'attention_kernel'), ('patch_embed', 'gemm_kernel<2>'), ('deconv', 'gemm_kernel<3>'),
+FAMILIES = [('attention', 'attention_kernel'), ('patch_embed', 'gemm_kernel<2,'), ('deconv', 'gemm_kernel<3,'),
             ('linear', 'gemm_kernel<'), ('layernorm', 'ln_'), ('conv1x1', 'conv1x1_kernel'), ('argmax', 'argmax_')]
 
 

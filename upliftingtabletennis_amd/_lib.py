@@ -57,6 +57,9 @@ SIGNATURES = {
     'ttup_uplift_graph_info': (_i, [_vp, _vp]),
     'ttup_uplift_stage_info': (_i, [_vp, _vp]),
     'ttup_uplift_forward': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp]),
+    'ttup_uplift_grad_layout': (_i, [_vp, _vp, _vp, _vp, _vp, _i]),
+    'ttup_uplift_grad_workspace_bytes': (_sz, [_vp, _i, _i]),
+    'ttup_uplift_loss_grad': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     'ttup_transform_rotationaxes': (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     'ttup_trajgen_max_samples': (_i, []),
     'ttup_trajgen_workspace_bytes': (_sz, [_i]),

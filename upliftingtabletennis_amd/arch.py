@@ -164,6 +164,32 @@ def uplift_variant_schema(name, size, mode):
     return [(k, s if s is not None else (d // heads // 2,)) for k, s in out]
 
 
+UPLIFT_GRAD_VARIANT = ('connectstage', 'dynamic')      # what the reference trains by default (uplifting/train.py:17-21); the only variant with gradients
+
+
+def check_uplift_grad_variant(name, mode):
+    """ValueError for a variant whose training loss / gradients are not served (csrc/uplift_grad.hip)."""
+    if (name, mode) != UPLIFT_GRAD_VARIANT:
+        raise ValueError('loss_and_grad serves %s/%s only, not uplift variant %s/%s' % (UPLIFT_GRAD_VARIANT + (name, mode)))
+
+
+def uplift_grad_layout(size='large'):
+    """[(parameter name, shape, offset, used)] of the flat gradient buffer of ttup_uplift_loss_grad: `uplift_variant_schema` order
+    without the `inv_freq` buffers (requires_grad=False, model.py:51), offsets in floats, contiguous.  `used` is False for the four
+    `embed.*` tensors: 'connectstage' holds them (model.py:513) and never reads them, so the reference leaves their `.grad` None;
+    their slots are written as zeros.  -> (layout, n_floats)"""
+    out, off = [], 0
+    for k, shape in uplift_variant_schema(*UPLIFT_GRAD_VARIANT[:1], size, UPLIFT_GRAD_VARIANT[1]):
+        if k.endswith('.inv_freq'):
+            continue
+        n = 1
+        for s in shape:
+            n *= s
+        out.append((k, tuple(shape), off, not k.startswith('embed.')))
+        off += n
+    return out, off
+
+
 def uplift_layers(size='large'):
     """Layer-prefix lists (pos_layers, layers, secondstage) for a 'connectstage' model."""
     return uplift_variant_layers('connectstage', size, 'dynamic')

@@ -17,6 +17,7 @@
 //                   semantics).  Short sequences (the 14-token table stage) share a wave four at a time.
 #include "no_packed_fp32_begin.h"      // this unit's kernels run beside the CNN's chain kernels: no packed fp32 (common.h)
 #include "common.h"
+#include "uplift_net.h"
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -27,22 +28,13 @@
 #include <vector>
 
 using namespace ttup;
+using namespace ttup::upl;
 
 
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-// ------------------------------------------------------------------ packed linear layer
-struct Linear {
-    int n = 0, k = 0;            // out features, in features
-    float* w_dev = nullptr;      // MFMA path: [ntile][k/16][64 lanes][4]; small-K path: [n][k] row major
-    float* b_dev = nullptr;      // [n] or null
-    bool mfma = false;
-    // K = 128 layers (all of the 'large' model's transformer layers): the weights split into three bf16 parts, packed per
-    // v_mfma_f32_16x16x32_bf16 A fragment: [ntile][k/32][plane][64 lanes][8] (linear_x3_kernel)
-    uint16_t* w3_dev = nullptr;
-};
 
 // sum over the 16 lanes of a DPP row (every lane gets it): rotations by 8, 4, 2, 1 -- the same pairings, hence bit for bit the same
 // value, as the xor butterfly of __shfl_xor, without its four trips through the LDS crossbar
@@ -1299,10 +1291,6 @@ __global__ __launch_bounds__(512) void attn_block_x3_kernel(AttnBlockArgs a) {
 // LDS: split planes [3][64][128] bf16 (48 KB; the attention output aliases them) | q | k tile [64][260] fp32 (65 KB; the fp32
 // staging of the LayerNorms and of the MLP aliases it) | V transposed [4 heads][32][84] fp32 (42 KB: the P V operand of four keys
 // is one 16-byte read; a sequence's tokens start at a multiple of 4) | 16 floats per wave = 155.5 KB.
-struct StageLayerW {
-    const uint16_t *w_qkv, *w_proj, *w_fc1, *w_fc2;
-    const float *b_qkv, *g1, *b1, *g2, *b2, *bias1, *bias2;
-};
 constexpr int STAGE_MAX_LAYERS = 16;   // the layer table travels in the kernel arguments (scalar loads, pointers known to be global)
 struct StageArgs {
     float* x; long long n_seq; StageLayerW layers[STAGE_MAX_LAYERS]; int n_layers;
@@ -1824,59 +1812,22 @@ __global__ void rotationaxes_kernel(const float* rot, const float* pos, int B, i
     out[b * 3 + 2] = r[0] * 0.f + r[1] * 0.f + r[2] * 1.f;
 }
 
-struct Layer { Linear qkv, proj, fc1, fc2; float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr; };
-struct Mlp2 { Linear fc1, fc2; };
-struct Head { Linear fc1, fc2, fc3; };
-// the variant of get_model a blob holds (hdr[6], hdr[7]; include/ttup.h)
-enum { NAME_CONNECT = 0, NAME_MULTI = 1, NAME_SINGLE = 2 };
-enum { MODE_DYNAMIC = 0, MODE_STACKED = 1, MODE_ORIGINAL = 2, MODE_FREE = 3 };
 
 }  // namespace
 
-struct ttup_uplift {
-    int D = 0, heads = 0, hd = 0, n_table = 13, max_batch = 0, max_len = 0, chunk = 1;
-    int name = NAME_CONNECT, mode = MODE_DYNAMIC; bool rot_old = false;
-    float *embed_w1t = nullptr, *embed_b1 = nullptr, *embed_w2t = nullptr, *embed_b2 = nullptr;      // 'multistage': embed, weights transposed [K][D]
-    float *stacked_wt = nullptr, *stacked_b = nullptr;                                                // 'stacked' / 'originalmethod': ball_embed.fc1 transposed [K][D]
-    float2* rope_index = nullptr;          // time_rotation 'old': [max_len][hd/2], row = index of the token in its sequence
-    float* pos_rows = nullptr;             // 'singlestage': position head output on all T+1 rows
-    std::vector<Layer> pos_layers, layers, second;
-    Mlp2 ball_embed, table_embed;
-    Head position_head, rotation_head;
-    float* cls_dev = nullptr; float* inv_freq_dev = nullptr; float* table_times_dev = nullptr;
-    std::vector<StageLayerW> stage_pos, stage_first, stage_second;      // weight pointers of the three stages' layers (stage_x3_kernel); empty = not available
-    long long stage_launches = 0;
-    float2 *rope = nullptr, *table_rope = nullptr;      // (cos, sin) tables: [chunk*max_len][hd/2] per forward, [n_table][hd/2] fixed
-    std::vector<void*> allocs;
-    // scratch (sized for `chunk` trajectories of max_len tokens)
-    float *x = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *x2 = nullptr, *tok = nullptr, *ttok = nullptr, *h1 = nullptr;
-    float *m1 = nullptr, *m2 = nullptr, *tmask = nullptr, *txy = nullptr, *tmp_small = nullptr;
-    int* flags_dev = nullptr;
-    // Small batches (a rally or a handful of them: the hub surface, the pipeline's per-clip uplift) are launch-bound -- about
-    // eighty kernels of a few microseconds each.  Their forward is captured once per (batch, length) into a hipGraph that works
-    // on handle-owned input / output buffers and is replayed with one launch (+ six small copies around it).
-    struct GraphEntry { hipGraphExec_t exec = nullptr; int seen = 0; };
-    std::map<std::pair<int, int>, GraphEntry> graphs;
-    bool graphs_off = false;
-    float *g_ball = nullptr, *g_table = nullptr, *g_mask = nullptr, *g_times = nullptr, *g_rot = nullptr, *g_pos = nullptr;
-    long long graph_tokens = 0;          // largest batch * len served by a graph
-    long long graph_replays = 0;
-    ~ttup_uplift() {
-        for (auto& kv : graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-        for (void* p : allocs) if (p) (void)hipFree(p);
-    }
-};
 
 namespace {
 
 struct Reader {
     const char* p; size_t left;
+    std::vector<float>* keep = nullptr;          // when set, every record is also appended here (the plain fp32 copy, uplift_net.h)
     bool take(std::vector<float>* v, size_t expect) {
         int n;
         if (left < 4) return false;
         memcpy(&n, p, 4); p += 4; left -= 4;
         if ((size_t)n != expect || left < expect * 4) return false;
         v->resize(expect); memcpy(v->data(), p, expect * 4); p += expect * 4; left -= expect * 4;
+        if (keep) keep->insert(keep->end(), v->begin(), v->end());
         return true;
     }
 };
@@ -2349,6 +2300,8 @@ extern "C" int ttup_uplift_create(const void* blob, size_t blob_bytes, int max_b
         TTUP_REQUIRE(r.take(&v, net->hd / 2), TTUP_EFORMAT, "uplift blob: bad inv_freq record");
         if ((rc = dev_copy(net.get(), v, &net->inv_freq_dev))) return rc;
     }
+    std::vector<float> plain;
+    if (net->name == NAME_CONNECT && net->mode == MODE_DYNAMIC) r.keep = &plain;
     if ((rc = make_vec(net.get(), r, D, &net->cls_dev))) return rc;
     if (net->mode == MODE_STACKED || net->mode == MODE_ORIGINAL) {
         if ((rc = make_linear_t(net.get(), r, D, 2 + net->n_table * (net->mode == MODE_STACKED ? 3 : 2), &net->stacked_wt, &net->stacked_b))) return rc;
@@ -2366,6 +2319,10 @@ extern "C" int ttup_uplift_create(const void* blob, size_t blob_bytes, int max_b
     for (auto& L : net->second) if ((rc = make_layer(net.get(), r, &L))) return rc;
     if ((rc = make_head(net.get(), r, &net->rotation_head))) return rc;
     TTUP_REQUIRE(r.left == 0, TTUP_EFORMAT, "uplift blob: %zu trailing bytes", r.left);
+    if (r.keep) {
+        if ((rc = dev_copy(net.get(), plain, &net->plain))) return rc;
+        net->plain_floats = (long long)plain.size();
+    }
     make_stage(net.get(), net->pos_layers, &net->stage_pos);
     make_stage(net.get(), net->layers, &net->stage_first);
     make_stage(net.get(), net->second, &net->stage_second);

@@ -8,7 +8,7 @@
 // which is short of this detector's accuracy bar.
 //
 // Kernels
-//   gemm_kernel<AM>      C[m][n] = epilogue(sum_k A[m][k] W[n][k]), W row-major (nn.Linear layout).  64x64 block tile, BK = 32,
+//   gemm_kernel<AM>      (csrc/gemm_f32.h, shared with uplift_grad.hip)  C[m][n] = epilogue(sum_k A[m][k] W[n][k]), W row-major (nn.Linear layout).  64x64 block tile, BK = 32,
 //                        4 waves of 32x32 (2x2 MFMA tiles), A and W tiles through LDS (row stride 36 floats: the MFMA operand
 //                        reads -- 16 rows x 4 k per instruction -- hit 64 distinct banks).  A modes:
 //                          A_DENSE  row-major activations;
@@ -30,6 +30,7 @@
 #include "no_packed_fp32_begin.h"      // this unit runs beside the CNN's chain kernels: no packed fp32 (common.h)
 #include "common.h"
 #include "wasb_net.h"
+#include "gemm_f32.h"
 
 #include <cstring>
 #include <vector>
@@ -39,149 +40,9 @@
 namespace ttup {
 namespace vit {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace ttup::gemm;
 
 constexpr int DIM = 384, HEADS = 12, HD = 32, MLP = 1536, DEC = 256, DEPTH = 12;
-constexpr int BM = 64, BN = 64, BK = 32, LDS_STRIDE = BK + 4;
-
-enum { A_DENSE = 0, A_LN = 1, A_PATCH = 2, A_DECONV = 3, A_PATCH_FRAMES = 4 };
-enum { E_GELU = 1, E_RESID = 2, E_POS = 4, E_RELU = 8 };
-
-struct GemmArgs {
-    const float* a;          // A_DENSE / A_LN: (M, K) row-major; A_PATCH: NCHW input; A_DECONV: NHWC input; A_PATCH_FRAMES: (n, 3, H, W)
-    const float* w;          // (N, K)
-    const float* bias;       // (N)
-    const float* ln_g;       // A_LN: (K) gain, bias
-    const float* ln_b;
-    const float* stats;      // A_LN: (M, 2) mean, rstd
-    const float* res;        // E_RESID: (M, N), may alias out
-    const float* pos;        // E_POS: (N_tok + 1, N)
-    float* out;
-    int M, N, K;
-    int cin, ih, iw;         // A_PATCH: input channels and size; A_DECONV: input channels and (phase) grid h x w
-    int ntok;                // tokens per sample (E_POS)
-    int py, px;              // A_DECONV: output phase
-    int flags;
-};
-
-__device__ __forceinline__ float gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
-
-// Four consecutive k of row m of A (k multiple of 4).
-template <int AM>
-__device__ __forceinline__ f32x4 load_a4(const GemmArgs& p, int m, int k) {
-    f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    if (m >= p.M) return z;
-    if (AM == A_DENSE || AM == A_LN) {
-        f32x4 v = *(const f32x4*)(p.a + (size_t)m * p.K + k);
-        if (AM == A_LN) {
-            const float mu = p.stats[2 * m], rs = p.stats[2 * m + 1];
-            const f32x4 g = *(const f32x4*)(p.ln_g + k), b = *(const f32x4*)(p.ln_b + k);
-            v.x = (v.x - mu) * rs * g.x + b.x;
-            v.y = (v.y - mu) * rs * g.y + b.y;
-            v.z = (v.z - mu) * rs * g.z + b.z;
-            v.w = (v.w - mu) * rs * g.w + b.w;
-        }
-        return v;
-    } else if (AM == A_PATCH || AM == A_PATCH_FRAMES) {
-        const int hp = p.ih >> 4, wp = p.iw >> 4, per = hp * wp;
-        const int b = m / per, t = m - b * per, ty = t / wp, tx = t - ty * wp;
-        const int c = k >> 8, ky = (k >> 4) & 15, kx = k & 15;
-        // padding 2 (vit.py:222: 4 + 2 * (ratio // 2 - 1), ratio 1): a quad starts at x = 2 mod 4, so it is read as two float2,
-        // each wholly on one side of a border (x even, W even)
-        const int y = 16 * ty - 2 + ky, x = 16 * tx - 2 + kx;
-        if (y < 0 || y >= p.ih) return z;
-        const size_t plane = AM == A_PATCH ? (size_t)b * p.cin + c : (size_t)(b + c / 3) * 3 + c % 3;
-        const float* r = p.a + (plane * p.ih + y) * p.iw;
-        if (x >= 0 && x < p.iw) { const float2 u = *(const float2*)(r + x); z.x = u.x; z.y = u.y; }
-        if (x + 2 >= 0 && x + 2 < p.iw) { const float2 u = *(const float2*)(r + x + 2); z.z = u.x; z.w = u.y; }
-        return z;
-    } else {
-        const int per = p.ih * p.iw;
-        const int b = m / per, t = m - b * per, y = t / p.iw, x = t - y * p.iw;
-        const int tap = k / p.cin, c = k - tap * p.cin;
-        const int iy = y + p.py + (tap >> 1) - 1, ix = x + p.px + (tap & 1) - 1;
-        if (iy < 0 || iy >= p.ih || ix < 0 || ix >= p.iw) return z;
-        return *(const f32x4*)(p.a + (((size_t)b * p.ih + iy) * p.iw + ix) * p.cin + c);
-    }
-}
-
-template <int AM>
-__global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
-    __shared__ float sa[BM * LDS_STRIDE];
-    __shared__ float sw[BN * LDS_STRIDE];
-    const int tid = ttup_tid_x(), lane = tid & 63, wave = tid >> 6;
-    const int m0 = ttup_bid_x() * BM, n0 = ttup_bid_y() * BN;
-    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
-    const int lr = lane & 15, lg = lane >> 4;
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // tile loads: 64 rows x 8 quads per operand, two passes of 32 rows
-    const int lrow = tid >> 3, lq = (tid & 7) * 4;
-    f32x4 ra[2], rw[2];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            ra[h] = load_a4<AM>(p, m0 + lrow + 32 * h, k0 + lq);
-            rw[h] = *(const f32x4*)(p.w + (size_t)(n0 + lrow + 32 * h) * p.K + k0 + lq);
-        }
-    };
-    fetch(0);
-    for (int k0 = 0; k0 < p.K; k0 += BK) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            *(f32x4*)(sa + (lrow + 32 * h) * LDS_STRIDE + lq) = ra[h];
-            *(f32x4*)(sw + (lrow + 32 * h) * LDS_STRIDE + lq) = rw[h];
-        }
-        __syncthreads();
-        if (k0 + BK < p.K) fetch(k0 + BK);            // next tile in flight during this tile's MFMAs
-#pragma unroll
-        for (int s = 0; s < BK / 4; ++s) {
-            float av[2], wv[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) av[i] = sa[(wm + 16 * i + lr) * LDS_STRIDE + 4 * s + lg];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) wv[j] = sw[(wn + 16 * j + lr) * LDS_STRIDE + 4 * s + lg];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], wv[j], acc[i][j], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    // epilogue: lane holds C[wm + 16i + 4*lg + r][wn + 16j + lr]
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + wn + 16 * j + lr;
-        const float bn = p.bias[n];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + wm + 16 * i + 4 * lg + r;
-                if (m >= p.M) continue;
-                float v = acc[i][j][r] + bn;
-                if (p.flags & E_POS) {
-                    const int tok = m % p.ntok;
-                    v = v + p.pos[(size_t)(1 + tok) * p.N + n] + p.pos[n];
-                }
-                if (p.flags & E_GELU) v = gelu(v);
-                if (p.flags & E_RESID) v = p.res[(size_t)m * p.N + n] + v;
-                if (p.flags & E_RELU) v = fmaxf(v, 0.f);
-                size_t o;
-                if (AM == A_DECONV) {
-                    const int per = p.ih * p.iw, b = m / per, t = m - b * per, y = t / p.iw, x = t - y * p.iw;
-                    o = (((size_t)b * 2 * p.ih + 2 * y + p.py) * (2 * p.iw) + 2 * x + p.px) * p.N + n;
-                } else {
-                    o = (size_t)m * p.N + n;
-                }
-                p.out[o] = v;
-            }
-        }
-    }
-}
 
 // one wave per row of DIM floats -> (mean, 1/sqrt(var + eps)), eps 1e-6 (vit.py:274)
 __global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__ x, int M, float* __restrict__ stats) {

@@ -117,6 +117,21 @@ def ragged_uplift_batch(b, t, seed=0, pad=1):
     return ball, table, mask, times
 
 
+def uplift_targets(b, length, seed=0):
+    """Seeded training targets for an uplift batch of `b` trajectories of padded length `length`: r_world (b,length,3) ~ N(0,1) and
+    rotation (b,3) ~ 50 N(0,1), float32 (the gradient fixtures, tools/make_goldens_uplift_grad.py)."""
+    rng = np.random.default_rng(seed + 7919)
+    return rng.standard_normal((b, length, 3)).astype(np.float32), (50.0 * rng.standard_normal((b, 3))).astype(np.float32)
+
+
+def sample_indices(numel, count=256, seed=0):
+    """Up to `count` distinct positions in a tensor of `numel` entries, sorted: a multiplicative hash of 0..count-1 (no library RNG,
+    so the fixtures need not store them)."""
+    if numel <= count:
+        return np.arange(numel, dtype=np.int64)
+    return np.unique((np.arange(count, dtype=np.int64) * 2654435761 + 40503 * (seed + 1)) % numel)
+
+
 def vitpose_inputs(seed, b, c, h, w, amp=4.0, sigma=2.0, noise=0.5):
     """(b,c,h,w) float32 detector inputs in the normalised range (noise plus one bright Gaussian blob per sample, on every
     channel) and the (b,2) blob centres (x, y): seeded test inputs of the ViTPose fixtures (tools/make_goldens_vitpose.py)."""

@@ -9,6 +9,17 @@ import torch
 from . import _lib, arch, weights
 
 
+class Gradients(dict):
+    """Parameter name -> gradient view; `.flat` is the one device tensor they all view, `.rot` / `.pos` the forward outputs."""
+
+
+def _numel(shape):
+    n = 1
+    for s in shape:
+        n *= s
+    return n
+
+
 class MultiStageModel:
     """One native handle for any variant (the class keeps the name of the shipped default's reference class)."""
 
@@ -56,6 +67,52 @@ class MultiStageModel:
         return rot, pos
 
     __call__ = forward
+
+    def grad_layout(self):
+        """[(parameter name, shape, offset, used)] and the length of the flat gradient buffer `loss_and_grad` fills
+        (arch.uplift_grad_layout; checked against the library's own ttup_uplift_grad_layout)."""
+        arch.check_uplift_grad_variant(self.name, self.mode)
+        layout, n = arch.uplift_grad_layout(self.size)
+        nf, nt = ctypes.c_longlong(0), ctypes.c_int(0)
+        offs, used = (ctypes.c_longlong * len(layout))(), (ctypes.c_int * len(layout))()
+        _lib.check(self._lib.ttup_uplift_grad_layout(self._handle, ctypes.byref(nf), ctypes.byref(nt), offs, used, len(layout)))
+        if (nf.value, nt.value, list(offs), [bool(u) for u in used]) != (n, len(layout), [e[2] for e in layout], [e[3] for e in layout]):
+            raise RuntimeError('the library lays the gradient buffer out differently from arch.uplift_grad_layout')
+        return layout, n
+
+    def loss_and_grad(self, ball_pos, table_pos, mask, times, r_world, rotation, transform_mode='global'):
+        """The reference's training loss (uplifting/train.py:121-127) and `loss.backward()` for one batch.
+        ball (B,T,2), table (B,13,3), mask (B,T) in {0,1}, times (B,T), r_world (B,T,3), rotation (B,3) -- the rows `r_img, table_img,
+        mask, r_world, rotation, times` of a reference batch (train.py:116) or of dataset.TableTennisDataset.batch, passed by name.
+        transform_mode 'local' first takes the target spin through transform_rotationaxes(rotation, r_world) (train.py:123-124).
+        -> (loss_rot, loss_pos, grads): two 0-d device tensors and a dict from the reference's parameter names to views into one flat
+        device tensor (`grads.flat`; `grad_layout()` has the offsets).  `grads.rot` / `grads.pos` are the forward outputs.
+        Raises ValueError for any variant but connectstage/dynamic before the library is asked."""
+        arch.check_uplift_grad_variant(self.name, self.mode)
+        if transform_mode not in ('global', 'local'):
+            raise ValueError("transform_mode should be 'global' or 'local'")
+        args = [t.to(self.device, torch.float32).contiguous() for t in (ball_pos, table_pos, mask, times, r_world, rotation)]
+        ball, table, mask, times, r_world, rotation = args
+        b, t, _ = ball.shape
+        if table.shape != (b, 13, 3) or mask.shape != (b, t) or times.shape != (b, t) or r_world.shape != (b, t, 3) or rotation.shape != (b, 3):
+            raise ValueError('inconsistent input shapes')
+        if b == 0 or t == 0:
+            raise ValueError('empty batch: the uplift model needs at least one trajectory with one time step')
+        layout, n = self.grad_layout()
+        with torch.cuda.device(self.device):
+            nbytes = int(self._lib.ttup_uplift_grad_workspace_bytes(self._handle, b, t))
+            ws = torch.empty(((nbytes + 3) // 4,), dtype=torch.float32, device=self.device)
+            flat = torch.empty((n,), dtype=torch.float32, device=self.device)
+            loss = torch.empty((2,), dtype=torch.float32, device=self.device)
+            rot = torch.empty((b, 3), dtype=torch.float32, device=self.device)
+            pos = torch.empty((b, t, 3), dtype=torch.float32, device=self.device)
+            rc = self._lib.ttup_uplift_loss_grad(self._handle, _lib.ptr(ball), _lib.ptr(table), _lib.ptr(mask), _lib.ptr(times), _lib.ptr(r_world),
+                                                 _lib.ptr(rotation), b, t, 1 if transform_mode == 'local' else 0, _lib.ptr(ws), nbytes,
+                                                 _lib.ptr(flat), _lib.ptr(loss), _lib.ptr(rot), _lib.ptr(pos), _lib.stream_ptr())
+        _lib.check(rc)
+        grads = Gradients((k, flat[off:off + _numel(shape)].view(shape)) for k, shape, off, _ in layout)
+        grads.flat, grads.rot, grads.pos = flat, rot, pos
+        return loss[0], loss[1], grads
 
     def graph_info(self):
         """{'graphs', 'off', 'replays', 'stage_launches'}: the small-batch path (hipGraph replay of a captured forward; all layers
