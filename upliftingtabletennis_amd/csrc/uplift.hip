@@ -18,6 +18,8 @@
 #include "no_packed_fp32_begin.h"      // this unit's kernels run beside the CNN's chain kernels: no packed fp32 (common.h)
 #include "common.h"
 #include "uplift_net.h"
+#include "uplift_x3.h"
+#include "uplift_tokens.h"
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
@@ -33,20 +35,6 @@ using namespace ttup::upl;
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-
-// sum over the 16 lanes of a DPP row (every lane gets it): rotations by 8, 4, 2, 1 -- the same pairings, hence bit for bit the same
-// value, as the xor butterfly of __shfl_xor, without its four trips through the LDS crossbar
-__device__ __forceinline__ float row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xf, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x124, 0xf, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x122, 0xf, 0xf, false));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x121, 0xf, 0xf, false));
-    return v;
-}
-// workgroup barrier that orders LDS traffic only: global loads issued before it stay in flight (a __syncthreads() drains vmcnt too)
-__device__ __forceinline__ void stage_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 struct LinArgs {
     const float* x; int ldx;
     const float* w; const float* bias;
@@ -158,7 +146,7 @@ __global__ __launch_bounds__(256 * MH) void linear_kernel(LinArgs a) {
                 const int m = m0 + wm * 64 + mt * 16 + c;
                 if (m >= a.M) continue;
                 f32x4 v = acc[t][mt] + b4;
-                if (a.relu) v = f32x4{v[0] > 0.f ? v[0] : 0.f, v[1] > 0.f ? v[1] : 0.f, v[2] > 0.f ? v[2] : 0.f, v[3] > 0.f ? v[3] : 0.f};
+                if (a.relu) v = relu4(v);
                 if (a.res) v += *(const f32x4*)(a.res + (size_t)m * a.ldr + n);
                 *(f32x4*)(a.out + (size_t)m * a.ldo + n) = v;
             }
@@ -180,17 +168,12 @@ __global__ __launch_bounds__(256 * MH) void linear_kernel(LinArgs a) {
     }
 }
 
-// The same layer on the bf16 matrix pipe with SPLIT operands (the arithmetic of csrc/conv_x3.hip): every fp32 weight and every
+// The same layer on the bf16 matrix pipe with SPLIT operands (the arithmetic of csrc/conv_x3.hip; the shared pieces are in uplift_x3.h): every fp32 weight and every
 // (LayerNorm'd) activation is split exactly into three bf16 parts, a product is the sum of six exact partial products (smallest
 // first) accumulated in fp32 -- accurate to below one fp32 fma rounding, at 2.7x the peak rate of v_mfma_f32_16x16x4_f32.  K = 128
 // only (the transformer layers of the 'large' model: 98 % of the work); TTUP_F32_EXACT=1 keeps the fp32-MFMA kernel.
 // LDS image: three planes [64*MH tokens][128] bf16 (256-byte rows), the 16-byte chunk index XOR-swizzled with the token's low four
 // bits: the 16 lanes of a ds_read_b128 group (8 tokens of one k chunk, 8 of the next) fall on 16 different chunks.
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-__device__ __forceinline__ unsigned ux3_pack2(float a, float b) { return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2)); }
 
 template <bool LN, int NTW, int MH>
 __global__ __launch_bounds__(256 * MH) void linear_x3_kernel(LinArgs a, const uint16_t* __restrict__ w3) {
@@ -274,14 +257,13 @@ __global__ __launch_bounds__(256 * MH) void linear_x3_kernel(LinArgs a, const ui
         for (int t = 0; t < NTW; ++t)
 #pragma unroll
             for (int p = 0; p < 3; ++p) wn_[p][t] = nt_ok[t] ? *(const bf16x8*)(w3 + ((((size_t)nt_g[t] * KS + sn) * 3 + p) * 64 + lane) * 8) : zero8;
-        constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};
 #pragma unroll
         for (int j = 0; j < 6; ++j)
 #pragma unroll
             for (int t = 0; t < NTW; ++t)
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt)
-                    acc[t][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[PA[j]][t], xb[PB[j]][mt], acc[t][mt], 0, 0, 0);
+                    acc[t][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[x3::PA[j]][t], xb[x3::PB[j]][mt], acc[t][mt], 0, 0, 0);
 #pragma unroll
         for (int t = 0; t < NTW; ++t)
 #pragma unroll
@@ -299,7 +281,7 @@ __global__ __launch_bounds__(256 * MH) void linear_x3_kernel(LinArgs a, const ui
             const int m = m0 + wm * 64 + mt * 16 + c;
             if (m >= a.M) continue;
             f32x4 v = acc[t][mt] + b4;
-            if (a.relu) v = f32x4{v[0] > 0.f ? v[0] : 0.f, v[1] > 0.f ? v[1] : 0.f, v[2] > 0.f ? v[2] : 0.f, v[3] > 0.f ? v[3] : 0.f};
+            if (a.relu) v = relu4(v);
             if (a.res) v += *(const f32x4*)(a.res + (size_t)m * a.ldr + n);
             *(f32x4*)(a.out + (size_t)m * a.ldo + n) = v;
         }
@@ -321,28 +303,14 @@ template <int MH>
 __global__ __launch_bounds__(256 * MH) void mlp_block_x3_kernel(MlpArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint16_t xh[];      // [3][BM][128] split planes, then float s2[BM][132]
     constexpr int BM = 64 * MH, K = 128, PLANE = BM * K, KS = K / 32, NTW = 2;
+    static_assert(K == X3_K, "the uplift_x3.h blocks are written for 128-wide rows");
     float* s2 = (float*)(xh + 3 * PLANE);                              // [BM][128] fp32, 16-byte chunks XOR-swizzled with the row's low 4 bits
     // (512-byte rows alias on the banks: the swizzle spreads the 8 rows of a ds_write_b128 lane group over 8 chunks; 80 KB per
     // 64-token workgroup = two per CU, 160 KB per 128-token workgroup)
-    auto s2p = [&](int r, int n) __attribute__((always_inline)) { return s2 + r * K + ((((n >> 2) ^ (r & 15))) << 2); };
     const int tid = ttup_tid_x(), lane = tid & 63, wave = tid >> 6, wn = wave & 3, wm = wave >> 2;
     const long long m0 = (long long)ttup_bid_x() * BM;
     const int q = lane >> 4, c = lane & 15;
     const int grp = tid >> 4, l16 = tid & 15;
-    auto split_store = [&](int r, int chunk, const f32x4& lo, const f32x4& hi) __attribute__((always_inline)) {
-        u32x4 p0, p1, p2;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float x0 = j < 2 ? lo[2 * j] : hi[2 * (j - 2)], x1 = j < 2 ? lo[2 * j + 1] : hi[2 * (j - 2) + 1];
-            const unsigned q0 = ux3_pack2(x0, x1);
-            const float r0 = x0 - __uint_as_float(q0 << 16), r1 = x1 - __uint_as_float(q0 & 0xffff0000u);
-            const unsigned q1 = ux3_pack2(r0, r1);
-            const float s0 = r0 - __uint_as_float(q1 << 16), s1 = r1 - __uint_as_float(q1 & 0xffff0000u);
-            p0[j] = q0; p1[j] = q1; p2[j] = ux3_pack2(s0, s1);
-        }
-        uint16_t* d = xh + r * K + ((chunk ^ (r & 15)) << 3);
-        *(u32x4*)d = p0; *(u32x4*)(d + PLANE) = p1; *(u32x4*)(d + 2 * PLANE) = p2;
-    };
     auto gemm = [&](const uint16_t* __restrict__ w3, f32x4 (&acc)[NTW][4]) __attribute__((always_inline)) {
         const uint16_t* xw = xh + (wm * 64 + c) * K;
         bf16x8 wa[3][NTW];
@@ -363,14 +331,13 @@ __global__ __launch_bounds__(256 * MH) void mlp_block_x3_kernel(MlpArgs a) {
             for (int t = 0; t < NTW; ++t)
 #pragma unroll
                 for (int p = 0; p < 3; ++p) wn_[p][t] = *(const bf16x8*)(w3 + ((((size_t)(wn + 4 * t) * KS + sn) * 3 + p) * 64 + lane) * 8);
-            constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};
 #pragma unroll
             for (int j = 0; j < 6; ++j)
 #pragma unroll
                 for (int t = 0; t < NTW; ++t)
 #pragma unroll
                     for (int mt = 0; mt < 4; ++mt)
-                        acc[t][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[PA[j]][t], xb[PB[j]][mt], acc[t][mt], 0, 0, 0);
+                        acc[t][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[x3::PA[j]][t], xb[x3::PB[j]][mt], acc[t][mt], 0, 0, 0);
 #pragma unroll
             for (int t = 0; t < NTW; ++t)
 #pragma unroll
@@ -384,7 +351,7 @@ __global__ __launch_bounds__(256 * MH) void mlp_block_x3_kernel(MlpArgs a) {
         const long long m = m0 + r;
         const f32x4 z = {0.f, 0.f, 0.f, 0.f};
         const f32x4 lo = m < a.M ? *(const f32x4*)(a.att + m * K + 8 * l16) : z, hi = m < a.M ? *(const f32x4*)(a.att + m * K + 8 * l16 + 4) : z;
-        split_store(r, l16, lo, hi);
+        x3_split_store<PLANE>(xh, r, l16, lo, hi);
     }
     __syncthreads();
     // ---- 2. x2 = proj(att) + x   (kept in registers; a copy goes to LDS for the LayerNorm)
@@ -402,7 +369,7 @@ __global__ __launch_bounds__(256 * MH) void mlp_block_x3_kernel(MlpArgs a) {
             const int r = wm * 64 + mt * 16 + c;
             const long long m = m0 + r;
             if (m < a.M) x2[t][mt] += *(const f32x4*)(a.x + m * K + n);
-            *(f32x4*)s2p(r, n) = x2[t][mt];
+            *(f32x4*)x3_f32(s2, r, n) = x2[t][mt];
         }
     }
     __syncthreads();              // every wave is done reading the att planes; x2 rows are complete in s2
@@ -410,7 +377,7 @@ __global__ __launch_bounds__(256 * MH) void mlp_block_x3_kernel(MlpArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r = grp + i * 16 * MH;
-        f32x4 v[2] = {*(const f32x4*)s2p(r, 8 * l16), *(const f32x4*)s2p(r, 8 * l16 + 4)};
+        f32x4 v[2] = {*(const f32x4*)x3_f32(s2, r, 8 * l16), *(const f32x4*)x3_f32(s2, r, 8 * l16 + 4)};
         float sum = ((v[0][0] + v[0][1]) + (v[0][2] + v[0][3])) + ((v[1][0] + v[1][1]) + (v[1][2] + v[1][3]));
         sum = row16_sum(sum);
         const float mean = sum / (float)K;
@@ -427,7 +394,7 @@ __global__ __launch_bounds__(256 * MH) void mlp_block_x3_kernel(MlpArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[u][e] = (v[u][e] - mean) * rstd * g[e] + bt[e];
         }
-        split_store(r, l16, v[0], v[1]);
+        x3_split_store<PLANE>(xh, r, l16, v[0], v[1]);
     }
     __syncthreads();
     // ---- 4. hid = relu(fc1(LN(x2)) + b1) -> split planes (through s2: a lane holds 4 outputs of a token, a chunk is 8)
@@ -445,8 +412,8 @@ __global__ __launch_bounds__(256 * MH) void mlp_block_x3_kernel(MlpArgs a) {
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 f32x4 v = acc[t][mt] + b4;
-                v = f32x4{v[0] > 0.f ? v[0] : 0.f, v[1] > 0.f ? v[1] : 0.f, v[2] > 0.f ? v[2] : 0.f, v[3] > 0.f ? v[3] : 0.f};
-                *(f32x4*)s2p(wm * 64 + mt * 16 + c, n) = v;          // (s2's LayerNorm input has been consumed: barrier above)
+                v = relu4(v);
+                *(f32x4*)x3_f32(s2, wm * 64 + mt * 16 + c, n) = v;          // (s2's LayerNorm input has been consumed: barrier above)
             }
         }
     }
@@ -454,7 +421,7 @@ __global__ __launch_bounds__(256 * MH) void mlp_block_x3_kernel(MlpArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r = grp + i * 16 * MH;
-        split_store(r, l16, *(const f32x4*)s2p(r, 8 * l16), *(const f32x4*)s2p(r, 8 * l16 + 4));
+        x3_split_store<PLANE>(xh, r, l16, *(const f32x4*)x3_f32(s2, r, 8 * l16), *(const f32x4*)x3_f32(s2, r, 8 * l16 + 4));
     }
     __syncthreads();
     // ---- 5. x = fc2(hid) + b2 + x2
@@ -486,27 +453,13 @@ __global__ __launch_bounds__(256 * MH) void mlp_block_x3_kernel(MlpArgs a) {
 __global__ __launch_bounds__(512) void mlp_block8_x3_kernel(MlpArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint16_t xh[];      // [3][64][128] split planes | float s2[64][128] (swizzled)
     constexpr int BM = 64, K = 128, PLANE = BM * K, KS = K / 32;
+    static_assert(K == X3_K, "the uplift_x3.h blocks are written for 128-wide rows");
     float* s2 = (float*)(xh + 3 * PLANE);
-    auto swz = [&](float* b, int r, int n) __attribute__((always_inline)) { return b + r * K + ((((n >> 2) ^ (r & 15))) << 2) + (n & 3); };
     const int tid = ttup_tid_x(), lane = tid & 63, wave = tid >> 6;
     const long long m0 = (long long)ttup_bid_x() * BM;
     const int q = lane >> 4, c = lane & 15;
     const int grp = tid >> 4, l16 = tid & 15;
     const int n = wave * 16 + 4 * q;
-    auto split_store = [&](int r, int chunk, const f32x4& lo, const f32x4& hi) __attribute__((always_inline)) {
-        u32x4 p0, p1, p2;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float x0 = j < 2 ? lo[2 * j] : hi[2 * (j - 2)], x1 = j < 2 ? lo[2 * j + 1] : hi[2 * (j - 2) + 1];
-            const unsigned q0 = ux3_pack2(x0, x1);
-            const float r0 = x0 - __uint_as_float(q0 << 16), r1 = x1 - __uint_as_float(q0 & 0xffff0000u);
-            const unsigned q1 = ux3_pack2(r0, r1);
-            const float s0 = r0 - __uint_as_float(q1 << 16), s1 = r1 - __uint_as_float(q1 & 0xffff0000u);
-            p0[j] = q0; p1[j] = q1; p2[j] = ux3_pack2(s0, s1);
-        }
-        uint16_t* d = xh + r * K + ((chunk ^ (r & 15)) << 3);
-        *(u32x4*)d = p0; *(u32x4*)(d + PLANE) = p1; *(u32x4*)(d + 2 * PLANE) = p2;
-    };
     auto load_tile = [&](const uint16_t* __restrict__ w3, bf16x8 (&w)[3][KS]) __attribute__((always_inline)) {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -514,22 +467,6 @@ __global__ __launch_bounds__(512) void mlp_block8_x3_kernel(MlpArgs a) {
 #pragma unroll
             for (int p = 0; p < 3; ++p) w[p][s] = *(const bf16x8*)(w3 + ((((size_t)wave * KS + s) * 3 + p) * 64 + lane) * 8);
         __builtin_amdgcn_sched_barrier(0);
-    };
-    auto gemm = [&](const bf16x8 (&w)[3][KS], f32x4 (&acc)[4]) __attribute__((always_inline)) {
-        const uint16_t* xw = xh + c * K;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            bf16x8 xb[3][4];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int p = 0; p < 3; ++p) xb[p][mt] = *(const bf16x8*)(xw + p * PLANE + mt * 16 * K + (((4 * s + q) ^ c) << 3));
-            constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};
-#pragma unroll
-            for (int j = 0; j < 6; ++j)
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[PA[j]][s], xb[PB[j]][mt], acc[mt], 0, 0, 0);
-        }
     };
     // ---- small operands first (the memory counter retires in order), then the first weight tile, then the att rows
     f32x4 xr[4], lg[2], lb[2];
@@ -552,24 +489,21 @@ __global__ __launch_bounds__(512) void mlp_block8_x3_kernel(MlpArgs a) {
     bf16x8 wnext[3][KS];
     load_tile(a.w_proj, wnext);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) split_store(grp + 32 * i, l16, at[i][0], at[i][1]);
+    for (int i = 0; i < 2; ++i) x3_split_store<PLANE>(xh, grp + 32 * i, l16, at[i][0], at[i][1]);
     stage_barrier();
     // ---- x2 = proj(att) + x
     f32x4 x2[4];
     {
         bf16x8 wc[3][KS];
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) wc[p][s] = wnext[p][s];
+        x3_take(wc, wnext);
         load_tile(a.w_fc1, wnext);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) x2[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        gemm(wc, x2);
+        x3_gemm64<PLANE>(xh, c, q, wc, x2);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             x2[mt] += xr[mt];
-            *(f32x4*)swz(s2, mt * 16 + c, n) = x2[mt];
+            *(f32x4*)x3_f32(s2, mt * 16 + c, n) = x2[mt];
         }
     }
     stage_barrier();
@@ -577,7 +511,7 @@ __global__ __launch_bounds__(512) void mlp_block8_x3_kernel(MlpArgs a) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int r = grp + 32 * i;
-        f32x4 v[2] = {*(const f32x4*)swz(s2, r, 8 * l16), *(const f32x4*)swz(s2, r, 8 * l16 + 4)};
+        f32x4 v[2] = {*(const f32x4*)x3_f32(s2, r, 8 * l16), *(const f32x4*)x3_f32(s2, r, 8 * l16 + 4)};
         float sum = ((v[0][0] + v[0][1]) + (v[0][2] + v[0][3])) + ((v[1][0] + v[1][1]) + (v[1][2] + v[1][3]));
         sum = row16_sum(sum);
         const float mean = sum / (float)K;
@@ -592,33 +526,30 @@ __global__ __launch_bounds__(512) void mlp_block8_x3_kernel(MlpArgs a) {
         for (int u = 0; u < 2; ++u)
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[u][e] = (v[u][e] - mean) * rstd * lg[u][e] + lb[u][e];
-        split_store(r, l16, v[0], v[1]);
+        x3_split_store<PLANE>(xh, r, l16, v[0], v[1]);
     }
     stage_barrier();
     // ---- hid = relu(fc1(LN(x2)) + b1) -> s2 -> split planes
     {
         bf16x8 wc[3][KS];
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) wc[p][s] = wnext[p][s];
+        x3_take(wc, wnext);
         load_tile(a.w_fc2, wnext);
         f32x4 acc[4];
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        gemm(wc, acc);
+        x3_gemm64<PLANE>(xh, c, q, wc, acc);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             f32x4 v = acc[mt] + bias1;
-            v = f32x4{v[0] > 0.f ? v[0] : 0.f, v[1] > 0.f ? v[1] : 0.f, v[2] > 0.f ? v[2] : 0.f, v[3] > 0.f ? v[3] : 0.f};
-            *(f32x4*)swz(s2, mt * 16 + c, n) = v;
+            v = relu4(v);
+            *(f32x4*)x3_f32(s2, mt * 16 + c, n) = v;
         }
     }
     stage_barrier();
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int r = grp + 32 * i;
-        split_store(r, l16, *(const f32x4*)swz(s2, r, 8 * l16), *(const f32x4*)swz(s2, r, 8 * l16 + 4));
+        x3_split_store<PLANE>(xh, r, l16, *(const f32x4*)x3_f32(s2, r, 8 * l16), *(const f32x4*)x3_f32(s2, r, 8 * l16 + 4));
     }
     stage_barrier();
     // ---- x = fc2(hid) + b2 + x2
@@ -626,7 +557,7 @@ __global__ __launch_bounds__(512) void mlp_block8_x3_kernel(MlpArgs a) {
         f32x4 acc[4];
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        gemm(wnext, acc);
+        x3_gemm64<PLANE>(xh, c, q, wnext, acc);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
             const long long m = m0 + mt * 16 + c;
@@ -702,10 +633,7 @@ __global__ __launch_bounds__(512) void qkv_block8_x3_kernel(QkvArgs a) {
 #pragma unroll
     for (int jp = 0; jp < 3; ++jp) {
         bf16x8 wc[3][KS];
-#pragma unroll
-        for (int s = 0; s < KS; ++s)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) wc[p][s] = wnext[p][s];
+        x3_take(wc, wnext);
         const int nn = jp * K + wave * 16 + 4 * q;
         const f32x4 b4 = *(const f32x4*)(a.b_qkv + nn);
         if (jp < 2) load_tile((jp + 1) * 8 + wave, wnext);
@@ -719,11 +647,10 @@ __global__ __launch_bounds__(512) void qkv_block8_x3_kernel(QkvArgs a) {
             for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
                 for (int p = 0; p < 3; ++p) xb[p][mt] = *(const bf16x8*)(xw + p * PLANE + mt * 16 * K + (((4 * s + q) ^ c) << 3));
-            constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};
 #pragma unroll
             for (int j = 0; j < 6; ++j)
 #pragma unroll
-                for (int mt = 0; mt < 4; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wc[PA[j]][s], xb[PB[j]][mt], acc[mt], 0, 0, 0);
+                for (int mt = 0; mt < 4; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wc[x3::PA[j]][s], xb[x3::PB[j]][mt], acc[mt], 0, 0, 0);
         }
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) {
@@ -746,22 +673,11 @@ __global__ void small_linear_kernel(const float* x, int ldx, const float* w, con
 }
 
 // ------------------------------------------------------------------ attention
-// rope[r][i] = (cos, sin)(round(t_r / 0.002) * inv_freq[i]) for every time stamp r           (model.py:62-80)
-__global__ void rope_table_kernel(const float* times, const float* inv_freq, float2* rope, int half, long long total) {
-    const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
-    if (i >= total) return;
-    const float pos = rintf(times[i / half] / 0.002f);          // round(t / (1/MAX_FPS)), model.py:72
-    const float f = pos * inv_freq[i % half];
-    rope[i] = make_float2(cosf(f), sinf(f));
-}
-
 struct AttnArgs {
     const float* qkv;   // [n_seq*S][3D]
     float* out;         // [n_seq*S][D]
-    const float* mask;  // additive, row = seq / mask_div, S entries
-    const float2* rope; // (cos, sin) rows of hd/2; row of token j = (seq / times_div) * times_stride + j - num_cls
-    int n_seq, S, D, heads, hd, num_cls, mask_div, times_div, times_stride;
-    float scale;
+    int n_seq, D, heads, hd;
+    SeqView sv;
 };
 
 // P threads per (sequence, head); a workgroup of ttup_bdim_x() threads serves ttup_bdim_x() / P sequences.  K (rotated) and V
@@ -769,7 +685,7 @@ struct AttnArgs {
 template <int HD, int P>
 __global__ __launch_bounds__(128) void attention_kernel(AttnArgs a) {      // at most 128 threads are ever launched: 256 VGPRs, no spills
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int S = a.S, G = ttup_bdim_x() / P;
+    const int S = a.sv.S, G = ttup_bdim_x() / P;
     const int SEQ = 2 * S * HD + 16;                 // floats per sequence; the +16 words spreads the groups over LDS banks
     float* ms = sm + G * SEQ;                        // [G][S] additive mask
     const int h = ttup_bid_y(), tid = ttup_tid_x();
@@ -782,8 +698,8 @@ __global__ __launch_bounds__(128) void attention_kernel(AttnArgs a) {      // at
         const float* kp = a.qkv + ((size_t)seq * S + j) * D3 + a.D + h * HD + part * 4;
         f32x4 k = *(const f32x4*)kp;
         const f32x4 v = *(const f32x4*)(kp + a.D);
-        if (j >= a.num_cls) {
-            const f32x4 cs = *(const f32x4*)(a.rope + ((size_t)(seq / a.times_div) * a.times_stride + (j - a.num_cls)) * (HD / 2) + part * 2);
+        if (j >= a.sv.num_cls) {
+            const f32x4 cs = *(const f32x4*)(a.sv.rope + ((size_t)(seq / a.sv.times_div) * a.sv.times_stride + (j - a.sv.num_cls)) * (HD / 2) + part * 2);
             k = f32x4{k[0] * cs[0] - k[1] * cs[1], k[0] * cs[1] + k[1] * cs[0], k[2] * cs[2] - k[3] * cs[3], k[2] * cs[3] + k[3] * cs[2]};
         }
         *(f32x4*)(sm + g * SEQ + j * HD + part * 4) = k;
@@ -791,7 +707,7 @@ __global__ __launch_bounds__(128) void attention_kernel(AttnArgs a) {      // at
     }
     for (int u = tid; u < G * S; u += ttup_bdim_x()) {
         const int seq = ttup_bid_x() * G + u / S;
-        ms[u] = seq < a.n_seq ? a.mask[(size_t)(seq / a.mask_div) * S + (u % S)] : -INFINITY;
+        ms[u] = seq < a.n_seq ? a.sv.mask[(size_t)(seq / a.sv.mask_div) * S + (u % S)] : -INFINITY;
     }
     __syncthreads();
     const int g = tid / P, i0 = tid - g * P;
@@ -805,8 +721,8 @@ __global__ __launch_bounds__(128) void attention_kernel(AttnArgs a) {      // at
         const float* qp = a.qkv + ((size_t)seq * S + i) * D3 + h * HD;
 #pragma unroll
         for (int d = 0; d < HV; ++d) q[d] = *(const f32x4*)(qp + 4 * d);
-        if (i >= a.num_cls) {
-            const float2* rp = a.rope + ((size_t)(seq / a.times_div) * a.times_stride + (i - a.num_cls)) * (HD / 2);
+        if (i >= a.sv.num_cls) {
+            const float2* rp = a.sv.rope + ((size_t)(seq / a.sv.times_div) * a.sv.times_stride + (i - a.sv.num_cls)) * (HD / 2);
 #pragma unroll
             for (int d = 0; d < HV; ++d) {
                 const f32x4 cs = *(const f32x4*)(rp + 2 * d);
@@ -827,7 +743,7 @@ __global__ __launch_bounds__(128) void attention_kernel(AttnArgs a) {      // at
                     const f32x4 kk = *(const f32x4*)(ks + j * HD + 4 * d);
                     s = fmaf(q[d][0], kk[0], s); s = fmaf(q[d][1], kk[1], s); s = fmaf(q[d][2], kk[2], s); s = fmaf(q[d][3], kk[3], s);
                 }
-                s *= a.scale;
+                s *= a.sv.scale;
                 if (s > mx) {
                     const float corr = expf(mx - s);
                     den *= corr;
@@ -861,15 +777,13 @@ __global__ __launch_bounds__(128) void attention_kernel(AttnArgs a) {      // at
 // a second pass for p = exp(s - max) and  out += P V  (8 more MFMAs, key index permuted so that p is already the A operand).  The
 // normalisation 1 / den goes through 16 floats of LDS (out rows are indexed by 4q + r, den by the lane's own query).
 struct AttnMArgs {
-    const float* qkv; float* out; const float* mask; const float2* rope;
-    int n_seq, S, num_cls, mask_div, times_div, times_stride;
-    float scale;
+    const float* qkv; float* out; SeqView sv; int n_seq;
 };
 constexpr int ATTM_KS = 36;          // floats per K / V row in LDS (144 B: 16 consecutive rows fall on 16 different 16-byte slots)
 __global__ __launch_bounds__(256) void attention_mfma_kernel(AttnMArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];      // K [SP][36] | V [SP][36] | inv [4 waves][16]
     constexpr int HD = 32, D = 128, D3 = 384, KS = ATTM_KS;
-    const int S = a.S, KT = (S + 15) / 16, SP = KT * 16;
+    const int S = a.sv.S, KT = (S + 15) / 16, SP = KT * 16;
     float* sk = sm;
     float* sv = sm + SP * KS;
     float* sinv = sv + SP * KS;
@@ -877,8 +791,8 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(AttnMArgs a) {
     const int q = lane >> 4, c = lane & 15;
     const int h = ttup_bid_y(), seq = ttup_bid_z();
     const float* base = a.qkv + (size_t)seq * S * D3 + h * HD;
-    const float2* rbase = a.rope + (size_t)(seq / a.times_div) * a.times_stride * (HD / 2);
-    const float* mrow = a.mask + (size_t)(seq / a.mask_div) * S;
+    const float2* rbase = a.sv.rope + (size_t)(seq / a.sv.times_div) * a.sv.times_stride * (HD / 2);
+    const float* mrow = a.sv.mask + (size_t)(seq / a.sv.mask_div) * S;
     // ---- stage K (rotated) and V: 8 threads per row, one float4 each; rows past S are zero
     for (int u = tid; u < SP * 8; u += 256) {
         const int j = u >> 3, part = u & 7;
@@ -886,8 +800,8 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(AttnMArgs a) {
         if (j < S) {
             k = *(const f32x4*)(base + (size_t)j * D3 + D + part * 4);
             v = *(const f32x4*)(base + (size_t)j * D3 + 2 * D + part * 4);
-            if (j >= a.num_cls) {
-                const f32x4 cs = *(const f32x4*)(rbase + (size_t)(j - a.num_cls) * (HD / 2) + part * 2);
+            if (j >= a.sv.num_cls) {
+                const f32x4 cs = *(const f32x4*)(rbase + (size_t)(j - a.sv.num_cls) * (HD / 2) + part * 2);
                 k = f32x4{k[0] * cs[0] - k[1] * cs[1], k[0] * cs[1] + k[1] * cs[0], k[2] * cs[2] - k[3] * cs[3], k[2] * cs[3] + k[3] * cs[2]};
             }
         }
@@ -904,8 +818,8 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(AttnMArgs a) {
     if (i < S) {
         q0 = *(const f32x4*)(base + (size_t)i * D3 + 8 * q);
         q1 = *(const f32x4*)(base + (size_t)i * D3 + 8 * q + 4);
-        if (i >= a.num_cls) {
-            const float2* rp = rbase + (size_t)(i - a.num_cls) * (HD / 2) + 4 * q;
+        if (i >= a.sv.num_cls) {
+            const float2* rp = rbase + (size_t)(i - a.sv.num_cls) * (HD / 2) + 4 * q;
             const f32x4 c0 = *(const f32x4*)rp, c1 = *(const f32x4*)(rp + 2);
             q0 = f32x4{q0[0] * c0[0] - q0[1] * c0[1], q0[0] * c0[1] + q0[1] * c0[0], q0[2] * c0[2] - q0[3] * c0[3], q0[2] * c0[3] + q0[3] * c0[2]};
             q1 = f32x4{q1[0] * c1[0] - q1[1] * c1[1], q1[0] * c1[1] + q1[1] * c1[0], q1[2] * c1[2] - q1[3] * c1[3], q1[2] * c1[3] + q1[3] * c1[2]};
@@ -924,7 +838,7 @@ __global__ __launch_bounds__(256) void attention_mfma_kernel(AttnMArgs a) {
         for (int r = 0; r < 4; ++r) {
             const int j = kt * 16 + 4 * q + r;
             const bool col_ok = j < S && mrow[j < S ? j : 0] == 0.f;
-            sc[r] = col_ok ? sc[r] * a.scale : -INFINITY;
+            sc[r] = col_ok ? sc[r] * a.sv.scale : -INFINITY;
         }
         return sc;
     };
@@ -977,7 +891,7 @@ template <int NG>
 __global__ __launch_bounds__(256) void attention_mfma8_kernel(AttnMArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];      // K [SP][36] | V^T [32][SP + 4] | inv [4 waves][16]
     constexpr int HD = 32, D = 128, D3 = 384, KS = ATTM_KS, NK = NG * 4;
-    const int S = a.S, KT = (S + 15) / 16, SP = KT * 16, VS = SP + 4;
+    const int S = a.sv.S, KT = (S + 15) / 16, SP = KT * 16, VS = SP + 4;
     float* sk = sm;
     float* svt = sm + SP * KS;
     float* sinv = svt + HD * VS;
@@ -985,8 +899,8 @@ __global__ __launch_bounds__(256) void attention_mfma8_kernel(AttnMArgs a) {
     const int q = lane >> 4, c = lane & 15;
     const int h = ttup_bid_y(), seq = ttup_bid_z();
     const float* base = a.qkv + (size_t)seq * S * D3 + h * HD;
-    const float2* rbase = a.rope + (size_t)(seq / a.times_div) * a.times_stride * (HD / 2);
-    const float* mrow = a.mask + (size_t)(seq / a.mask_div) * S;
+    const float2* rbase = a.sv.rope + (size_t)(seq / a.sv.times_div) * a.sv.times_stride * (HD / 2);
+    const float* mrow = a.sv.mask + (size_t)(seq / a.sv.mask_div) * S;
     // ---- stage K (rotated) and V^T: 8 threads per token, one float4 of each per thread; tokens past S are zero
     for (int u = tid; u < SP * 8; u += 256) {
         const int j = u >> 3, part = u & 7;
@@ -994,8 +908,8 @@ __global__ __launch_bounds__(256) void attention_mfma8_kernel(AttnMArgs a) {
         if (j < S) {
             k = *(const f32x4*)(base + (size_t)j * D3 + D + part * 4);
             v = *(const f32x4*)(base + (size_t)j * D3 + 2 * D + part * 4);
-            if (j >= a.num_cls) {
-                const f32x4 cs = *(const f32x4*)(rbase + (size_t)(j - a.num_cls) * (HD / 2) + part * 2);
+            if (j >= a.sv.num_cls) {
+                const f32x4 cs = *(const f32x4*)(rbase + (size_t)(j - a.sv.num_cls) * (HD / 2) + part * 2);
                 k = f32x4{k[0] * cs[0] - k[1] * cs[1], k[0] * cs[1] + k[1] * cs[0], k[2] * cs[2] - k[3] * cs[3], k[2] * cs[3] + k[3] * cs[2]};
             }
         }
@@ -1015,8 +929,8 @@ __global__ __launch_bounds__(256) void attention_mfma8_kernel(AttnMArgs a) {
     if (i < S) {
         q0 = *(const f32x4*)(base + (size_t)i * D3 + 8 * q);
         q1 = *(const f32x4*)(base + (size_t)i * D3 + 8 * q + 4);
-        if (i >= a.num_cls) {
-            const float2* rp = rbase + (size_t)(i - a.num_cls) * (HD / 2) + 4 * q;
+        if (i >= a.sv.num_cls) {
+            const float2* rp = rbase + (size_t)(i - a.sv.num_cls) * (HD / 2) + 4 * q;
             const f32x4 c0 = *(const f32x4*)rp, c1 = *(const f32x4*)(rp + 2);
             q0 = f32x4{q0[0] * c0[0] - q0[1] * c0[1], q0[0] * c0[1] + q0[1] * c0[0], q0[2] * c0[2] - q0[3] * c0[3], q0[2] * c0[3] + q0[3] * c0[2]};
             q1 = f32x4{q1[0] * c1[0] - q1[1] * c1[1], q1[0] * c1[1] + q1[1] * c1[0], q1[2] * c1[2] - q1[3] * c1[3], q1[2] * c1[3] + q1[3] * c1[2]};
@@ -1051,7 +965,7 @@ __global__ __launch_bounds__(256) void attention_mfma8_kernel(AttnMArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const bool col_ok = kt < KT && (((kt < 4 ? lo_q : hi_q) >> ((kt & 3) * 16 + r)) & 1);
-            sc[kt][r] = col_ok ? sc[kt][r] * a.scale : -INFINITY;
+            sc[kt][r] = col_ok ? sc[kt][r] * a.sv.scale : -INFINITY;
             mx = sc[kt][r] > mx ? sc[kt][r] : mx;
         }
     { const float o = __shfl_xor(mx, 16, 64); mx = o > mx ? o : mx; }
@@ -1113,9 +1027,7 @@ __global__ __launch_bounds__(256) void attention_mfma8_kernel(AttnMArgs a) {
 struct AttnBlockArgs {
     const float* x; float* att; long long n_seq;
     const uint16_t* w_qkv; const float* b_qkv; const float* g1; const float* b1;
-    const float* mask; const float2* rope;
-    int S, num_cls, mask_div, times_div, times_stride;
-    float scale;
+    SeqView sv;
 };
 constexpr int ATTN_QS = 196;          // floats per row of the qkv tile: 2 heads x 96 + 4 (784 B = 49 slots of 16 B: consecutive rows fall on consecutive slots)
 __global__ __launch_bounds__(512) void attn_block_x3_kernel(AttnBlockArgs a) {
@@ -1124,7 +1036,7 @@ __global__ __launch_bounds__(512) void attn_block_x3_kernel(AttnBlockArgs a) {
     constexpr int BM = 64, K = 128, PLANE = BM * K, KS = K / 32, HD = 32, QS = ATTN_QS;
     float* qh = (float*)xh;
     const int tid = ttup_tid_x(), lane = tid & 63, wave = tid >> 6;
-    const int S = a.S, SEQS = BM / S, ROWS = SEQS * S;
+    const int S = a.sv.S, SEQS = BM / S, ROWS = SEQS * S;
     const long long seq0 = (long long)ttup_bid_x() * SEQS;
     const long long m0 = seq0 * S, M = a.n_seq * S;
     const int q = lane >> 4, c = lane & 15;
@@ -1181,8 +1093,8 @@ __global__ __launch_bounds__(512) void attn_block_x3_kernel(AttnBlockArgs a) {
     const int grow = mt * 16 + c;                            // the lane's token row in the tile
     const int gsl = grow / S, gjt = grow - gsl * S;
     const long long gseq = seq0 + gsl;
-    const bool rot = grow < ROWS && gseq < a.n_seq && gjt >= a.num_cls;
-    const float2* rrow = a.rope + ((size_t)((rot ? gseq : 0) / a.times_div) * a.times_stride + (rot ? gjt - a.num_cls : 0)) * (HD / 2);
+    const bool rot = grow < ROWS && gseq < a.n_seq && gjt >= a.sv.num_cls;
+    const float2* rrow = a.sv.rope + ((size_t)((rot ? gseq : 0) / a.sv.times_div) * a.sv.times_stride + (rot ? gjt - a.sv.num_cls : 0)) * (HD / 2);
     for (int rd = 0; rd < 2; ++rd) {                         // two heads per round: wave (m-tile w & 3, head 2 rd + (w >> 2))
         {
             const int h = 2 * rd + hp;
@@ -1197,13 +1109,12 @@ __global__ __launch_bounds__(512) void attn_block_x3_kernel(AttnBlockArgs a) {
 #pragma unroll
                         for (int p = 0; p < 3; ++p) wa[e][p][sK] = *(const bf16x8*)(a.w_qkv + ((((size_t)(nt0 + e) * KS + sK) * 3 + p) * 64 + lane) * 8);
                 f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-                constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};
 #pragma unroll
                 for (int sK = 0; sK < KS; ++sK)
 #pragma unroll
                     for (int jj = 0; jj < 6; ++jj)
 #pragma unroll
-                        for (int e = 0; e < 2; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[e][PA[jj]][sK], xb[PB[jj]][sK], acc[e], 0, 0, 0);
+                        for (int e = 0; e < 2; ++e) acc[e] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[e][x3::PA[jj]][sK], xb[x3::PB[jj]][sK], acc[e], 0, 0, 0);
 #pragma unroll
                 for (int e = 0; e < 2; ++e) {
                     f32x4 v = acc[e] + *(const f32x4*)(a.b_qkv + (nt0 + e) * 16 + 4 * q);
@@ -1222,7 +1133,7 @@ __global__ __launch_bounds__(512) void attn_block_x3_kernel(AttnBlockArgs a) {
         const long long seq = seq0 + sl;
         if (seq >= a.n_seq) continue;                        // wave-uniform
         const float* base = qh + (sl * S) * QS + (task & 1) * 96;
-        const float* mrow = a.mask + (size_t)(seq / a.mask_div) * S;
+        const float* mrow = a.sv.mask + (size_t)(seq / a.sv.mask_div) * S;
         // scores^T = K Q^T: A = K (row j = c, dims 8q .. 8q+7), B = Q (column i = c, the same dims); rows past the tile's last
         // sequence belong to nobody and are masked below
         const int jr = sl * S + c < BM ? c : 0;
@@ -1240,7 +1151,7 @@ __global__ __launch_bounds__(512) void attn_block_x3_kernel(AttnBlockArgs a) {
         for (int r = 0; r < 4; ++r) {
             const int j = 4 * q + r;
             const bool col_ok = j < S && mrow[j < S ? j : 0] == 0.f;
-            sc[r] = col_ok ? sc[r] * a.scale : -INFINITY;
+            sc[r] = col_ok ? sc[r] * a.sv.scale : -INFINITY;
             mx = sc[r] > mx ? sc[r] : mx;
         }
         { const float o = __shfl_xor(mx, 16, 64); mx = o > mx ? o : mx; }
@@ -1294,9 +1205,7 @@ __global__ __launch_bounds__(512) void attn_block_x3_kernel(AttnBlockArgs a) {
 constexpr int STAGE_MAX_LAYERS = 16;   // the layer table travels in the kernel arguments (scalar loads, pointers known to be global)
 struct StageArgs {
     float* x; long long n_seq; StageLayerW layers[STAGE_MAX_LAYERS]; int n_layers;
-    const float* mask; const float2* rope;
-    int S, num_cls, mask_div, times_div, times_stride;
-    float scale;
+    SeqView sv;
     // table stage without the assembled token tensor (model.py:374-378 and the gather after the stage): when `table_tok` is set, row 0
     // of sequence (b, t) is read from x[(b*T + t)] (the ball token), row 1 + n from table_tok[b*NT + n], and only row 0 is written back
     // -- to the same place.  14 of 15 token rows of the stage never exist in HBM.
@@ -1309,36 +1218,22 @@ constexpr size_t STAGE_LDS = (size_t)3 * 64 * 128 * 2 + (size_t)64 * STAGE_QS * 
 __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint16_t xh[];       // split planes
     constexpr int BM = 64, K = 128, PLANE = BM * K, KS = K / 32, HD = 32, QS = STAGE_QS, VS = STAGE_VS;
+    static_assert(K == X3_K, "the uplift_x3.h blocks are written for 128-wide rows");
     float* att = (float*)xh;                                          // attention output (fp32, swizzled), while the planes are dead
     float* qh = (float*)(xh + 3 * PLANE);                             // q | k of the four heads: [row][head][q|k][32]
     float* s2 = qh;                                                   // fp32 row staging (swizzled), while the q | k tile is dead
     float* vt = qh + BM * QS;                                         // V^T: [head][dim][sequence sl at column sl*S4 + token]
     float* sinv = vt + 4 * HD * VS;
-    auto swz = [&](float* b, int r, int n) __attribute__((always_inline)) { return b + r * K + ((((n >> 2) ^ (r & 15))) << 2) + (n & 3); };
     const int tid = ttup_tid_x(), lane = tid & 63, wave = tid >> 6;
-    const int S = a.S, SEQS = BM / S, ROWS = SEQS * S, QT = (S + 15) >> 4, S4 = (S + 3) & ~3;
+    const int S = a.sv.S, SEQS = BM / S, ROWS = SEQS * S, QT = (S + 15) >> 4, S4 = (S + 3) & ~3;
     const long long seq0 = (long long)ttup_bid_x() * SEQS;
     const long long m0 = seq0 * S, M = a.n_seq * S;
     const int q = lane >> 4, c = lane & 15;
     const int grp = tid >> 4, l16 = tid & 15;
     const int n = wave * 16 + 4 * q;                                  // the lane's four output features in every 128-wide GEMM
-    auto split_store = [&](int r, int chunk, const f32x4& lo, const f32x4& hi) __attribute__((always_inline)) {
-        u32x4 p0, p1, p2;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float x0 = j < 2 ? lo[2 * j] : hi[2 * (j - 2)], x1 = j < 2 ? lo[2 * j + 1] : hi[2 * (j - 2) + 1];
-            const unsigned q0 = ux3_pack2(x0, x1);
-            const float r0 = x0 - __uint_as_float(q0 << 16), r1 = x1 - __uint_as_float(q0 & 0xffff0000u);
-            const unsigned q1 = ux3_pack2(r0, r1);
-            const float s0 = r0 - __uint_as_float(q1 << 16), s1 = r1 - __uint_as_float(q1 & 0xffff0000u);
-            p0[j] = q0; p1[j] = q1; p2[j] = ux3_pack2(s0, s1);
-        }
-        uint16_t* d = xh + r * K + ((chunk ^ (r & 15)) << 3);
-        *(u32x4*)d = p0; *(u32x4*)(d + PLANE) = p1; *(u32x4*)(d + 2 * PLANE) = p2;
-    };
     // LayerNorm of row r of s2 (16 lanes per row, 8 features each) -> split planes
     auto ln_split = [&](int r, const f32x4 (&g)[2], const f32x4 (&bt)[2]) __attribute__((always_inline)) {
-        f32x4 v[2] = {*(const f32x4*)swz(s2, r, 8 * l16), *(const f32x4*)swz(s2, r, 8 * l16 + 4)};
+        f32x4 v[2] = {*(const f32x4*)x3_f32(s2, r, 8 * l16), *(const f32x4*)x3_f32(s2, r, 8 * l16 + 4)};
         float sum = ((v[0][0] + v[0][1]) + (v[0][2] + v[0][3])) + ((v[1][0] + v[1][1]) + (v[1][2] + v[1][3]));
         sum = row16_sum(sum);
         const float mean = sum / (float)K;
@@ -1353,7 +1248,7 @@ __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
         for (int u = 0; u < 2; ++u)
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[u][e] = (v[u][e] - mean) * rstd * g[u][e] + bt[u][e];
-        split_store(r, l16, v[0], v[1]);
+        x3_split_store<PLANE>(xh, r, l16, v[0], v[1]);
     };
     // one 16-output weight tile: 4 k-steps x 3 planes, 16 bytes per lane each
     // (the scheduling barriers pin the twelve requests where they are written: left alone, the scheduler sinks them to their
@@ -1367,22 +1262,6 @@ __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
         __builtin_amdgcn_sched_barrier(0);
     };
     // acc[mt] += W_tile . planes  (64 tokens x 16 outputs x 128 inputs, six partial products smallest first)
-    auto gemm = [&](const bf16x8 (&w)[3][KS], f32x4 (&acc)[4]) __attribute__((always_inline)) {
-        const uint16_t* xw = xh + c * K;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            bf16x8 xb[3][4];
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int p = 0; p < 3; ++p) xb[p][mt] = *(const bf16x8*)(xw + p * PLANE + mt * 16 * K + (((4 * s + q) ^ c) << 3));
-            constexpr int PA[6] = {0, 1, 2, 0, 1, 0}, PB[6] = {2, 1, 0, 1, 0, 0};
-#pragma unroll
-            for (int j = 0; j < 6; ++j)
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[PA[j]][s], xb[PB[j]][mt], acc[mt], 0, 0, 0);
-        }
-    };
     // ---- the tokens: global -> registers (row mt*16 + c, features n .. n+3)
     f32x4 xr[4];
     bool rot[4]; const float2* rrow[4]; int vcol[4];
@@ -1395,8 +1274,8 @@ __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
         const float* src = a.x + m * K;
         if (a.table_tok) src = jt == 0 ? a.x + sq * K : a.table_tok + ((sq < a.n_seq ? sq / a.T : 0) * a.NT + jt - 1) * K;
         xr[mt] = (r < ROWS && m < M) ? *(const f32x4*)(src + n) : f32x4{0.f, 0.f, 0.f, 0.f};
-        rot[mt] = r < ROWS && sq < a.n_seq && jt >= a.num_cls;
-        rrow[mt] = a.rope + ((size_t)((rot[mt] ? sq : 0) / a.times_div) * a.times_stride + (rot[mt] ? jt - a.num_cls : 0)) * (HD / 2);
+        rot[mt] = r < ROWS && sq < a.n_seq && jt >= a.sv.num_cls;
+        rrow[mt] = a.sv.rope + ((size_t)((rot[mt] ? sq : 0) / a.sv.times_div) * a.sv.times_stride + (rot[mt] ? jt - a.sv.num_cls : 0)) * (HD / 2);
         vcol[mt] = r < ROWS ? sl * S4 + jt : -1;             // the row's column in V^T (rows of no sequence are not stored)
     }
     for (int i = tid; i < 4 * HD * VS + 8 * 16; i += 512) vt[i] = 0.f;          // V^T and the normalisers: never-written columns must read as finite (0 x NaN)
@@ -1405,7 +1284,7 @@ __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
     {
         const int sl = lane / S, jt = lane - sl * S;
         const long long sq = seq0 + sl;
-        rowbits = __builtin_amdgcn_ballot_w64(lane < ROWS && sq < a.n_seq && a.mask[(size_t)((lane < ROWS && sq < a.n_seq ? sq : 0) / a.mask_div) * S + jt] == 0.f);
+        rowbits = __builtin_amdgcn_ballot_w64(lane < ROWS && sq < a.n_seq && a.sv.mask[(size_t)((lane < ROWS && sq < a.n_seq ? sq : 0) / a.sv.mask_div) * S + jt] == 0.f);
     }
     bf16x8 wnext[3][KS];
     if (a.n_layers > 0) load_tile(a.layers[0].w_qkv, wave, wnext);
@@ -1420,7 +1299,7 @@ __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) { lg[u] = *(const f32x4*)(L.g1 + 8 * l16 + 4 * u); lb[u] = *(const f32x4*)(L.b1 + 8 * l16 + 4 * u); }
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt) *(f32x4*)swz(s2, mt * 16 + c, n) = xr[mt];
+        for (int mt = 0; mt < 4; ++mt) *(f32x4*)x3_f32(s2, mt * 16 + c, n) = xr[mt];
         stage_barrier();
         ln_split(grp, lg, lb);
         ln_split(grp + 32, lg, lb);
@@ -1430,10 +1309,7 @@ __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
 #pragma unroll
         for (int jp = 0; jp < 3; ++jp) {
             bf16x8 wc[3][KS];
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-#pragma unroll
-                for (int p = 0; p < 3; ++p) wc[p][s] = wnext[p][s];
+            x3_take(wc, wnext);
             const f32x4 b4 = *(const f32x4*)(L.b_qkv + jp * K + n);
             f32x4 cs4[4];
             if (jp < 2) {
@@ -1444,7 +1320,7 @@ __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
             f32x4 acc[4];
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            gemm(wc, acc);
+            x3_gemm64<PLANE>(xh, c, q, wc, acc);
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 f32x4 v = acc[mt] + b4;
@@ -1507,7 +1383,7 @@ __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const bool col_ok = (colbits >> (kt * 16 + r)) & 1;
-                        sc[kt][r] = col_ok ? sc[kt][r] * a.scale : -INFINITY;
+                        sc[kt][r] = col_ok ? sc[kt][r] * a.sv.scale : -INFINITY;
                         mx = sc[kt][r] > mx ? sc[kt][r] : mx;
                     }
                 { const float o = __shfl_xor(mx, 16, 64); mx = o > mx ? o : mx; }
@@ -1542,8 +1418,8 @@ __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
                 const int io = qt * 16 + 4 * q + r;
                 if (io >= S) continue;
                 const float inv = sinv[wave * 16 + 4 * q + r];
-                *swz(att, sl * S + io, h * HD + c) = o0[r] * inv;
-                *swz(att, sl * S + io, h * HD + 16 + c) = o1[r] * inv;
+                *x3_f32(att, sl * S + io, h * HD + c) = o0[r] * inv;
+                *x3_f32(att, sl * S + io, h * HD + 16 + c) = o1[r] * inv;
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -1554,10 +1430,10 @@ __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
         {
             f32x4 t[2][2];
 #pragma unroll
-            for (int i = 0; i < 2; ++i) { t[i][0] = *(const f32x4*)swz(att, grp + 32 * i, 8 * l16); t[i][1] = *(const f32x4*)swz(att, grp + 32 * i, 8 * l16 + 4); }
+            for (int i = 0; i < 2; ++i) { t[i][0] = *(const f32x4*)x3_f32(att, grp + 32 * i, 8 * l16); t[i][1] = *(const f32x4*)x3_f32(att, grp + 32 * i, 8 * l16 + 4); }
             stage_barrier();
 #pragma unroll
-            for (int i = 0; i < 2; ++i) split_store(grp + 32 * i, l16, t[i][0], t[i][1]);
+            for (int i = 0; i < 2; ++i) x3_split_store<PLANE>(xh, grp + 32 * i, l16, t[i][0], t[i][1]);
         }
         stage_barrier();
         stamp(6);
@@ -1565,20 +1441,17 @@ __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
         f32x4 x2[4];
         {
             bf16x8 wc[3][KS];
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-#pragma unroll
-                for (int p = 0; p < 3; ++p) wc[p][s] = wnext[p][s];
+            x3_take(wc, wnext);
 #pragma unroll
             for (int u = 0; u < 2; ++u) { lg[u] = *(const f32x4*)(L.g2 + 8 * l16 + 4 * u); lb[u] = *(const f32x4*)(L.b2 + 8 * l16 + 4 * u); }
             load_tile(L.w_fc1, wave, wnext);
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) x2[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            gemm(wc, x2);
+            x3_gemm64<PLANE>(xh, c, q, wc, x2);
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 x2[mt] += xr[mt];
-                *(f32x4*)swz(s2, mt * 16 + c, n) = x2[mt];
+                *(f32x4*)x3_f32(s2, mt * 16 + c, n) = x2[mt];
             }
         }
         stage_barrier();
@@ -1590,44 +1463,38 @@ __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
         // ---- 6. hid = relu(fc1(LN(x2)) + b1) -> s2 -> split planes
         {
             bf16x8 wc[3][KS];
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-#pragma unroll
-                for (int p = 0; p < 3; ++p) wc[p][s] = wnext[p][s];
+            x3_take(wc, wnext);
             const f32x4 b4 = *(const f32x4*)(L.bias1 + n);
             load_tile(L.w_fc2, wave, wnext);
             f32x4 acc[4];
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            gemm(wc, acc);
+            x3_gemm64<PLANE>(xh, c, q, wc, acc);
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 f32x4 v = acc[mt] + b4;
-                v = f32x4{v[0] > 0.f ? v[0] : 0.f, v[1] > 0.f ? v[1] : 0.f, v[2] > 0.f ? v[2] : 0.f, v[3] > 0.f ? v[3] : 0.f};
-                *(f32x4*)swz(s2, mt * 16 + c, n) = v;
+                v = relu4(v);
+                *(f32x4*)x3_f32(s2, mt * 16 + c, n) = v;
             }
         }
         stage_barrier();
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int r = grp + 32 * i;
-            split_store(r, l16, *(const f32x4*)swz(s2, r, 8 * l16), *(const f32x4*)swz(s2, r, 8 * l16 + 4));
+            x3_split_store<PLANE>(xh, r, l16, *(const f32x4*)x3_f32(s2, r, 8 * l16), *(const f32x4*)x3_f32(s2, r, 8 * l16 + 4));
         }
         stage_barrier();
         stamp(9);
         // ---- 7. x = fc2(hid) + b2 + x2
         {
             bf16x8 wc[3][KS];
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-#pragma unroll
-                for (int p = 0; p < 3; ++p) wc[p][s] = wnext[p][s];
+            x3_take(wc, wnext);
             const f32x4 b4 = *(const f32x4*)(L.bias2 + n);
             if (li + 1 < a.n_layers) load_tile(a.layers[li + 1].w_qkv, wave, wnext);
             f32x4 acc[4];
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            gemm(wc, acc);
+            x3_gemm64<PLANE>(xh, c, q, wc, acc);
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) xr[mt] = (acc[mt] + b4) + x2[mt];
         }
@@ -1650,32 +1517,6 @@ __global__ __launch_bounds__(512) void stage_x3_kernel(StageArgs a) {
 }
 
 // ------------------------------------------------------------------ token assembly helpers
-// x[(b,t), 0] = ball_tok[b,t]; x[(b,t), 1+n] = table_tok[b,n]      (model.py:374-378)
-__global__ void assemble_table_kernel(const float* ball_tok, const float* table_tok, float* x, int T, int NT, int D, long long total) {
-    const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
-    if (i >= total) return;
-    const int d = (int)(i % D);
-    long long r = i / D;
-    const int n = (int)(r % (NT + 1)); r /= (NT + 1);      // r = b*T + t
-    x[i] = n == 0 ? ball_tok[r * D + d] : table_tok[((r / T) * NT + (n - 1)) * D + d];
-}
-// y[r] = x[r*stride_tok] rows (token 0 of every sequence)            (model.py:383-384)
-__global__ void gather_rows_kernel(const float* x, float* y, int D, int seq_tokens, long long total) {
-    const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
-    if (i >= total) return;
-    const int d = (int)(i % D);
-    const long long r = i / D;
-    y[i] = x[(r * seq_tokens) * D + d];
-}
-// y[b, 0] = cls; y[b, 1+t] = x[b, t]                                 (model.py:560)
-__global__ void prepend_cls_kernel(const float* x, const float* cls, float* y, int T, int D, long long total) {
-    const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
-    if (i >= total) return;
-    const int d = (int)(i % D);
-    long long r = i / D;
-    const int t = (int)(r % (T + 1)); const long long b = r / (T + 1);
-    y[i] = t == 0 ? cls[d] : x[(b * T + (t - 1)) * D + d];
-}
 // y[b, t] = x[b, 1+t] on rows of 3 floats: the position head of 'singlestage' runs over all T+1 rows of every sequence (model.py:495-497)
 __global__ void strip_cls3_kernel(const float* x, float* y, int T, long long total) {
     const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
@@ -1773,50 +1614,32 @@ __global__ __launch_bounds__(256) void embed3_cls_kernel(const float* __restrict
             for (int n = tid; n < D; n += 256) x[(r / T) * (T + 1) * D + n] = cls[n];
     }
 }
-// masks: mask (B,T) {0,1} -> additive m1 (B,T), m2 (B,T+1) with leading 0; table (B,13,3) -> tmask (B,14), txy (B*13,2)
-__global__ void prepare_kernel(const float* mask, const float* table, float* m1, float* m2, float* tmask, float* txy, int B, int T, int NT, int* flags) {
-    const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
-    const long long nmask = (long long)B * T, ntab = (long long)B * NT;
-    int fl = 0;
-    if (i < nmask) {
-        const float m = mask[i];
-        const float add = m == 0.f ? -INFINITY : 0.f;
-        m1[i] = add;
-        const long long b = i / T; const int t = (int)(i % T);
-        m2[b * (T + 1) + 1 + t] = add;
-        if (t == 0) m2[b * (T + 1)] = 0.f;
-        // bit0: some m==0, bit1: some m==1, bit2: some m<0, bit3: some m>1  (min==0 && max==1  <=>  flags==3)
-        fl = m == 0.f ? 1 : m == 1.f ? 2 : m < 0.f ? 4 : 8;
-    } else if (i < nmask + ntab) {
-        const long long j = i - nmask;
-        const long long b = j / NT; const int n = (int)(j % NT);
-        tmask[b * (NT + 1) + 1 + n] = table[j * 3 + 2] == 1.f ? 0.f : -INFINITY;      // KEYPOINT_VISIBLE == 1, model.py:363
-        if (n == 0) tmask[b * (NT + 1)] = 0.f;
-        txy[j * 2] = table[j * 3]; txy[j * 2 + 1] = table[j * 3 + 1];
-    }
-    // one atomic per wave (every thread used to hit the one flag word: 1.4 ms per call at B = 10 000)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) fl |= __shfl_xor(fl, off, 64);
-    if ((ttup_tid_x() & 63) == 0 && fl) atomicOr(flags, fl);
-}
-__global__ void rotationaxes_kernel(const float* rot, const float* pos, int B, int T, float* out) {
-    const int b = ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
-    if (b >= B) return;
-    const float* p = pos + (size_t)b * T * 3;
-    const float vx = p[3] - p[0], vy = p[4] - p[1];
-    const float nrm = sqrtf(vx * vx + vy * vy);
-    const float ex = vx / nrm, ey = vy / nrm;            // e_x = (ex, ey, 0); e_y = e_z x e_x = (-ey, ex, 0)
-    const float* r = rot + (size_t)b * 3;
-    out[b * 3 + 0] = r[0] * ex + r[1] * ey + r[2] * 0.f;
-    out[b * 3 + 1] = r[0] * (-ey) + r[1] * ex + r[2] * 0.f;
-    out[b * 3 + 2] = r[0] * 0.f + r[1] * 0.f + r[2] * 1.f;
-}
 
 
 }  // namespace
 
 
 namespace {
+
+// The environment switches (README, "knobs"), all read together, once per process, on the first use of any of them.  env_set() and
+// env_ll() are the only places that ask the environment: TTUP_UPLIFT_NO_GRAPH is sampled through env_set() at every handle
+// creation, TTUP_DEBUG where its message is printed.
+bool env_set(const char* name) { return getenv(name) != nullptr; }
+long long env_ll(const char* name, long long unset) { const char* v = getenv(name); return v ? atoll(v) : unset; }
+struct Switches {
+    bool f32_exact = env_set("TTUP_F32_EXACT");                          // fp32-MFMA kernels throughout, scalar attention
+    bool unfused = env_set("TTUP_UPLIFT_UNFUSED");                       // one launch per linear layer
+    bool scalar_attention = env_set("TTUP_UPLIFT_SCALAR_ATTENTION");
+    bool attention_2pass = env_set("TTUP_UPLIFT_ATTENTION_2PASS");       // the first matrix-pipe form (cross-check)
+    bool qkv_linear = env_set("TTUP_UPLIFT_QKV_LINEAR");                 // the general linear kernel instead of qkv_block8_x3_kernel (cross-check)
+    bool mlp_4waves = env_set("TTUP_UPLIFT_MLP_4WAVES");                 // mlp_block_x3_kernel: 4 waves, two n-tiles each
+    bool no_stage = env_set("TTUP_UPLIFT_NO_STAGE");
+    bool assemble = env_set("TTUP_UPLIFT_ASSEMBLE");                     // build the table stage's token tensor in memory
+    bool stacked_per_token = env_set("TTUP_UPLIFT_STACKED_PER_TOKEN");   // the other summation order (cross-check)
+    bool stage_stamps = env_set("TTUP_STAGE_STAMPS");
+    long long stage_wg = env_ll("TTUP_UPLIFT_STAGE_WG", 1ll << 40);         // largest launch (workgroups) stage_x3_kernel is used for
+};
+const Switches& switches() { static const Switches s; return s; }
 
 struct Reader {
     const char* p; size_t left;
@@ -1937,6 +1760,29 @@ int make_head(ttup_uplift* net, Reader& r, Head* h) {
     return make_linear(net, r, 3, D / 4, true, &h->fc3);
 }
 
+// linear_x3_kernel (X3) or linear_kernel <LN, NTW, MH> for the run-time choice of (LayerNorm, n-tiles per wave, 128-row tile)
+template <bool X3, bool LN, int NTW, int MH>
+int launch_linear_as(dim3 grid, size_t smem, hipStream_t st, const LinArgs& a, const uint16_t* w3) {
+    if constexpr (X3) {
+        if (int rc = ensure_max_lds((const void*)linear_x3_kernel<LN, NTW, MH>, 160 * 1024)) return rc;
+        hipLaunchKernelGGL((linear_x3_kernel<LN, NTW, MH>), grid, dim3(256 * MH), smem, st, a, w3);
+    } else {
+        if (int rc = ensure_max_lds((const void*)linear_kernel<LN, NTW, MH>, 160 * 1024)) return rc;
+        hipLaunchKernelGGL((linear_kernel<LN, NTW, MH>), grid, dim3(256 * MH), smem, st, a);
+    }
+    return TTUP_OK;
+}
+template <bool X3, bool LN, int MH>
+int launch_linear_n(int ntw, dim3 grid, size_t smem, hipStream_t st, const LinArgs& a, const uint16_t* w3) {
+    return ntw == 3 ? launch_linear_as<X3, LN, 3, MH>(grid, smem, st, a, w3) : ntw == 2 ? launch_linear_as<X3, LN, 2, MH>(grid, smem, st, a, w3)
+                                                                                      : launch_linear_as<X3, LN, 1, MH>(grid, smem, st, a, w3);
+}
+template <bool X3>
+int launch_linear(bool ln, bool big, int ntw, dim3 grid, size_t smem, hipStream_t st, const LinArgs& a, const uint16_t* w3) {
+    if (ln) return big ? launch_linear_n<X3, true, 2>(ntw, grid, smem, st, a, w3) : launch_linear_n<X3, true, 1>(ntw, grid, smem, st, a, w3);
+    return big ? launch_linear_n<X3, false, 2>(ntw, grid, smem, st, a, w3) : launch_linear_n<X3, false, 1>(ntw, grid, smem, st, a, w3);
+}
+
 int run_linear(const Linear& L, const float* x, int ldx, long long M, const float* gamma, const float* beta, int relu,
                const float* res, int ldr, float* out, int ldo, hipStream_t st) {
     if (M == 0) return TTUP_OK;
@@ -1956,50 +1802,18 @@ int run_linear(const Linear& L, const float* x, int ldx, long long M, const floa
     const int ntw = L.n > 128 ? 3 : L.n > 64 ? 2 : 1;
     const int bm = big ? 128 : 64;
     const dim3 grid((unsigned)((M + bm - 1) / bm), (unsigned)((L.n + 64 * ntw - 1) / (64 * ntw)));
-    static const bool exact = getenv("TTUP_F32_EXACT") != nullptr;
-    if (L.w3_dev && !exact && ldo % 4 == 0 && (!res || ldr % 4 == 0)) {
-        const size_t smem3 = (size_t)3 * bm * 128 * sizeof(uint16_t);
-#define TTUP_LIN3(LN_, NTW_, MH_)                                                                                             \
-    do {                                                                                                                      \
-        if (int rc_ = ensure_max_lds((const void*)linear_x3_kernel<LN_, NTW_, MH_>, 160 * 1024)) return rc_;                  \
-        hipLaunchKernelGGL((linear_x3_kernel<LN_, NTW_, MH_>), grid, dim3(256 * MH_), smem3, st, a, (const uint16_t*)L.w3_dev); \
-    } while (0)
-#define TTUP_LIN3_N(LN_, MH_)                                         \
-    do {                                                              \
-        if (ntw == 3) TTUP_LIN3(LN_, 3, MH_);                         \
-        else if (ntw == 2) TTUP_LIN3(LN_, 2, MH_);                    \
-        else TTUP_LIN3(LN_, 1, MH_);                                  \
-    } while (0)
-        if (gamma) { if (big) TTUP_LIN3_N(true, 2); else TTUP_LIN3_N(true, 1); }
-        else { if (big) TTUP_LIN3_N(false, 2); else TTUP_LIN3_N(false, 1); }
-#undef TTUP_LIN3_N
-#undef TTUP_LIN3
-        TTUP_LAUNCH_CHECK();
-        return TTUP_OK;
-    }
-    const size_t smem = (size_t)4 * bm * (L.k / 4 + 4) * sizeof(float);
-#define TTUP_LIN(LN_, NTW_, MH_)                                                                                              \
-    do {                                                                                                                      \
-        if (int rc_ = ensure_max_lds((const void*)linear_kernel<LN_, NTW_, MH_>, 160 * 1024)) return rc_;                     \
-        hipLaunchKernelGGL((linear_kernel<LN_, NTW_, MH_>), grid, dim3(256 * MH_), smem, st, a);                              \
-    } while (0)
-#define TTUP_LIN_N(LN_, MH_)                                          \
-    do {                                                              \
-        if (ntw == 3) TTUP_LIN(LN_, 3, MH_);                          \
-        else if (ntw == 2) TTUP_LIN(LN_, 2, MH_);                     \
-        else TTUP_LIN(LN_, 1, MH_);                                   \
-    } while (0)
-    if (gamma) { if (big) TTUP_LIN_N(true, 2); else TTUP_LIN_N(true, 1); }
-    else { if (big) TTUP_LIN_N(false, 2); else TTUP_LIN_N(false, 1); }
-#undef TTUP_LIN_N
-#undef TTUP_LIN
+    const bool x3 = L.w3_dev && !switches().f32_exact && ldo % 4 == 0 && (!res || ldr % 4 == 0);
+    const size_t smem = x3 ? (size_t)3 * bm * 128 * sizeof(uint16_t) : (size_t)4 * bm * (L.k / 4 + 4) * sizeof(float);
+    const int rc = x3 ? launch_linear<true>(gamma != nullptr, big, ntw, grid, smem, st, a, L.w3_dev)
+                      : launch_linear<false>(gamma != nullptr, big, ntw, grid, smem, st, a, nullptr);
+    if (rc) return rc;
     TTUP_LAUNCH_CHECK();
     return TTUP_OK;
 }
 
 template <int HD>
 void launch_attention(const AttnArgs& a, hipStream_t st) {
-    const int S = a.S;
+    const int S = a.sv.S;
     const int P = S <= 16 ? 16 : S <= 32 ? 32 : S <= 64 ? 64 : 128;
     const int threads = P == 128 ? 128 : 64, G = threads / P;
     const size_t smem = ((size_t)G * (2 * S * HD + 16) + (size_t)G * S) * sizeof(float);
@@ -2012,21 +1826,15 @@ void launch_attention(const AttnArgs& a, hipStream_t st) {
     }
 }
 
-int run_attention(ttup_uplift* net, const float* qkv, float* out, int n_seq, int S, int num_cls, const float* mask, int mask_div,
-                  const float2* rope, int times_div, int times_stride, hipStream_t st) {
-    AttnArgs a;
-    a.qkv = qkv; a.out = out; a.mask = mask; a.rope = rope;
-    a.n_seq = n_seq; a.S = S; a.D = net->D; a.heads = net->heads; a.hd = net->hd; a.num_cls = num_cls;
-    a.mask_div = mask_div; a.times_div = times_div; a.times_stride = times_stride;
-    a.scale = 1.0f / sqrtf((float)net->hd);
-    static const bool scalar_attn = getenv("TTUP_UPLIFT_SCALAR_ATTENTION") != nullptr || getenv("TTUP_F32_EXACT") != nullptr;
+int run_attention(ttup_uplift* net, const float* qkv, float* out, int n_seq, const SeqView& sv, hipStream_t st) {
+    const int S = sv.S;
+    const AttnArgs a{qkv, out, n_seq, net->D, net->heads, net->hd, sv};
+    const Switches& sw = switches();
+    const bool scalar_attn = sw.scalar_attention || sw.f32_exact;
     if (net->hd == 32 && net->D == 128 && S > 16 && S <= 512 && !scalar_attn) {
-        AttnMArgs m;
-        m.qkv = qkv; m.out = out; m.mask = mask; m.rope = rope; m.n_seq = n_seq; m.S = S; m.num_cls = num_cls;
-        m.mask_div = mask_div; m.times_div = times_div; m.times_stride = times_stride; m.scale = a.scale;
+        const AttnMArgs m{qkv, out, sv, n_seq};
         const int KT = (S + 15) / 16;
-        static const bool two_pass = getenv("TTUP_UPLIFT_ATTENTION_2PASS") != nullptr;          // the first matrix-pipe form (cross-check)
-        if (KT <= 8 && !two_pass) {
+        if (KT <= 8 && !sw.attention_2pass) {
             const size_t smem8 = ((size_t)KT * 16 * ATTM_KS + (size_t)32 * (KT * 16 + 4) + 64) * sizeof(float);
             if (KT <= 4) hipLaunchKernelGGL(attention_mfma8_kernel<1>, dim3((KT + 3) / 4, net->heads, n_seq), dim3(256), smem8, st, m);
             else hipLaunchKernelGGL(attention_mfma8_kernel<2>, dim3((KT + 3) / 4, net->heads, n_seq), dim3(256), smem8, st, m);
@@ -2052,17 +1860,16 @@ int run_attention(ttup_uplift* net, const float* qkv, float* out, int n_seq, int
 }
 
 // SimpleStaticLayer.forward (model.py:278-300) on x [n_seq*S][D] in place (x2 is scratch of the same size)
-int run_layer(ttup_uplift* net, const Layer& L, float* x, long long tokens, int n_seq, int S, int num_cls,
-              const float* mask, int mask_div, const float2* rope, int times_div, int times_stride, hipStream_t st) {
-    const int D = net->D;
+int run_layer(ttup_uplift* net, const Layer& L, float* x, long long tokens, int n_seq, const SeqView& sv, hipStream_t st) {
+    const int D = net->D, S = sv.S;
     int rc;
-    static const bool exact0 = getenv("TTUP_F32_EXACT") != nullptr, unfused0 = getenv("TTUP_UPLIFT_UNFUSED") != nullptr;
-    if (D == 128 && net->heads == 4 && S <= 16 && L.qkv.w3_dev && !exact0 && !unfused0) {
+    const Switches& sw = switches();
+    const bool fused = !sw.f32_exact && !sw.unfused;
+    if (D == 128 && net->heads == 4 && S <= 16 && L.qkv.w3_dev && fused) {
         // short sequences (table stage): LN + qkv + RoPE + attention in one kernel, qkv never leaves the CU (attn_block_x3_kernel)
         AttnBlockArgs a;
         a.x = x; a.att = net->att; a.n_seq = n_seq; a.w_qkv = L.qkv.w3_dev; a.b_qkv = L.qkv.b_dev; a.g1 = L.g1; a.b1 = L.b1;
-        a.mask = mask; a.rope = rope; a.S = S; a.num_cls = num_cls; a.mask_div = mask_div; a.times_div = times_div; a.times_stride = times_stride;
-        a.scale = 1.0f / sqrtf((float)net->hd);
+        a.sv = sv;
         const int seqs = 64 / S;
         const size_t smem = (size_t)64 * ATTN_QS * sizeof(float);          // (>= the 48 KB of the three split planes it first holds)
         const dim3 grid((unsigned)((n_seq + seqs - 1) / seqs));
@@ -2070,18 +1877,16 @@ int run_layer(ttup_uplift* net, const Layer& L, float* x, long long tokens, int 
         hipLaunchKernelGGL(attn_block_x3_kernel, grid, dim3(512), smem, st, a);
         TTUP_LAUNCH_CHECK();
     } else {
-        static const bool qkv_linear = getenv("TTUP_UPLIFT_QKV_LINEAR") != nullptr;          // the general linear kernel instead (cross-check)
         // (small launches only: on a full device the general kernel -- 128-token tiles, two workgroups per 128 x 384 block -- is 4 % ahead,
         // B = 10 000: 65.2 k vs 62.8 k trajectories/s; three 121-token trajectories: 0.712 -> 0.689 ms with this one)
-        if (D == 128 && L.qkv.w3_dev && L.qkv.n == 384 && !exact0 && !unfused0 && !qkv_linear && tokens <= 64 * 256) {
+        if (D == 128 && L.qkv.w3_dev && L.qkv.n == 384 && fused && !sw.qkv_linear && tokens <= 64 * 256) {
             QkvArgs qa{x, net->qkv, tokens, L.qkv.w3_dev, L.qkv.b_dev, L.g1, L.b1};
             hipLaunchKernelGGL(qkv_block8_x3_kernel, dim3((unsigned)((tokens + 63) / 64)), dim3(512), (size_t)3 * 64 * 128 * sizeof(uint16_t), st, qa);
             TTUP_LAUNCH_CHECK();
         } else if ((rc = run_linear(L.qkv, x, D, tokens, L.g1, L.b1, 0, nullptr, 0, net->qkv, 3 * D, st))) return rc;
-        if ((rc = run_attention(net, net->qkv, net->att, n_seq, S, num_cls, mask, mask_div, rope, times_div, times_stride, st))) return rc;
+        if ((rc = run_attention(net, net->qkv, net->att, n_seq, sv, st))) return rc;
     }
-    static const bool exact = getenv("TTUP_F32_EXACT") != nullptr, unfused = getenv("TTUP_UPLIFT_UNFUSED") != nullptr;
-    if (D == 128 && L.proj.w3_dev && L.fc1.w3_dev && L.fc2.w3_dev && !exact && !unfused) {
+    if (D == 128 && L.proj.w3_dev && L.fc1.w3_dev && L.fc2.w3_dev && fused) {
         // x = fc2(relu(fc1(LN(proj(att) + x)))) + (proj(att) + x) in one pass over the tokens (mlp_block_x3_kernel)
         MlpArgs a;
         a.att = net->att; a.x = x; a.M = tokens;
@@ -2092,8 +1897,7 @@ int run_layer(ttup_uplift* net, const Layer& L, float* x, long long tokens, int 
         constexpr int bm = 64;
         const size_t smem = (size_t)3 * bm * 128 * sizeof(uint16_t) + (size_t)bm * 128 * sizeof(float);
         const dim3 grid((unsigned)((tokens + bm - 1) / bm));
-        static const bool four = getenv("TTUP_UPLIFT_MLP_4WAVES") != nullptr;          // the round-3 form: 4 waves, two n-tiles each
-        if (four) {
+        if (sw.mlp_4waves) {
             if ((rc = ensure_max_lds((const void*)mlp_block_x3_kernel<1>, 160 * 1024))) return rc;
             hipLaunchKernelGGL(mlp_block_x3_kernel<1>, grid, dim3(256), smem, st, a);
         } else {
@@ -2123,14 +1927,15 @@ void make_stage(ttup_uplift* net, const std::vector<Layer>& layers, std::vector<
 // still beats the per-layer kernels (two per CU) on a full device: 55 k cycles per 64-token layer against 19 k (attention block,
 // bound by the L1 traffic of its weight fragments: every m-tile wave streams its head's weights) + 38 k (MLP block); B = 10 000,
 // T = 120: 50.1 k -> 55.4 k trajectories/s, B = 4096, T = 50: 123 k -> 149 k.  TTUP_UPLIFT_STAGE_WG caps the launch size it is used for.
-int run_stage(ttup_uplift* net, const std::vector<Layer>& layers, const std::vector<StageLayerW>& stage, float* x, long long tokens, int n_seq, int S, int num_cls,
-              const float* mask, int mask_div, const float2* rope, int times_div, int times_stride, hipStream_t st,
-              const float* table_tok = nullptr, int T = 0, int NT = 0, bool* fused_tokens = nullptr) {
+int run_stage(ttup_uplift* net, const std::vector<Layer>& layers, const std::vector<StageLayerW>& stage, float* x, long long tokens, int n_seq, const SeqView& sv,
+              hipStream_t st, const float* table_tok = nullptr, int T = 0, int NT = 0, bool* fused_tokens = nullptr) {
     // (table_tok: the table stage.  When the stage kernel runs, `x` is then the ball-token tensor [n_seq][D], read and written in
     // place, and *fused_tokens = true; otherwise the caller assembles / gathers around the per-layer kernels, which get `x` as usual)
     if (fused_tokens) *fused_tokens = false;
-    static const bool off = getenv("TTUP_F32_EXACT") != nullptr || getenv("TTUP_UPLIFT_UNFUSED") != nullptr || getenv("TTUP_UPLIFT_NO_STAGE") != nullptr;
-    static const long long max_wg = getenv("TTUP_UPLIFT_STAGE_WG") ? atoll(getenv("TTUP_UPLIFT_STAGE_WG")) : (1ll << 40);
+    const int S = sv.S;
+    const Switches& sw = switches();
+    const bool off = sw.f32_exact || sw.unfused || sw.no_stage;
+    const long long max_wg = sw.stage_wg;
     if (!stage.empty() && !off && S <= 64 && n_seq > 0 && (64 / S) * ((S + 3) & ~3) <= STAGE_VS) {          // (V^T holds every sequence of the tile at a multiple of 4)
         const int seqs = 64 / S;
         const long long wgs = ((long long)n_seq + seqs - 1) / seqs;
@@ -2138,12 +1943,11 @@ int run_stage(ttup_uplift* net, const std::vector<Layer>& layers, const std::vec
             StageArgs a;
             a.x = x; a.n_seq = n_seq; a.n_layers = (int)layers.size();
             memcpy(a.layers, stage.data(), stage.size() * sizeof(StageLayerW));
-            a.mask = mask; a.rope = rope; a.S = S; a.num_cls = num_cls; a.mask_div = mask_div; a.times_div = times_div; a.times_stride = times_stride;
-            a.scale = 1.0f / sqrtf((float)net->hd);
+            a.sv = sv;
             a.table_tok = table_tok; a.T = T; a.NT = NT;
             if (fused_tokens) *fused_tokens = table_tok != nullptr;
             if (int rc = ensure_max_lds((const void*)stage_x3_kernel, 160 * 1024)) return rc;
-            static const bool want_stamps = getenv("TTUP_STAGE_STAMPS") != nullptr;
+            const bool want_stamps = sw.stage_stamps;
             static long long* stamps_dev = nullptr;
             a.stamps = nullptr;
             if (want_stamps) {
@@ -2171,7 +1975,7 @@ int run_stage(ttup_uplift* net, const std::vector<Layer>& layers, const std::vec
     }
     if (table_tok) return TTUP_OK;          // declined (*fused_tokens is false, nothing launched): the caller assembles the tokens and calls again
     for (const Layer& L : layers)
-        if (int rc = run_layer(net, L, x, tokens, n_seq, S, num_cls, mask, mask_div, rope, times_div, times_stride, st)) return rc;
+        if (int rc = run_layer(net, L, x, tokens, n_seq, sv, st)) return rc;
     return TTUP_OK;
 }
 
@@ -2196,7 +2000,7 @@ int forward_chunk(ttup_uplift* net, const float* ball, const float* table, const
     int rc;
     {
         const long long n = (long long)B * T + (long long)B * NT;
-        hipLaunchKernelGGL(prepare_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mask, table, net->m1, net->m2, net->tmask, net->txy, B, T, NT, net->flags_dev);
+        hipLaunchKernelGGL(prepare_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, mask, table, net->m1, net->m2, net->tmask, net->txy, B, T, NT, net->flags_dev);
         TTUP_LAUNCH_CHECK();
     }
     const float2* rope = net->rope_index;
@@ -2207,9 +2011,13 @@ int forward_chunk(ttup_uplift* net, const float* ball, const float* table, const
         TTUP_LAUNCH_CHECK();
         rope = net->rope;
     }
+    // the sequences of the three stages: (b, t) -> [ball token, 13 table tokens] at fake times; b -> T tokens; b -> cls + T tokens
+    const float scale = 1.0f / sqrtf((float)net->hd);
+    const SeqView sv_table{net->tmask, net->table_rope, S1, 1, T, 1, 0, scale};
+    const SeqView sv_time{net->m1, rope, T, 0, 1, 1, rope_stride, scale}, sv_cls{net->m2, rope, T + 1, 1, 1, 1, rope_stride, scale};
     // embeddings
     if (net->mode == MODE_STACKED || net->mode == MODE_ORIGINAL) {
-        static const bool per_token = getenv("TTUP_UPLIFT_STACKED_PER_TOKEN") != nullptr;          // the other summation order (cross-check)
+        const bool per_token = switches().stacked_per_token;
         const dim3 grid((unsigned)B, (unsigned)((T + STACKED_TOKENS - 1) / STACKED_TOKENS));
         const int tw = net->mode == MODE_STACKED ? 3 : 2;
         if (per_token) hipLaunchKernelGGL(stacked_embed_kernel<true>, grid, dim3(256), 0, st, ball, table, net->stacked_wt, net->stacked_b, net->h1, T, D, tw);
@@ -2222,17 +2030,17 @@ int forward_chunk(ttup_uplift* net, const float* ball, const float* table, const
         if ((rc = run_linear(net->table_embed.fc2, net->h1, D, (long long)B * NT, nullptr, nullptr, 0, nullptr, 0, net->ttok, D, st))) return rc;
         // table stage: every (b, t) is a 14-token sequence [ball token, 13 table tokens]; its row 0 replaces the ball token afterwards
         const long long tok1 = (long long)B * T * S1;
-        static const bool no_token_fusion = getenv("TTUP_UPLIFT_ASSEMBLE") != nullptr;
+        const bool no_token_fusion = switches().assemble;
         bool fused = false;
         if (!no_token_fusion) {
             // stage kernel: reads the two token tensors itself and writes row 0 only (nothing has been launched if it declines)
-            if ((rc = run_stage(net, net->pos_layers, net->stage_pos, net->tok, tok1, B * T, S1, 1, net->tmask, T, net->table_rope, 1, 0, st, net->ttok, T, NT, &fused))) return rc;
+            if ((rc = run_stage(net, net->pos_layers, net->stage_pos, net->tok, tok1, B * T, sv_table, st, net->ttok, T, NT, &fused))) return rc;
         }
         if (!fused) {
             const long long total = tok1 * D;
             hipLaunchKernelGGL(assemble_table_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, net->tok, net->ttok, net->x, T, NT, D, total);
             TTUP_LAUNCH_CHECK();
-            if ((rc = run_stage(net, net->pos_layers, net->stage_pos, net->x, tok1, B * T, S1, 1, net->tmask, T, net->table_rope, 1, 0, st))) return rc;
+            if ((rc = run_stage(net, net->pos_layers, net->stage_pos, net->x, tok1, B * T, sv_table, st))) return rc;
             const long long total2 = (long long)B * T * D;
             hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((total2 + 255) / 256)), dim3(256), 0, st, net->x, net->tok, D, S1, total2);
             TTUP_LAUNCH_CHECK();
@@ -2240,7 +2048,7 @@ int forward_chunk(ttup_uplift* net, const float* ball, const float* table, const
     }
     if (net->name != NAME_SINGLE) {
         // temporal stage (tok is [B*T][D])
-        if ((rc = run_stage(net, net->layers, net->stage_first, net->tok, (long long)B * T, B, T, 0, net->m1, 1, rope, 1, rope_stride, st))) return rc;
+        if ((rc = run_stage(net, net->layers, net->stage_first, net->tok, (long long)B * T, B, sv_time, st))) return rc;
         if ((rc = run_head(net, net->position_head, net->tok, D, (long long)B * T, pos, st))) return rc;
     }
     // cls token in front of every sequence (x is [B*(T+1)][D])
@@ -2255,13 +2063,13 @@ int forward_chunk(ttup_uplift* net, const float* ball, const float* table, const
         TTUP_LAUNCH_CHECK();
     }
     if (net->name == NAME_SINGLE) {
-        if ((rc = run_stage(net, net->layers, net->stage_first, net->x, (long long)B * (T + 1), B, T + 1, 1, net->m2, 1, rope, 1, rope_stride, st))) return rc;
+        if ((rc = run_stage(net, net->layers, net->stage_first, net->x, (long long)B * (T + 1), B, sv_cls, st))) return rc;
         // position head on every row, the cls rows dropped afterwards (3 floats a row; the head's rows must be evenly spaced)
         if ((rc = run_head(net, net->position_head, net->x, D, (long long)B * (T + 1), net->pos_rows, st))) return rc;
         const long long total = (long long)B * T * 3;
         hipLaunchKernelGGL(strip_cls3_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, net->pos_rows, pos, T, total);
         TTUP_LAUNCH_CHECK();
-    } else if ((rc = run_stage(net, net->second, net->stage_second, net->x, (long long)B * (T + 1), B, T + 1, 1, net->m2, 1, rope, 1, rope_stride, st))) return rc;
+    } else if ((rc = run_stage(net, net->second, net->stage_second, net->x, (long long)B * (T + 1), B, sv_cls, st))) return rc;
     // rotation head on the cls rows (row stride (T+1)*D)
     return run_head(net, net->rotation_head, net->x, (T + 1) * D, B, rot, st);
 }
@@ -2379,7 +2187,7 @@ extern "C" int ttup_uplift_create(const void* blob, size_t blob_bytes, int max_b
         long long gt = (long long)max_batch * max_len < GRAPH_TOKENS ? (long long)max_batch * max_len : GRAPH_TOKENS;
         if (gt < max_len) gt = max_len;          // at least one trajectory of the longest length
         net->graph_tokens = gt;
-        net->graphs_off = getenv("TTUP_UPLIFT_NO_GRAPH") != nullptr;
+        net->graphs_off = env_set("TTUP_UPLIFT_NO_GRAPH");
         const size_t nb = (size_t)(gt / 1 > max_batch ? max_batch : gt);          // trajectories a graph call can hold (len >= 1)
         if ((rc = dev_alloc(net.get(), (size_t)gt * 2, &net->g_ball))) return rc;
         if ((rc = dev_alloc(net.get(), nb * net->n_table * 3, &net->g_table))) return rc;
@@ -2432,7 +2240,7 @@ extern "C" int ttup_uplift_forward(ttup_uplift* net, const float* ball_dev, cons
             if (ok) ok = hipGraphInstantiate(&ge.exec, graph, nullptr, nullptr, 0) == hipSuccess;
             if (graph) (void)hipGraphDestroy(graph);
             if (!ok) {
-                if (getenv("TTUP_DEBUG")) fprintf(stderr, "ttup_uplift: graph capture failed (%s): eager from now on\n", hipGetErrorString(hipGetLastError()));
+                if (env_set("TTUP_DEBUG")) fprintf(stderr, "ttup_uplift: graph capture failed (%s): eager from now on\n", hipGetErrorString(hipGetLastError()));
                 (void)hipGetLastError(); ge.exec = nullptr; net->graphs_off = true;
             }          // this runtime cannot capture the forward: eager from now on
             else {

@@ -16,6 +16,7 @@
 #include "common.h"
 #include "uplift_net.h"
 #include "gemm_f32.h"
+#include "uplift_tokens.h"
 #include <math.h>
 #include <vector>
 
@@ -183,20 +184,18 @@ __global__ void relu_kernel(const float* __restrict__ x, float* __restrict__ y, 
 // masked query row yields zeros (torch SDPA) and gets a zero gradient.
 struct AttnArgs {
     const float* qkv;   // [n_seq*S][3D], q and k before RoPE
-    const float* mask;  // additive, row = seq / mask_div, S entries
-    const float2* rope; // (cos, sin) rows of hd/2; row of token j = (seq / times_div) * times_stride + j - num_cls
     float* out;         // forward: attention output [n_seq*S][D]
     const float* o;     // backward: the forward's output
     const float* d_o;   // backward: its gradient
     float* dqkv;        // backward: [n_seq*S][3D]
-    int n_seq, S, D, num_cls, mask_div, times_div, times_stride, P;
-    float scale;
+    int n_seq, D, P;
+    SeqView sv;
 };
 
 template <int HD, bool BWD>
 __global__ __launch_bounds__(256) void attention_grad_kernel(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int S = a.S, P = a.P, G = ttup_bdim_x() / P;
+    const int S = a.sv.S, P = a.P, G = ttup_bdim_x() / P;
     const int NARR = BWD ? 4 : 2;                     // k~, v, (q~, dO)
     const int SEQ = NARR * S * HD + (BWD ? 3 * S : 0) + S;          // floats per sequence: the arrays, (mx, 1/den, rowsum(dO o O)), mask
     const int h = ttup_bid_y(), tid = ttup_tid_x();
@@ -210,8 +209,8 @@ __global__ __launch_bounds__(256) void attention_grad_kernel(AttnArgs a) {
         const float* qp = a.qkv + ((size_t)seq * S + j) * D3 + h * HD + 2 * e;
         float2 q = *(const float2*)qp, k = *(const float2*)(qp + a.D);
         const float2 v = *(const float2*)(qp + 2 * a.D);
-        if (j >= a.num_cls) {
-            const float2 cs = a.rope[((size_t)(seq / a.times_div) * a.times_stride + (j - a.num_cls)) * (HD / 2) + e];
+        if (j >= a.sv.num_cls) {
+            const float2 cs = a.sv.rope[((size_t)(seq / a.sv.times_div) * a.sv.times_stride + (j - a.sv.num_cls)) * (HD / 2) + e];
             k = make_float2(k.x * cs.x - k.y * cs.y, k.x * cs.y + k.y * cs.x);
             q = make_float2(q.x * cs.x - q.y * cs.y, q.x * cs.y + q.y * cs.x);
         }
@@ -226,7 +225,7 @@ __global__ __launch_bounds__(256) void attention_grad_kernel(AttnArgs a) {
     for (int u = tid; u < G * S; u += ttup_bdim_x()) {
         const int g = u / S, j = u - g * S;
         const int seq = ttup_bid_x() * G + g;
-        sm[(size_t)g * SEQ + NARR * S * HD + (BWD ? 3 * S : 0) + j] = seq < a.n_seq ? a.mask[(size_t)(seq / a.mask_div) * S + j] : -INFINITY;
+        sm[(size_t)g * SEQ + NARR * S * HD + (BWD ? 3 * S : 0) + j] = seq < a.n_seq ? a.sv.mask[(size_t)(seq / a.sv.mask_div) * S + j] : -INFINITY;
     }
     __syncthreads();
     const int g = tid / P, i = tid - g * P;
@@ -250,8 +249,8 @@ __global__ __launch_bounds__(256) void attention_grad_kernel(AttnArgs a) {
             const float* qp = a.qkv + ((size_t)seq * S + i) * D3 + h * HD;
 #pragma unroll
             for (int d = 0; d < HD; ++d) q[d] = qp[d];
-            if (i >= a.num_cls) {
-                const float2* rp = a.rope + ((size_t)(seq / a.times_div) * a.times_stride + (i - a.num_cls)) * (HD / 2);
+            if (i >= a.sv.num_cls) {
+                const float2* rp = a.sv.rope + ((size_t)(seq / a.sv.times_div) * a.sv.times_stride + (i - a.sv.num_cls)) * (HD / 2);
 #pragma unroll
                 for (int e = 0; e < HD / 2; ++e) {
                     const float2 cs = rp[e];
@@ -265,7 +264,7 @@ __global__ __launch_bounds__(256) void attention_grad_kernel(AttnArgs a) {
             float s = 0.f;
 #pragma unroll
             for (int d = 0; d < HD; ++d) s = fmaf(q[d], ks[j * HD + d], s);
-            s *= a.scale;
+            s *= a.sv.scale;
             mx = s > mx ? s : mx;
         }
         for (int j = 0; j < S; ++j) {
@@ -273,7 +272,7 @@ __global__ __launch_bounds__(256) void attention_grad_kernel(AttnArgs a) {
             float s = 0.f;
 #pragma unroll
             for (int d = 0; d < HD; ++d) s = fmaf(q[d], ks[j * HD + d], s);
-            den += expf(s * a.scale - mx);
+            den += expf(s * a.sv.scale - mx);
         }
     }
     const float inv = den > 0.f ? 1.f / den : 0.f;
@@ -288,7 +287,7 @@ __global__ __launch_bounds__(256) void attention_grad_kernel(AttnArgs a) {
                 float s = 0.f;
 #pragma unroll
                 for (int d = 0; d < HD; ++d) s = fmaf(q[d], ks[j * HD + d], s);
-                const float p = expf(s * a.scale - mx) * inv;
+                const float p = expf(s * a.sv.scale - mx) * inv;
 #pragma unroll
                 for (int d = 0; d < HD; ++d) o[d] = fmaf(p, vs[j * HD + d], o[d]);
             }
@@ -311,8 +310,8 @@ __global__ __launch_bounds__(256) void attention_grad_kernel(AttnArgs a) {
             float s = 0.f, dp = 0.f;
 #pragma unroll
             for (int d = 0; d < HD; ++d) { s = fmaf(q[d], ks[j * HD + d], s); dp = fmaf(ds[i * HD + d], vs[j * HD + d], dp); }
-            const float p = expf(s * a.scale - mx) * inv;
-            const float t = p * (dp - dsum) * a.scale;
+            const float p = expf(s * a.sv.scale - mx) * inv;
+            const float t = p * (dp - dsum) * a.sv.scale;
 #pragma unroll
             for (int d = 0; d < HD; ++d) acc[d] = fmaf(t, ks[j * HD + d], acc[d]);
         }
@@ -320,8 +319,8 @@ __global__ __launch_bounds__(256) void attention_grad_kernel(AttnArgs a) {
     if (live) {
         stats[3 * i] = row_on ? mx : 0.f; stats[3 * i + 1] = row_on ? inv : 0.f; stats[3 * i + 2] = dsum;
         float* gp = a.dqkv + ((size_t)seq * S + i) * D3 + h * HD;
-        if (i >= a.num_cls) {          // back through the rotation: its transpose
-            const float2* rp = a.rope + ((size_t)(seq / a.times_div) * a.times_stride + (i - a.num_cls)) * (HD / 2);
+        if (i >= a.sv.num_cls) {          // back through the rotation: its transpose
+            const float2* rp = a.sv.rope + ((size_t)(seq / a.sv.times_div) * a.sv.times_stride + (i - a.sv.num_cls)) * (HD / 2);
 #pragma unroll
             for (int e = 0; e < HD / 2; ++e) {
                 const float2 cs = rp[e];
@@ -348,15 +347,15 @@ __global__ __launch_bounds__(256) void attention_grad_kernel(AttnArgs a) {
             float s = 0.f, dp = 0.f;
 #pragma unroll
             for (int d = 0; d < HD; ++d) { s = fmaf(qs[r * HD + d], kk[d], s); dp = fmaf(ds[r * HD + d], vv[d], dp); }
-            const float p = expf(s * a.scale - stats[3 * r]) * stats[3 * r + 1];
-            const float t = p * (dp - stats[3 * r + 2]) * a.scale;
+            const float p = expf(s * a.sv.scale - stats[3 * r]) * stats[3 * r + 1];
+            const float t = p * (dp - stats[3 * r + 2]) * a.sv.scale;
 #pragma unroll
             for (int d = 0; d < HD; ++d) { dk[d] = fmaf(t, qs[r * HD + d], dk[d]); dv[d] = fmaf(p, ds[r * HD + d], dv[d]); }
         }
     }
     float* gk = a.dqkv + ((size_t)seq * S + i) * D3 + a.D + h * HD;
-    if (i >= a.num_cls) {
-        const float2* rp = a.rope + ((size_t)(seq / a.times_div) * a.times_stride + (i - a.num_cls)) * (HD / 2);
+    if (i >= a.sv.num_cls) {
+        const float2* rp = a.sv.rope + ((size_t)(seq / a.sv.times_div) * a.sv.times_stride + (i - a.sv.num_cls)) * (HD / 2);
 #pragma unroll
         for (int e = 0; e < HD / 2; ++e) {
             const float2 cs = rp[e];
@@ -374,8 +373,8 @@ __global__ __launch_bounds__(256) void attention_grad_kernel(AttnArgs a) {
 template <int HD, bool BWD>
 int launch_attention(const AttnArgs& a, int heads, hipStream_t st) {
     const int G = a.P >= 64 ? 1 : 64 / a.P, threads = G * a.P;
-    const size_t smem = (size_t)G * ((BWD ? 4 : 2) * a.S * HD + (BWD ? 3 * a.S : 0) + a.S) * sizeof(float);
-    TTUP_REQUIRE(smem <= 160 * 1024, TTUP_EINVAL, "uplift gradient: sequence length %d too long for the attention kernels", a.S);
+    const size_t smem = (size_t)G * ((BWD ? 4 : 2) * a.sv.S * HD + (BWD ? 3 * a.sv.S : 0) + a.sv.S) * sizeof(float);
+    TTUP_REQUIRE(smem <= 160 * 1024, TTUP_EINVAL, "uplift gradient: sequence length %d too long for the attention kernels", a.sv.S);
     if (smem > 48 * 1024)
         if (int rc = ensure_max_lds((const void*)attention_grad_kernel<HD, BWD>, 160 * 1024)) return rc;
     hipLaunchKernelGGL((attention_grad_kernel<HD, BWD>), dim3((unsigned)((a.n_seq + G - 1) / G), (unsigned)heads), dim3(threads), smem, st, a);
@@ -384,10 +383,10 @@ int launch_attention(const AttnArgs& a, int heads, hipStream_t st) {
 }
 template <bool BWD>
 int run_attention(const ttup_uplift* net, AttnArgs a, hipStream_t st) {
-    a.D = net->D; a.scale = 1.0f / sqrtf((float)net->hd);
+    a.D = net->D;
     int P = 16;
-    while (P < a.S) P *= 2;
-    TTUP_REQUIRE(P <= 256, TTUP_EINVAL, "uplift gradient: sequence length %d above 256", a.S);
+    while (P < a.sv.S) P *= 2;
+    TTUP_REQUIRE(P <= 256, TTUP_EINVAL, "uplift gradient: sequence length %d above 256", a.sv.S);
     a.P = P;
     if (a.n_seq == 0) return TTUP_OK;
     switch (net->hd) {
@@ -400,17 +399,8 @@ int run_attention(const ttup_uplift* net, AttnArgs a, hipStream_t st) {
     return TTUP_EINVAL;
 }
 
-// ------------------------------------------------------------------ token plumbing, masks, RoPE table, loss
-// x[(b,t), 0] = ball_tok[b,t]; x[(b,t), 1+n] = table_tok[b,n]      (model.py:374-378)
-__global__ void assemble_kernel(const float* ball_tok, const float* table_tok, float* x, int T, int NT, int D, long long total) {
-    const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
-    if (i >= total) return;
-    const int d = (int)(i % D);
-    long long r = i / D;
-    const int n = (int)(r % (NT + 1)); r /= (NT + 1);
-    x[i] = n == 0 ? ball_tok[r * D + d] : table_tok[((r / T) * NT + (n - 1)) * D + d];
-}
-// its transpose: d ball_tok[b,t] = dx[(b,t), 0];  d table_tok[b,n] = sum over t (in order) of dx[(b,t), 1+n]
+// ------------------------------------------------------------------ token plumbing (the rest: uplift_tokens.h), loss
+// the transpose of assemble_table_kernel (uplift_tokens.h): d ball_tok[b,t] = dx[(b,t), 0];  d table_tok[b,n] = sum over t (in order) of dx[(b,t), 1+n]
 __global__ void assemble_bwd_kernel(const float* dx, float* d_ball, float* d_table, int B, int T, int NT, int D) {
     const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
     const long long nb = (long long)B * T * D, ntab = (long long)B * NT * D;
@@ -426,66 +416,12 @@ __global__ void assemble_bwd_kernel(const float* dx, float* d_ball, float* d_tab
         d_table[j] = acc;
     }
 }
-// y[r] = x[r * seq_tokens] (row 0 of every sequence)
-__global__ void gather_rows_kernel(const float* x, float* y, int D, int seq_tokens, long long total) {
-    const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
-    if (i >= total) return;
-    y[i] = x[((i / D) * seq_tokens) * D + i % D];
-}
-// its transpose: y[r * seq_tokens] = x[r], every other row 0
+// the transpose of gather_rows_kernel: y[r * seq_tokens] = x[r], every other row 0
 __global__ void expand_rows_kernel(const float* x, float* y, int D, int seq_tokens, long long total) {
     const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
     if (i >= total) return;
     const long long r = i / D;
     y[i] = r % seq_tokens == 0 ? x[(r / seq_tokens) * D + i % D] : 0.f;
-}
-// y[b, 0] = cls; y[b, 1+t] = x[b, t]                                 (model.py:560)
-__global__ void prepend_cls_kernel(const float* x, const float* cls, float* y, int T, int D, long long total) {
-    const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
-    if (i >= total) return;
-    const int d = (int)(i % D);
-    const long long r = i / D;
-    const int t = (int)(r % (T + 1)); const long long b = r / (T + 1);
-    y[i] = t == 0 ? cls[d] : x[(b * T + (t - 1)) * D + d];
-}
-// masks: mask (B,T) {0,1} -> additive m1 (B,T), m2 (B,T+1) with leading 0; table (B,13,3) -> tmask (B,14), txy (B*13,2)
-__global__ void prepare_kernel(const float* mask, const float* table, float* m1, float* m2, float* tmask, float* txy, int B, int T, int NT) {
-    const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
-    const long long nmask = (long long)B * T, ntab = (long long)B * NT;
-    if (i < nmask) {
-        const float add = mask[i] == 0.f ? -INFINITY : 0.f;
-        m1[i] = add;
-        const long long b = i / T; const int t = (int)(i % T);
-        m2[b * (T + 1) + 1 + t] = add;
-        if (t == 0) m2[b * (T + 1)] = 0.f;
-    } else if (i < nmask + ntab) {
-        const long long j = i - nmask;
-        const long long b = j / NT; const int n = (int)(j % NT);
-        tmask[b * (NT + 1) + 1 + n] = table[j * 3 + 2] == 1.f ? 0.f : -INFINITY;      // KEYPOINT_VISIBLE == 1, model.py:363
-        if (n == 0) tmask[b * (NT + 1)] = 0.f;
-        txy[j * 2] = table[j * 3]; txy[j * 2 + 1] = table[j * 3 + 1];
-    }
-}
-// rope[r][i] = (cos, sin)(round(t_r / 0.002) * inv_freq[i])           (model.py:62-80, time_rotation 'new')
-__global__ void rope_table_kernel(const float* times, const float* inv_freq, float2* rope, int half, long long total) {
-    const long long i = (long long)ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
-    if (i >= total) return;
-    const float pos = rintf(times[i / half] / 0.002f);
-    const float f = pos * inv_freq[i % half];
-    rope[i] = make_float2(cosf(f), sinf(f));
-}
-// transform_rotationaxes (uplifting/helper.py:394-420) of the target spin
-__global__ void rotationaxes_kernel(const float* rot, const float* pos, int B, int T, float* out) {
-    const int b = ttup_bid_x() * ttup_bdim_x() + ttup_tid_x();
-    if (b >= B) return;
-    const float* p = pos + (size_t)b * T * 3;
-    const float vx = p[3] - p[0], vy = p[4] - p[1];
-    const float nrm = sqrtf(vx * vx + vy * vy);
-    const float ex = vx / nrm, ey = vy / nrm;
-    const float* r = rot + (size_t)b * 3;
-    out[b * 3 + 0] = r[0] * ex + r[1] * ey + r[2] * 0.f;
-    out[b * 3 + 1] = r[0] * (-ey) + r[1] * ex + r[2] * 0.f;
-    out[b * 3 + 2] = r[0] * 0.f + r[1] * 0.f + r[2] * 1.f;
 }
 // one workgroup, fixed tree: thread t sums elements t, t+1024, ...; then the halving tree over the 1024 partial sums
 __device__ __forceinline__ float block_sum_1024(float v, float* sm) {
@@ -641,8 +577,6 @@ void make_plan(const ttup_uplift* net, int batch, int len, float* base, Plan* p)
         }                                                                                                                 \
     } while (0)
 
-struct Seq { const float* mask; int mask_div; const float2* rope; int times_div, times_stride; };
-
 int ln_fwd(const Ctx& c, const float* x, const float* g, const float* b, float* y, long long M, int D) {
     if (M == 0) return TTUP_OK;
     hipLaunchKernelGGL(ln_fwd_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, c.st, x, g, b, y, M, D);
@@ -651,14 +585,13 @@ int ln_fwd(const Ctx& c, const float* x, const float* g, const float* b, float* 
 }
 
 // SimpleStaticLayer.forward (model.py:278-300): x -> xo, keeping S
-int layer_fwd(const ttup_uplift* net, const Ctx& c, const Plan& p, const LayerP& L, const Saved& S, float* xo, const Stage& sg, int n_seq, const Seq& q) {
+int layer_fwd(const ttup_uplift* net, const Ctx& c, const Plan& p, const LayerP& L, const Saved& S, float* xo, const Stage& sg, int n_seq, const SeqView& sv) {
     const int D = net->D;
     const long long M = (long long)n_seq * sg.S;
     GRC(ln_fwd(c, S.x, L.g1, L.b1, p.tA, M, D));
     GRC(linear_fwd(p.tA, D, L.qkv.w, L.qkv.b, S.qkv, 3 * D, M, 3 * D, D, 0, nullptr, 0, c.st));
     AttnArgs a = {};
-    a.qkv = S.qkv; a.mask = q.mask; a.rope = q.rope; a.out = S.att; a.n_seq = n_seq; a.S = sg.S; a.num_cls = sg.num_cls;
-    a.mask_div = q.mask_div; a.times_div = q.times_div; a.times_stride = q.times_stride;
+    a.qkv = S.qkv; a.sv = sv; a.out = S.att; a.n_seq = n_seq;
     GRC(run_attention<false>(net, a, c.st));
     GRC(linear_fwd(S.att, D, L.proj.w, nullptr, S.x2, D, M, D, D, E_RESID, S.x, D, c.st));
     GRC(ln_fwd(c, S.x2, L.g2, L.b2, p.tA, M, D));
@@ -668,7 +601,7 @@ int layer_fwd(const ttup_uplift* net, const Ctx& c, const Plan& p, const LayerP&
 }
 // its backward: dxo (gradient at the layer's output) -> dxi (at its input; may be the same buffer), parameter gradients accumulated
 int layer_bwd(const ttup_uplift* net, const Ctx& c, const Plan& p, const LayerP& L, const Saved& S, const float* dxo, float* dxi, const Stage& sg,
-              int n_seq, const Seq& q) {
+              int n_seq, const SeqView& sv) {
     const int D = net->D;
     const long long M = (long long)n_seq * sg.S;
     // fc2
@@ -687,8 +620,7 @@ int layer_bwd(const ttup_uplift* net, const Ctx& c, const Plan& p, const LayerP&
     GRC(linear_dw(c, p.tC, D, S.att, D, M, D, D, L.proj.gw, nullptr));
     GRC(linear_dx(p.tC, D, L.proj.w, p.tA, D, M, D, D, 0, nullptr, 0, nullptr, 0, c.st));               // tA = d att
     AttnArgs a = {};
-    a.qkv = S.qkv; a.mask = q.mask; a.rope = q.rope; a.o = S.att; a.d_o = p.tA; a.dqkv = p.tQ; a.n_seq = n_seq; a.S = sg.S; a.num_cls = sg.num_cls;
-    a.mask_div = q.mask_div; a.times_div = q.times_div; a.times_stride = q.times_stride;
+    a.qkv = S.qkv; a.sv = sv; a.o = S.att; a.d_o = p.tA; a.dqkv = p.tQ; a.n_seq = n_seq;
     GRC(run_attention<true>(net, a, c.st));
     // qkv over LayerNorm 1
     GRC(ln_fwd(c, S.x, L.g1, L.b1, p.tB, M, D));
@@ -699,14 +631,14 @@ int layer_bwd(const ttup_uplift* net, const Ctx& c, const Plan& p, const LayerP&
     GRC(colsum_into(c, p.tE, D, M, D, L.dg1));
     return colsum_into(c, p.tA, D, M, D, L.db1);
 }
-int stage_fwd(const ttup_uplift* net, const Ctx& c, const Plan& p, const std::vector<LayerP>& W, const Stage& sg, int n_seq, const Seq& q) {
+int stage_fwd(const ttup_uplift* net, const Ctx& c, const Plan& p, const std::vector<LayerP>& W, const Stage& sg, int n_seq, const SeqView& sv) {
     for (size_t l = 0; l < W.size(); ++l)
-        GRC(layer_fwd(net, c, p, W[l], sg.L[l], l + 1 < W.size() ? sg.L[l + 1].x : sg.out, sg, n_seq, q));
+        GRC(layer_fwd(net, c, p, W[l], sg.L[l], l + 1 < W.size() ? sg.L[l + 1].x : sg.out, sg, n_seq, sv));
     return TTUP_OK;
 }
-int stage_bwd(const ttup_uplift* net, const Ctx& c, const Plan& p, const std::vector<LayerP>& W, const Stage& sg, int n_seq, const Seq& q, float* dx) {
+int stage_bwd(const ttup_uplift* net, const Ctx& c, const Plan& p, const std::vector<LayerP>& W, const Stage& sg, int n_seq, const SeqView& sv, float* dx) {
     for (size_t l = W.size(); l-- > 0;)
-        GRC(layer_bwd(net, c, p, W[l], sg.L[l], dx, dx, sg, n_seq, q));
+        GRC(layer_bwd(net, c, p, W[l], sg.L[l], dx, dx, sg, n_seq, sv));
     return TTUP_OK;
 }
 // MyHead (model.py:232-261): x (row stride ldx) -> out (M,3), keeping the two hidden activations
@@ -745,7 +677,7 @@ int group_pass(const ttup_uplift* net, const Ctx& c, const Plan& p, const Params
                const float* times, const float* r_world, const float* rotation, int B, int T, int flags, float* loss, float* rot, float* pos) {
     const int D = net->D, NT = net->n_table, S1 = NT + 1;
     const long long nt = (long long)B * T, n1 = nt * S1, n2 = (long long)B * (T + 1);
-    LAUNCH1D(prepare_kernel, nt + (long long)B * NT, mask, table, p.m1, p.m2, p.tmask, p.txy, B, T, NT);
+    LAUNCH1D(prepare_kernel<false>, nt + (long long)B * NT, mask, table, p.m1, p.m2, p.tmask, p.txy, B, T, NT, (int*)nullptr);
     const float2* rope = net->rope_index;
     const int rope_stride = net->rot_old ? 0 : T;
     if (!net->rot_old) {
@@ -753,11 +685,13 @@ int group_pass(const ttup_uplift* net, const Ctx& c, const Plan& p, const Params
         LAUNCH1D(rope_table_kernel, n, times, net->inv_freq_dev, (float2*)p.rope, net->hd / 2, n);
         rope = (const float2*)p.rope;
     }
-    const Seq q_table{p.tmask, T, net->table_rope, 1, 0}, q_time{p.m1, 1, rope, 1, rope_stride}, q_spin{p.m2, 1, rope, 1, rope_stride};
+    const float scale = 1.0f / sqrtf((float)net->hd);
+    const SeqView q_table{p.tmask, net->table_rope, S1, 1, T, 1, 0, scale};
+    const SeqView q_time{p.m1, rope, T, 0, 1, 1, rope_stride, scale}, q_spin{p.m2, rope, T + 1, 1, 1, 1, rope_stride, scale};
     // ---- forward
     GRC(embed_fwd(net, c, W.ball1, W.ball2, ball, nt, p.ball_h, p.ball_tok));
     GRC(embed_fwd(net, c, W.tab1, W.tab2, p.txy, (long long)B * NT, p.tab_h, p.tab_tok));
-    LAUNCH1D(assemble_kernel, n1 * D, p.ball_tok, p.tab_tok, p.table.L[0].x, T, NT, D, n1 * D);
+    LAUNCH1D(assemble_table_kernel, n1 * D, p.ball_tok, p.tab_tok, p.table.L[0].x, T, NT, D, n1 * D);
     GRC(stage_fwd(net, c, p, W.pos, p.table, (int)nt, q_table));
     LAUNCH1D(gather_rows_kernel, nt * D, p.table.out, p.temporal.L[0].x, D, S1, nt * D);
     GRC(stage_fwd(net, c, p, W.first, p.temporal, B, q_time));

@@ -26,6 +26,15 @@ struct StageLayerW {
     const float *b_qkv, *g1, *b1, *g2, *b2, *bias1, *bias2;
 };
 
+// The sequences an attention kernel works on, in a flat [n_seq * S][..] token array
+struct SeqView {
+    const float* mask;      // additive {0, -inf}; row of sequence seq = seq / mask_div, S entries
+    const float2* rope;     // (cos, sin) rows of hd/2; row of token j of sequence seq = (seq / times_div) * times_stride + j - num_cls
+    int S, num_cls;         // tokens per sequence; leading tokens that are not rotated (the cls token)
+    int mask_div, times_div, times_stride;
+    float scale;            // 1 / sqrt(head dim)
+};
+
 struct Layer { Linear qkv, proj, fc1, fc2; float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr; };
 struct Mlp2 { Linear fc1, fc2; };
 struct Head { Linear fc1, fc2, fc3; };
