@@ -305,7 +305,15 @@ int ttup_uplift_stage_info(ttup_uplift* net, long long* out_host);
  * unsupported handle.  It grows with min(batch, 262144 / (14 len)) trajectories: larger batches are processed in groups of that size.
  * ttup_uplift_loss_grad: ball (B,T,2), table (B,13,3), mask (B,T) in {0,1}, times (B,T), r_world (B,T,3), rotation (B,3), all
  * float32 on the device.  flags bit 0: transform_mode 'local' -- the target spin is first passed through
- * ttup_transform_rotationaxes(rotation, r_world) (train.py:123-124; no gradient flows into it).  Outputs (device): grad
+ * ttup_transform_rotationaxes(rotation, r_world) (train.py:123-124; no gradient flows into it).  flags bit 1: check the mask's
+ * format as ttup_uplift_forward's check_mask does -- the reference's training step goes through model.forward, which raises
+ * unless the mask holds 0 and 1, both present, and nothing else (model.py:541-546): TTUP_EMASK otherwise (an all-ones or all-zeros
+ * batch, a value such as 0.5, the additive {-1e9, 0} form).  The check costs one word read back and one stream synchronisation
+ * after the pass is enqueued, so a call refused with TTUP_EMASK HAS written grad, loss, rot and pos: they hold no defined values
+ * (loss_pos of an all-zeros mask is 0 / 0) and must not be used.  Without bit 1 nothing is checked, the call does not synchronise,
+ * and the results are the same bits.  Every other refusal (TTUP_EINVAL: a null pointer, an unsupported variant, len outside
+ * [1,255], 'local' with len 1, time_rotation 'old' with len above the handle's max_len, unknown flag bits, a workspace that is
+ * too small or not 16-byte aligned) comes before anything is enqueued and leaves every output untouched.  Outputs (device): grad
  * (n_floats), loss[2] = {loss_rot, loss_pos}, rot (B,3), pos (B,T,3).  len <= 255.  No floating-point atomics: two calls on the
  * same inputs return the same bits, whatever the handle's max_batch.  A padded time step (mask 0) or an invisible keypoint
  * contributes exactly zero to every output but its own rows of pos. */

@@ -1,4 +1,4 @@
-"""Reading tests/golden/uplift_grad.npz / uplift_grad_sampled.npz (tools/make_goldens_uplift_grad.py) and comparing a gradient
+"""Reading tests/golden/uplift_grad.npz / uplift_grad_sampled.npz / uplift_grad_edges.npz (tools/make_goldens_uplift_grad.py) and comparing a gradient
 against a case: shared by the CPU test of the torch restatement and the GPU test of the library."""
 import os
 
@@ -7,7 +7,7 @@ import numpy as np
 from upliftingtabletennis_amd import arch, synth, weights
 
 GOLDEN = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'golden')
-FILES = ('uplift_grad.npz', 'uplift_grad_sampled.npz')
+FILES = ('uplift_grad.npz', 'uplift_grad_sampled.npz', 'uplift_grad_edges.npz')
 # the cases the fixture must hold: (size, time_rotation, transform_mode, batch, t, pad, stored in full)
 EXPECTED = {
     'small_new_global_T20': ('small', 'new', 'global', 3, 17, 3, True),
@@ -17,7 +17,12 @@ EXPECTED = {
     'large_new_global_T50': ('large', 'new', 'global', 4, 43, 7, False),
     'large_new_global_T121': ('large', 'new', 'global', 3, 120, 1, False),
     'huge_new_global_T20': ('huge', 'new', 'global', 2, 17, 3, False),
+    'edge_small_new_global_T16': ('small', 'new', 'global', 4, 13, 3, True),
+    'edge_small_old_local_T16': ('small', 'old', 'local', 4, 13, 3, True),
 }
+# their input kind: 'ragged' (synth.ragged_uplift_batch) unless named here
+EXPECTED_KIND = {'edge_small_new_global_T16': 'edge', 'edge_small_old_local_T16': 'edge'}
+INPUTS = {'ragged': synth.ragged_uplift_batch, 'edge': synth.edge_uplift_batch}
 N_SAMPLES = 256
 
 
@@ -28,6 +33,7 @@ class Case:
         self.seed, self.b, self.t, self.pad, local = [int(v) for v in g('meta')]
         self.size, self.rot_kind = [str(v) for v in g('variant')]
         self.mode = 'local' if local else 'global'
+        self.kind = str(g('kind')) if ('%s/kind' % key) in z.files else 'ragged'
         self.loss, self.rot, self.pos = g('loss'), g('rot'), g('pos')
         self.unused = [str(v) for v in g('unused')]
         self.norms, self.self_noise, self.relu_margin = g('norms'), g('self_noise'), float(g('relu_margin'))
@@ -41,7 +47,7 @@ class Case:
 
     def inputs(self):
         """ball, table, mask, times, r_world, rotation (numpy float32)"""
-        return list(synth.ragged_uplift_batch(self.b, self.t, seed=self.seed, pad=self.pad)) + list(synth.uplift_targets(self.b, self.t + self.pad, self.seed))
+        return list(INPUTS[self.kind](self.b, self.t, seed=self.seed, pad=self.pad)) + list(synth.uplift_targets(self.b, self.t + self.pad, self.seed))
 
     def compare(self, grads):
         """grads: {name: numpy array or None}.  -> (worst relative L2 over the tensors' stored entries, worst relative norm error);

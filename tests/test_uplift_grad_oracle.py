@@ -51,6 +51,12 @@ def test_fixture_holds_the_cases_and_its_own_conditions():
     for key, want in C.EXPECTED.items():
         c = CASES[key]
         assert (c.size, c.rot_kind, c.mode, c.b, c.t, c.pad, c.full) == want, key
+        assert c.kind == C.EXPECTED_KIND.get(key, 'ragged'), key
+        if c.kind == 'edge':          # the mask forms the edge cases are there for, on the inputs the case rebuilds
+            _, table, mask, _ = c.inputs()[:4]
+            vis = (table[:, :, 2] == 1).sum(1)
+            assert mask[0, 2] == 0 and mask[0, 1] == 1 and mask[0, 3] == 1 and mask[1].sum() == 1 and not mask[3].any()
+            assert vis[0] == 0 and vis[2] == 1
         used = np.array([u for _, _, _, u in c.layout])
         assert c.self_noise.max() <= NOISE_CEILING
         assert c.relu_margin >= R.RELU_MARGIN == 2.0 ** -24          # no ReLU of the reference's forward on its kink

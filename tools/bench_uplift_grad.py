@@ -54,7 +54,7 @@ def main():
         data = inputs(b, a.len)
         net = uplift.MultiStageModel(sd, size='large', max_batch=b, max_len=a.len)
         ws = int(net._lib.ttup_uplift_grad_workspace_bytes(net._handle, b, a.len))
-        tg = timed(lambda: net.loss_and_grad(*data), a.repeat)
+        tg = timed(lambda: net.loss_and_grad(*data, check_mask=False), a.repeat)
         tf = timed(lambda: net.forward(*data[:4], check_mask=False), a.repeat)
         rows.append({'batch': b, 'len': a.len, 'workspace_bytes': ws,
                      'grad_samples_per_s_best': b / min(tg), 'grad_samples_per_s_median': b / statistics.median(tg),

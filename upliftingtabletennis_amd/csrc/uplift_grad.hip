@@ -29,6 +29,7 @@ namespace {
 constexpr int KSLICE = 512;                  // rows per partial sum of dW / db / dgamma / dbeta / d cls
 constexpr long long GROUP_TOKENS = 262144;   // table-stage tokens (14 per time step) per group of trajectories
 constexpr int FLAG_LOCAL = 1;                // transform_mode == 'local'
+constexpr int FLAG_CHECK_MASK = 2;           // the reference's mask-format ValueError (model.py:541-546): one read-back and one stream synchronisation
 
 // ------------------------------------------------------------------ GEMM wrappers (gemm_f32.h, GUARD form)
 template <int AM, int WM>
@@ -677,7 +678,10 @@ int group_pass(const ttup_uplift* net, const Ctx& c, const Plan& p, const Params
                const float* times, const float* r_world, const float* rotation, int B, int T, int flags, float* loss, float* rot, float* pos) {
     const int D = net->D, NT = net->n_table, S1 = NT + 1;
     const long long nt = (long long)B * T, n1 = nt * S1, n2 = (long long)B * (T + 1);
-    LAUNCH1D(prepare_kernel<false>, nt + (long long)B * NT, mask, table, p.m1, p.m2, p.tmask, p.txy, B, T, NT, (int*)nullptr);
+    if (flags & FLAG_CHECK_MASK)          // the same m1 / m2 / tmask / txy, plus the mask's value classes or-ed into the handle's flag word
+        LAUNCH1D(prepare_kernel<true>, nt + (long long)B * NT, mask, table, p.m1, p.m2, p.tmask, p.txy, B, T, NT, net->flags_dev);
+    else
+        LAUNCH1D(prepare_kernel<false>, nt + (long long)B * NT, mask, table, p.m1, p.m2, p.tmask, p.txy, B, T, NT, (int*)nullptr);
     const float2* rope = net->rope_index;
     const int rope_stride = net->rot_old ? 0 : T;
     if (!net->rot_old) {
@@ -770,7 +774,7 @@ extern "C" int ttup_uplift_loss_grad(ttup_uplift* net, const float* ball_dev, co
                  TTUP_EINVAL, "ttup_uplift_loss_grad: null pointer");
     TTUP_REQUIRE(supported(net), TTUP_EINVAL, "ttup_uplift_loss_grad: gradients are served for connectstage/dynamic only, this handle holds %s", variant_text(net));
     TTUP_REQUIRE(batch > 0 && len > 0 && len <= 255, TTUP_EINVAL, "ttup_uplift_loss_grad: batch %d / sequence length %d outside [1,..] x [1,255]", batch, len);
-    TTUP_REQUIRE((flags & ~FLAG_LOCAL) == 0, TTUP_EINVAL, "ttup_uplift_loss_grad: unknown flag bits %d", flags);
+    TTUP_REQUIRE((flags & ~(FLAG_LOCAL | FLAG_CHECK_MASK)) == 0, TTUP_EINVAL, "ttup_uplift_loss_grad: unknown flag bits %d", flags);
     TTUP_REQUIRE(!(flags & FLAG_LOCAL) || len >= 2, TTUP_EINVAL, "ttup_uplift_loss_grad: transform_mode 'local' needs at least two positions");
     TTUP_REQUIRE(!net->rot_old || len <= net->max_len, TTUP_EINVAL, "ttup_uplift_loss_grad: sequence length %d above the handle's %d", len, net->max_len);
     TTUP_REQUIRE(((size_t)workspace & 15) == 0, TTUP_EINVAL, "ttup_uplift_loss_grad: workspace must be 16-byte aligned");
@@ -784,6 +788,7 @@ extern "C" int ttup_uplift_loss_grad(ttup_uplift* net, const float* ball_dev, co
     Ctx c{(hipStream_t)stream, p.partial};
     TTUP_HIP_CHECK(hipMemsetAsync(grad_dev, 0, (size_t)W.n_floats * sizeof(float), c.st));
     TTUP_HIP_CHECK(hipMemsetAsync(loss_dev, 0, 2 * sizeof(float), c.st));
+    if (flags & FLAG_CHECK_MASK) TTUP_HIP_CHECK(hipMemsetAsync(net->flags_dev, 0, sizeof(int), c.st));
     hipLaunchKernelGGL(mask_sum_kernel, dim3(1), dim3(1024), 0, c.st, mask_dev, (long long)batch * len, p.mask_sum);
     TTUP_LAUNCH_CHECK();
     for (int b0 = 0; b0 < batch; b0 += p.G) {
@@ -791,6 +796,15 @@ extern "C" int ttup_uplift_loss_grad(ttup_uplift* net, const float* ball_dev, co
         GRC(group_pass(net, c, p, W, ball_dev + (size_t)b0 * len * 2, table_dev + (size_t)b0 * net->n_table * 3, mask_dev + (size_t)b0 * len,
                        times_dev + (size_t)b0 * len, r_world_dev + (size_t)b0 * len * 3, rotation_dev + (size_t)b0 * 3, nb, len, flags, loss_dev,
                        rot_dev + (size_t)b0 * 3, pos_dev + (size_t)b0 * len * 3));
+    }
+    if (flags & FLAG_CHECK_MASK) {
+        // as ttup_uplift_forward: the whole batch's mask must hold 0 and 1 and nothing else (mask.min() == 0 and mask.max() == 1,
+        // model.py:541-546; the additive {-1e9, 0} form of the elif branch is not accepted).  The pass is already enqueued when the
+        // answer is known, so a refused call has written its outputs: they hold no defined values.
+        int seen = 0;
+        TTUP_HIP_CHECK(hipMemcpyAsync(&seen, net->flags_dev, sizeof(int), hipMemcpyDeviceToHost, c.st));
+        TTUP_HIP_CHECK(hipStreamSynchronize(c.st));
+        TTUP_REQUIRE(seen == 3, TTUP_EMASK, "wrong format for masks. Should be 0, 1 or -1e9, 0.");
     }
     return TTUP_OK;
 }

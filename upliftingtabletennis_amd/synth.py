@@ -117,6 +117,23 @@ def ragged_uplift_batch(b, t, seed=0, pad=1):
     return ball, table, mask, times
 
 
+def edge_uplift_batch(b, t, seed=0, pad=1):
+    """`ragged_uplift_batch` with the mask forms padding alone never gives (b >= 3): trajectory 0 has interior holes (every fifth
+    step from 2) and a table with no visible keypoint, trajectory 1 a single valid step, trajectory 2 a table with one visible
+    keypoint, trajectory 3 (if present) is padded throughout.  Ball coordinates and times at the holes keep their values: a masked
+    slot must be inert whatever it holds."""
+    if b < 3:
+        raise ValueError('edge_uplift_batch needs at least three trajectories')
+    ball, table, mask, times = ragged_uplift_batch(b, t, seed=seed, pad=pad)
+    mask[0, 2:t:5] = 0
+    table[0, :, 2] = 0
+    mask[1, 1:] = 0
+    table[2, :, 2] = 0; table[2, 6, 2] = 1
+    if b > 3:
+        mask[3, :] = 0
+    return ball, table, mask, times
+
+
 def uplift_targets(b, length, seed=0):
     """Seeded training targets for an uplift batch of `b` trajectories of padded length `length`: r_world (b,length,3) ~ N(0,1) and
     rotation (b,3) ~ 50 N(0,1), float32 (the gradient fixtures, tools/make_goldens_uplift_grad.py)."""

@@ -80,14 +80,16 @@ class MultiStageModel:
             raise RuntimeError('the library lays the gradient buffer out differently from arch.uplift_grad_layout')
         return layout, n
 
-    def loss_and_grad(self, ball_pos, table_pos, mask, times, r_world, rotation, transform_mode='global'):
+    def loss_and_grad(self, ball_pos, table_pos, mask, times, r_world, rotation, transform_mode='global', check_mask=True):
         """The reference's training loss (uplifting/train.py:121-127) and `loss.backward()` for one batch.
         ball (B,T,2), table (B,13,3), mask (B,T) in {0,1}, times (B,T), r_world (B,T,3), rotation (B,3) -- the rows `r_img, table_img,
         mask, r_world, rotation, times` of a reference batch (train.py:116) or of dataset.TableTennisDataset.batch, passed by name.
         transform_mode 'local' first takes the target spin through transform_rotationaxes(rotation, r_world) (train.py:123-124).
         -> (loss_rot, loss_pos, grads): two 0-d device tensors and a dict from the reference's parameter names to views into one flat
         device tensor (`grads.flat`; `grad_layout()` has the offsets).  `grads.rot` / `grads.pos` are the forward outputs.
-        Raises ValueError for any variant but connectstage/dynamic before the library is asked."""
+        Raises ValueError for any variant but connectstage/dynamic before the library is asked, and -- as `forward` does, and as the
+        reference's training step does through model.forward (model.py:541-546) -- for a mask that is not {0,1} with both values
+        present.  That check reads one word back and synchronises the stream once; check_mask=False skips both."""
         arch.check_uplift_grad_variant(self.name, self.mode)
         if transform_mode not in ('global', 'local'):
             raise ValueError("transform_mode should be 'global' or 'local'")
@@ -107,7 +109,7 @@ class MultiStageModel:
             rot = torch.empty((b, 3), dtype=torch.float32, device=self.device)
             pos = torch.empty((b, t, 3), dtype=torch.float32, device=self.device)
             rc = self._lib.ttup_uplift_loss_grad(self._handle, _lib.ptr(ball), _lib.ptr(table), _lib.ptr(mask), _lib.ptr(times), _lib.ptr(r_world),
-                                                 _lib.ptr(rotation), b, t, 1 if transform_mode == 'local' else 0, _lib.ptr(ws), nbytes,
+                                                 _lib.ptr(rotation), b, t, (1 if transform_mode == 'local' else 0) | (2 if check_mask else 0), _lib.ptr(ws), nbytes,
                                                  _lib.ptr(flat), _lib.ptr(loss), _lib.ptr(rot), _lib.ptr(pos), _lib.stream_ptr())
         _lib.check(rc)
         grads = Gradients((k, flat[off:off + _numel(shape)].view(shape)) for k, shape, off, _ in layout)
