@@ -1,5 +1,6 @@
 // Library-level entry points: version, error string, device probe.
 #include "common.h"
+#include <stdlib.h>
 #include <map>
 #include <mutex>
 #include <utility>
@@ -24,6 +25,9 @@ void kernel_note(const char* fmt, ...) {
 }
 void kernel_note_reset() { g_kernel[0] = 0; }
 const char* kernel_noted() { return g_kernel; }
+
+bool env_set(const char* name) { return getenv(name) != nullptr; }
+long long env_ll(const char* name, long long unset) { const char* v = getenv(name); return v ? atoll(v) : unset; }
 
 int ensure_max_lds(const void* kernel, size_t bytes) {
     if (bytes <= 64 * 1024) return TTUP_OK;

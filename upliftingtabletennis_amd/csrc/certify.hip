@@ -459,12 +459,12 @@ extern "C" int ttup_wasb_set_certify(ttup_wasb* net, float eps_abs, int crop, in
     cert_free(net);
     c.eps = eps_abs;
     c.small = 0;
-    static const int env_maxc = getenv("TTUP_CERT_MAXC") ? atoi(getenv("TTUP_CERT_MAXC")) : 0, env_list = getenv("TTUP_CERT_LIST") ? atoi(getenv("TTUP_CERT_LIST")) : 0;
+    static const int env_maxc = (int)env_ll("TTUP_CERT_MAXC", 0), env_list = (int)env_ll("TTUP_CERT_LIST", 0);
     c.maxc = max_crops_per_map > 0 ? max_crops_per_map : (env_maxc > 0 && env_maxc <= CERT_MAX_FRAME_CROPS ? env_maxc : 8);
     c.maxf = c.maxc * net->n_out < CERT_MAX_FRAME_CROPS ? c.maxc * net->n_out : CERT_MAX_FRAME_CROPS;      // the channels of a frame share its crops
     // Crop side: 2 R + the core.  The origin of a crop is a multiple of 8 (the 1/8-resolution branch), so a crop centred on a candidate
     // has it within 4 pixels of its centre: the core must hold 8 positions + the 3x3 window = 2 R + 16 at least.
-    static const int env_crop = getenv("TTUP_CERT_CROP") ? atoi(getenv("TTUP_CERT_CROP")) : 0;          // experiment knob, read once
+    static const int env_crop = (int)env_ll("TTUP_CERT_CROP", 0);          // experiment knob, read once
     int side = crop > 0 ? crop : (env_crop > 0 ? env_crop : 168);
     TTUP_REQUIRE(side % 8 == 0 && side >= 2 * c.R + 16, TTUP_EINVAL, "ttup_wasb_set_certify: crop %d must be a multiple of 8 and at least %d", side, 2 * c.R + 16);
     c.Hc = side < net->H ? side : net->H;
@@ -472,7 +472,7 @@ extern "C" int ttup_wasb_set_certify(ttup_wasb* net, float eps_abs, int crop, in
     // the scan reads float4 quads of whole heatmaps; a crop is exact only when its (clamped) origin is a multiple of 8
     TTUP_REQUIRE(((long long)net->H * net->W) % 4 == 0 && (net->H - c.Hc) % 8 == 0 && (net->W - c.Wc) % 8 == 0, TTUP_EINVAL,
                  "ttup_wasb_set_certify: %dx%d heatmaps with %dx%d crops cannot be certified (H*W %% 4, (H-Hc) %% 8, (W-Wc) %% 8 must be 0)", net->H, net->W, c.Hc, c.Wc);
-    static const int env_ch = getenv("TTUP_CERT_CH") ? atoi(getenv("TTUP_CERT_CH")) : 0;          // crops per fp32 pass (experiment knob, read once)
+    static const int env_ch = (int)env_ll("TTUP_CERT_CH", 0);          // crops per fp32 pass (experiment knob, read once)
     const int ch_cap = env_ch >= 8 && env_ch <= 512 ? env_ch : 128;          // 128 against 64: varied content +1.7 %, parity mode and noise weights +1.1 % (fewer, fuller passes; round 6)
     c.CH = net->max_batch < ch_cap ? net->max_batch : ch_cap;
     const int per_map = env_list > 0 && env_list <= 16 ? env_list : 4;
@@ -516,11 +516,11 @@ extern "C" int ttup_wasb_set_certify(ttup_wasb* net, float eps_abs, int crop, in
     if (rc) { cert_free(net); return rc; }
     // cone pruning of the crop net: an interior crop's candidates lie R + 1 pixels inside it, their 3x3 windows one more: only the
     // heatmap rows / columns [R, side - R) are ever read (lookup kernel), and every layer only has to produce what those depend on
-    static const bool no_cone = getenv("TTUP_NO_CONE") != nullptr || getenv("TTUP_F32_EXACT") != nullptr || getenv("TTUP_F32_DIRECT") != nullptr;
+    static const bool no_cone = env_set("TTUP_NO_CONE") || env_set("TTUP_F32_EXACT") || env_set("TTUP_F32_DIRECT");
     if (!no_cone && c.Hc == c.Wc && c.Hc > 2 * c.R + 2 && c.Hc < net->H && c.Wc < net->W) {
         // class 2: a 16-pixel heatmap region (14 candidate positions + their 3x3 windows) at the crop's corner-aligned end of the core
         // range -- its cone is the crop's first 160 rows / columns, i.e. one 16-pixel tile row / column less in the full-resolution layers
-        static const bool no_small = getenv("TTUP_CERT_SMALL") != nullptr && atoi(getenv("TTUP_CERT_SMALL")) == 0;
+        static const bool no_small = env_ll("TTUP_CERT_SMALL", 1) == 0;
         c.small = (!no_small && c.Hc >= 2 * c.R + 24) ? 14 : 0;
         const int rc2 = compute_roi(c.cropnet, c.R, c.Hc - c.R, c.R, c.small ? c.R + c.small + 2 : c.R);
         if (rc2) { cert_free(net); return rc2; }

@@ -1,8 +1,8 @@
 // The 16-channel two-block chain of the full-resolution branch, round-6 form: four 3x3 convs 16 -> 16 (two BasicBlocks,
 // balldetection/models/wasb.py:48-64) per 24x32 output tile with every intermediate in LDS, and the fuse-layer sum that consumes the
 // branch (wasb.py:227-245) -- or, in stage 4, the 1x1 head + argmax partial (wasb.py:484, 606) -- in the last conv's epilogue.
-// Included by conv.hip (uses its BBArgs / BBFrag16 / pack2 / relu_pk / bb_key helpers).  Same tiling, LDS images, k-step order and
-// rounding points as bb_chain2_kernel (csrc/conv.hip: the run-time-epilogue fallback and cross-check); what changed, from the round-5
+// Uses conv_bb.h's BBArgs / BBFrag16 / bb_key helpers and conv_dev.h's pack2 / relu_pk.  Same tiling, LDS images, k-step order and
+// rounding points as bb_chain2_kernel (csrc/conv_bb.h: the run-time-epilogue fallback and cross-check); what changed, from the round-5
 // counters (VALU 4.3-5.7 per MFMA, SQ_LDS_BANK_CONFLICT 17 % of the LDS cycles, phase stamps: staging 4.4 k + conv4 6.3 k of 24 k cycles):
 //   * conv1-3 store TWO 16-pixel groups per ds_write_b128: v_permlane16_swap turns (group A, group B) x (couts 4g..4g+3) into
 //     (pixel of A | pixel of B) x (8-channel chunk), 8 consecutive lanes then cover 8 different 16-byte bank groups -- the 2-way conflict
@@ -16,6 +16,9 @@
 //   * the first conv's weight fragments and the identity fragment (a 1-KB table instead of ~35 instructions) are requested before
 //     the tile, so that they arrive with it instead of costing a second memory round trip behind the first barrier.
 #pragma once
+#include "conv_bb.h"
+
+namespace ttup {
 
 struct C16IdmTab {
     unsigned short v[64 * 8];
@@ -478,12 +481,8 @@ static int launch_c16_t(const BBArgs& a, int batch, int h, int w, hipStream_t st
     constexpr int SA = ((TW + 8) & 1) ? TW + 8 : TW + 9, SB = ((TW + 6) & 1) ? TW + 6 : TW + 7;       // odd row strides, as in the kernel
     constexpr size_t SMEM = (size_t)((TH + 8) * SA + (TH + 6) * SB) * C16_PB + 64;       // + one argmax slot per wave
     static_assert(2 * SMEM <= 160 * 1024, "two workgroups per CU");
-    if (int rc = ensure_max_lds((const void*)c16_chain_kernel<TH, TW, MODE>, SMEM)) return rc;
-    BBArgs k = a;
-    k.H = h; k.W = w; k.tiles_x = cdiv(w, TW); k.tiles_per_img = k.tiles_x * cdiv(h, TH); k.total_tiles = k.tiles_per_img * batch;
-    if (k.total_tiles == 0) return TTUP_OK;
-    kernel_note("c16_chain_kernel<%d, %d, %d>", TH, TW, MODE);
-    hipLaunchKernelGGL((c16_chain_kernel<TH, TW, MODE>), dim3(k.tiles_x, cdiv(h, TH), batch), dim3(512), SMEM, st, k);
-    TTUP_LAUNCH_CHECK();
-    return TTUP_OK;
+    const BBArgs k = bb_tiled<TH, TW>(a, batch, h, w);
+    return launch_noted(c16_chain_kernel<TH, TW, MODE>, dim3(k.tiles_x, cdiv(h, TH), batch), 512, SMEM, st, k, "c16_chain_kernel<%d, %d, %d>", TH, TW, MODE);
 }
+
+}  // namespace ttup

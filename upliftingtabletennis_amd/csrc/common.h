@@ -85,6 +85,11 @@ __host__ __device__ inline bf16_t f32_to_bf16(float f) {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// The only two places of the library that ask the environment (api.hip).  A call site decides WHEN its knob is sampled: a function-local
+// static for "once per process, on the first visit", a plain call at handle creation for the knobs a handle samples for itself.
+bool env_set(const char* name);                                // the variable exists (whatever its value)
+long long env_ll(const char* name, long long unset);           // its integer value, `unset` when it does not exist
+
 // Per-device one-time setup (api.hip).  Kernels that need more than 64 KB of dynamic LDS must have
 // hipFuncAttributeMaxDynamicSharedMemorySize raised on EVERY device they are launched on, and handles may live on any
 // device of the process: both helpers key their state by hipGetDevice() under a mutex (no process-global flags).

@@ -75,18 +75,18 @@ bool conv_x3_supported(const PackedConv& p);
 int launch_conv_x3(const PackedConv& p, const ConvLaunch& l, hipStream_t stream);
 int pack_conv_x3(const std::vector<float>& w_tap_cin_cout, int cout, int cin_total, int c0, int k, int stride, PackedConv* out);
 
-// fused stem: conv1 + conv2 + Bottleneck conv1, bf16 only, persistent with all weights resident in LDS (csrc/conv.hip)
+// fused stem: conv1 + conv2 + Bottleneck conv1, bf16 only, persistent with all weights resident in LDS (csrc/conv_stem.h)
 // frames_per_sample = 0: x0 is the (B,H,W,16) input tensor; 1 / 3: x0 is the per-frame pre-processed clip (B+nf-1,H,W,4) and p1 is
 // packed in the slot order f*4 + c (see stem_kernel)
 int launch_stem(const PackedConv& p1, const PackedConv& p2, const PackedConv& p3, const void* x0, void* t2, void* a1,
                 int batch, int h, int w, hipStream_t st, int frames_per_sample = 0);
 #define TTUP_LAYOUT_NHWC4_FRAME 2      // internal: launch_preprocess output = one bf16 (c0,c1,c2,0) record per frame pixel
 
-// fused Bottleneck tail (conv3 + downsample + add + relu) + both transition1 convs, bf16 only (csrc/conv.hip)
+// fused Bottleneck tail (conv3 + downsample + add + relu) + both transition1 convs, bf16 only (csrc/conv_bneck.h)
 int launch_bneck_trans(const PackedConv& p1, const PackedConv& p5, const PackedConv& p6, const void* a2, const void* t2,
                        void* b0, void* b1, int batch, int h, int w, hipStream_t st);
 
-// fused chain of 1 or 2 BasicBlocks (2 or 4 3x3 convs, C = 16 or 32) of one branch, bf16 only (csrc/conv.hip).
+// fused chain of 1 or 2 BasicBlocks (2 or 4 3x3 convs, C = 16 or 32) of one branch, bf16 only (csrc/conv_bb.h, csrc/chain16.h).
 // BBSum (16-channel two-block chain only): the fuse-layer sum that consumes the branch, computed in the epilogue of the last
 // conv -- ysum = relu(y + sum_k up(terms[k], 2^shifts[k])); with `heat` set the sum is not stored: the 1x1 head and the
 // per-tile argmax partial (pv / pi [map * bb_chain_tiles_per_img + tile]) are computed from it in registers, and y may be null.

@@ -1,7 +1,7 @@
 // fp32 convolution on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32: exact fp32 products, one rounding per product, a
 // k-ordered fma chain) -- the arithmetic of the parity path (TTUP_DTYPE_F32) and of the certified-argmax re-evaluation
 // (csrc/certify.hip), 6-8x faster than the one-thread-per-output direct kernel it replaces (conv_direct_f32_kernel, kept in
-// conv.hip and selectable with TTUP_F32_DIRECT=1 as a cross-check).
+// conv_pointwise.h and selectable with TTUP_F32_DIRECT=1 as a cross-check).
 // Reference: the conv / BN(folded) / ReLU / residual call sites of balldetection/models/wasb.py:48-64, :85-105, :227-245, :446-451.
 //
 // GEMM view per output tile (8 rows x 16 columns):  D[cout][px] = sum_{chunk, tap, c} W[tap][c][cout] * X[c][px(tap)]
@@ -12,10 +12,9 @@
 // Persistent workgroups walk the tiles; `n_active` (device memory, optional) overrides the batch so that a launch sized
 // for the largest batch does only the work that a previous kernel decided on (no host synchronisation).
 #include "conv.h"
+#include "conv_dev.h"
 
 namespace ttup {
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 struct ConvF32Args {
     const float* src0; const float* src1; const float* w; const float* bias; const float* residual; float* dst;

@@ -10,23 +10,18 @@
 // TTUP_F32_EXACT=1 selects the fp32-MFMA kernel instead (cross-check).
 // Reference: the conv / BN(folded) / ReLU / residual call sites of balldetection/models/wasb.py:48-64, :85-105, :227-245, :446-451.
 //
-// Structure = the bf16 implicit-GEMM kernel of csrc/conv.hip (persistent workgroups walk (tile, channel chunk) items, the next item's
+// Structure = the bf16 implicit-GEMM kernel of csrc/conv_mfma.h (persistent workgroups walk (tile, channel chunk) items, the next item's
 // global loads are issued before the MFMA loop of the current one): fp32 NHWC activations in, split while they are written to the
 // LDS halo tile (three bf16 planes, pixel-major, the chunk swizzle of lds_off), weights split on the host and packed per MFMA
 // fragment in three planes; fp32 NHWC out (+bias, +residual, ReLU).  Couts are processed in blocks of MT*16 (grid.y).
 // The k order per output pixel (chunk, k-step, the MFMA's own order) does not depend on the tile or on the image size: a pixel
 // computed on a crop equals the pixel computed on the whole frame bit for bit (what the certified argmax relies on).
 #include "conv.h"
+#include "conv_dev.h"
 #include <stdlib.h>
 #include <vector>
 
 namespace ttup {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 struct ConvX3Args {
     const float* src0; const float* src1; const bf16_t* wpack; const float* bias; const float* residual; float* dst;
@@ -50,11 +45,7 @@ __device__ __forceinline__ float x3_sub(float a, float b) {
     return r;
 }
 
-// two fp32 -> packed bf16 pair, round-to-nearest-even (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned x3_pack2(float a, float b) {
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
-// the same chunk swizzle as lds_off in csrc/conv.hip (CK = 32: 16-byte chunk index XOR bits 1..2 of the tile column)
+// the same chunk swizzle as lds_off in csrc/conv_dev.h (CK = 32: 16-byte chunk index XOR bits 1..2 of the tile column)
 template <int CK, int IW>
 __device__ __forceinline__ int x3_off(int iy, int ix, int c8) {
     if (CK == 32) return ((iy * IW + ix) * 4 + (c8 ^ ((ix >> 1) & 3))) * 8;
@@ -66,11 +57,11 @@ __device__ __forceinline__ void x3_split8(const f32x4& lo, const f32x4& hi, u32x
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const float a = v[2 * i], b = v[2 * i + 1];
-        const unsigned q0 = x3_pack2(a, b);
+        const unsigned q0 = pack2(a, b);
         const float ra = x3_sub(a, __uint_as_float(q0 << 16)), rb = x3_sub(b, __uint_as_float(q0 & 0xffff0000u));
-        const unsigned q1 = x3_pack2(ra, rb);
+        const unsigned q1 = pack2(ra, rb);
         const float sa = x3_sub(ra, __uint_as_float(q1 << 16)), sb = x3_sub(rb, __uint_as_float(q1 & 0xffff0000u));
-        p0[i] = q0; p1[i] = q1; p2[i] = x3_pack2(sa, sb);
+        p0[i] = q0; p1[i] = q1; p2[i] = pack2(sa, sb);
     }
 }
 
@@ -198,7 +189,7 @@ __global__ __launch_bounds__(NW * 64) void conv_x3_kernel(ConvX3Args a) {
     issue(item);
     // every path into the item loop has the prefetch registers complete; inside the loop they are waited for right behind the MFMA loop,
     // in front of the epilogue's stores (at the top of the next item, behind the stores, the wait would be an s_waitcnt vmcnt(0) that
-    // drains them too: csrc/conv.hip prefetch_arrived)
+    // drains them too: csrc/conv_dev.h prefetch_arrived)
     auto arrived = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int k = 0; k < IN_PT; ++k) asm volatile("" :: "v"(pin[k][0]), "v"(pin[k][1]));
@@ -247,7 +238,7 @@ __global__ __launch_bounds__(NW * 64) void conv_x3_kernel(ConvX3Args a) {
 #pragma unroll
                     for (int m = 0; m < MT; ++m) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[PA[q]][m], bfr[PB[q]][t], acc[m][t], 0, 0, 0);
         };
-        // (not pipelined like conv64_tile_mfma in csrc/conv.hip, measured round 5 on full frames and 256 / 384-pixel crops: 2-3 % SLOWER
+        // (not pipelined like conv64_tile_mfma in csrc/conv64.h, measured round 5 on full frames and 256 / 384-pixel crops: 2-3 % SLOWER
         // here, 3.50 against 3.39 ms per frame -- it costs the 16-channel kernels an occupancy step, 116 -> 132 registers: one workgroup
         // per CU instead of two)
 #pragma unroll

@@ -2,14 +2,10 @@
 // streaming HBM kernels, timed with HIP events on the caller's stream.  Measurement aids, not part of the hot path; the reference
 // has no counterpart.  Random operands on purpose: the chip holds a lower clock on random data than on zeros
 // (MI355X_MICROARCH.md, DVFS give-back), and that clock is the one the convolutions get.
-#include "common.h"
+#include "conv_dev.h"
 
 namespace ttup {
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 // 16 independent accumulator chains of v_mfma_f32_16x16x32_bf16 per wave, operands in registers
 __global__ __launch_bounds__(256) void mfma16_loop_kernel(const uint4* __restrict__ seed, float* __restrict__ sink, int iters) {

@@ -1621,11 +1621,9 @@ __global__ __launch_bounds__(256) void embed3_cls_kernel(const float* __restrict
 
 namespace {
 
-// The environment switches (README, "knobs"), all read together, once per process, on the first use of any of them.  env_set() and
-// env_ll() are the only places that ask the environment: TTUP_UPLIFT_NO_GRAPH is sampled through env_set() at every handle
-// creation, TTUP_DEBUG where its message is printed.
-bool env_set(const char* name) { return getenv(name) != nullptr; }
-long long env_ll(const char* name, long long unset) { const char* v = getenv(name); return v ? atoll(v) : unset; }
+// The environment switches (README, "knobs"), all read together, once per process, on the first use of any of them, through
+// env_set() / env_ll() (common.h); TTUP_UPLIFT_NO_GRAPH is sampled through env_set() at every handle creation, TTUP_DEBUG where its
+// message is printed.
 struct Switches {
     bool f32_exact = env_set("TTUP_F32_EXACT");                          // fp32-MFMA kernels throughout, scalar attention
     bool unfused = env_set("TTUP_UPLIFT_UNFUSED");                       // one launch per linear layer

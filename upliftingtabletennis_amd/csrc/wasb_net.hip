@@ -92,9 +92,21 @@ int parse_blob(const void* blob, size_t bytes, std::vector<FoldedConv>* out, int
     return TTUP_OK;
 }
 
+// The graph switches (README, "knobs"): every net samples them for itself, all together, when its builder is set up -- the tests set
+// them in-process between two handles (never static).
+struct GraphSwitches {
+    bool fuse = !env_set("TTUP_NO_FUSE");                      // any fused kernel at all (bf16 nets)
+    bool fuse_sum = !env_set("TTUP_NO_FUSE_SUM");              // the fuse-layer sum / the head in the 16-channel chain's epilogue
+    bool fuse_lin = !env_set("TTUP_NO_FUSE_LIN");              // the 64 -> 16 / 64 -> 32 fuse convs in conv64's epilogue
+    bool pair = !env_set("TTUP_NO_PAIR");                      // the two stride-2 convs of stage 3's fuse layer in one pass
+    bool stem = !env_set("TTUP_NO_STEM");                      // the fused stem
+    bool frames_mode = !env_set("TTUP_NO_FRAMES_MODE");        // the stem reads per-frame records
+};
+
 struct Builder {
     ttup_wasb* net;
     const std::vector<FoldedConv>* folded;
+    const GraphSwitches sw{};          // read here, once per net
     size_t cursor = 0;     // next folded conv in reference order
     int rc = TTUP_OK;
 
@@ -149,10 +161,10 @@ struct Builder {
     // HighResolutionModule (wasb.py:227-245); returns fused outputs 0..n_out-1
     std::vector<int> stage(std::vector<int> xs, int n_out, bool head_mode = false) {
         const int nb = (int)xs.size();
-        const bool fuse = net->dtype == TTUP_DTYPE_BF16 && !getenv("TTUP_NO_FUSE");
+        const bool fuse = net->dtype == TTUP_DTYPE_BF16 && sw.fuse;
         // the full-resolution branch's fuse-layer sum rides in the epilogue of its two-block chain, which is therefore emitted
         // AFTER the lower branches and their 1x1 fuse convs (deferred below); its weights are still consumed in reference order
-        const bool fuse_sum = fuse && !getenv("TTUP_NO_FUSE_SUM") && net->tensors[xs[0]].c == 16;
+        const bool fuse_sum = fuse && sw.fuse_sum && net->tensors[xs[0]].c == 16;
         Op deferred; bool has_deferred = false;
         const int x0_in = xs[0];
         for (int b = 0; b < nb; ++b) {
@@ -211,7 +223,7 @@ struct Builder {
                         }
                     }
                     // 64 -> 16 / 64 -> 32 on the output of the branch's last 64 -> 64 conv: rides in that conv's epilogue
-                    if (!attached && fuse && sj.c == 64 && (STAGE_CH[i] == 16 || STAGE_CH[i] == 32) && !getenv("TTUP_NO_FUSE_LIN")) {
+                    if (!attached && fuse && sj.c == 64 && (STAGE_CH[i] == 16 || STAGE_CH[i] == 32) && sw.fuse_lin) {
                         for (int k = (int)net->ops.size() - 1; k >= 0 && !attached; --k) {
                             Op& po = net->ops[k];
                             if (po.dst != xs[j]) continue;
@@ -239,7 +251,7 @@ struct Builder {
                         // 16 -> 16 on the full-resolution branch while an earlier fuse chain took the same tensor down 16 -> 32: both
                         // convs in one pass over it (conv_s2_pair_kernel)
                         bool paired = false;
-                        if (fuse && !last && f.cout == 16 && sc.c == 16 && !getenv("TTUP_NO_PAIR")) {
+                        if (fuse && !last && f.cout == 16 && sc.c == 16 && sw.pair) {
                             for (int q = (int)net->ops.size() - 1; q >= 0 && !paired; --q) {
                                 Op& po = net->ops[q];
                                 if (po.kind != Op::CONV || po.src0 != cur || po.conv < 0) continue;
@@ -307,9 +319,9 @@ int build(ttup_wasb* net, const std::vector<FoldedConv>& folded) {
     net->t_input = b.new_tensor(16, H, W);
     // stem (wasb.py:446-451)
     int x;
-    const bool fuse_c1 = net->dtype == TTUP_DTYPE_BF16 && !getenv("TTUP_NO_FUSE");
+    const bool fuse_c1 = net->dtype == TTUP_DTYPE_BF16 && b.sw.fuse;
     int stem_a1 = -1;
-    if (fuse_c1 && !getenv("TTUP_NO_STEM")) {
+    if (fuse_c1 && b.sw.stem) {
         // conv1 + conv2 + Bottleneck conv1 in one persistent kernel; the first 64-channel tensor never reaches HBM
         const FoldedConv& c1 = b.next(64, net->in_ch, 3, 1);
         const int p1 = b.pack(c1, nullptr, 16);
@@ -321,7 +333,7 @@ int build(ttup_wasb* net, const std::vector<FoldedConv>& folded) {
             for (int ci = 0; ci < net->in_ch; ++ci)
                 for (int t = 0; t < 9; ++t) c1f.w[((size_t)co * 16 + (ci / 3) * 4 + ci % 3) * 9 + t] = c1.w[((size_t)co * net->in_ch + ci) * 9 + t];
         int p1f = b.pack(c1f, nullptr, 16);
-        // ... and, for triples, the 4-k-step form of that conv (csrc/conv.hip stem_kernel<3, true>): K = 3 tap rows x 40 slots, slot
+        // ... and, for triples, the 4-k-step form of that conv (csrc/conv_stem.h stem_kernel<3, true>): K = 3 tap rows x 40 slots, slot
         // o of a row = pixel dx = o / 12, frame (o % 12) / 4, colour o % 4 (colour 3 and o >= 36: zero weights), packed as a
         // "1x1 conv with 128 inputs" so that k-step s, lane group g, element j holds k = 32 s + 8 g + j
         if (net->in_ch == 9) {
@@ -342,7 +354,7 @@ int build(ttup_wasb* net, const std::vector<FoldedConv>& folded) {
         Op op; op.kind = Op::STEM; op.conv = p1; op.conv2 = p2; op.conv3 = p3; op.src0 = net->t_input; op.dst = x; op.dst2 = stem_a1;
         op.conv1f = p1f;
         net->ops.push_back(op);
-        if (!getenv("TTUP_NO_FRAMES_MODE")) {
+        if (b.sw.frames_mode) {
             // (micro + nf - 1) frames of (H, W, 4) bf16: allocated through the tensor list so that every lane gets its own copy
             Tensor t; t.c = 4; t.h = H; t.w = W; t.extra = net->in_ch / 3 - 1;
             const size_t bytes = (size_t)(net->micro + net->in_ch / 3 - 1) * H * W * 4 * 2;
@@ -376,7 +388,7 @@ int build(ttup_wasb* net, const std::vector<FoldedConv>& folded) {
         const FoldedConv& c3 = b.next(128, 32, 1, 1);
         const FoldedConv& ds = b.next(128, 64, 1, 1);
         const int pc = b.pack(c3, &ds, 0);
-        const bool fuse = net->dtype == TTUP_DTYPE_BF16 && !getenv("TTUP_NO_FUSE") && H % 2 == 0 && W % 2 == 0;
+        const bool fuse = net->dtype == TTUP_DTYPE_BF16 && b.sw.fuse && H % 2 == 0 && W % 2 == 0;
         if (fuse) {
             const int p5 = b.pack(b.next(16, 128, 3, 1), nullptr, 0);
             const int p6 = b.pack(b.next(32, 128, 3, 2), nullptr, 0);
@@ -400,12 +412,12 @@ int build(ttup_wasb* net, const std::vector<FoldedConv>& folded) {
     ys = b.stage(xs, 3);
     net->taps["stage3_0"] = ys[0]; net->taps["stage3_1"] = ys[1]; net->taps["stage3_2"] = ys[2];
     xs = {ys[0], ys[1], ys[2], b.conv(ys[2], 128, 3, 2, 1)};
-    const bool head_in_chain = net->dtype == TTUP_DTYPE_BF16 && net->n_out == 1 && !getenv("TTUP_NO_FUSE") && !getenv("TTUP_NO_FUSE_SUM");
+    const bool head_in_chain = net->dtype == TTUP_DTYPE_BF16 && net->n_out == 1 && b.sw.fuse && b.sw.fuse_sum;
     ys = b.stage(xs, 1, head_in_chain);
     net->t_out = ys[0];
     if (head_in_chain && net->ops.back().kind == Op::BB_CHAIN && net->ops.back().head) {
         net->fused_head = true;                       // stage-4 output 0 lives only in the registers of the last block chain
-    } else if (net->dtype == TTUP_DTYPE_BF16 && net->n_out == 1 && !getenv("TTUP_NO_FUSE") && net->ops.back().kind == Op::UPSUM && net->ops.back().dst == ys[0]) {
+    } else if (net->dtype == TTUP_DTYPE_BF16 && net->n_out == 1 && b.sw.fuse && net->ops.back().kind == Op::UPSUM && net->ops.back().dst == ys[0]) {
         net->ops.back().kind = Op::UPSUM_HEAD;        // stage-4 output 0 is consumed in registers and never stored
         net->fused_head = true;
     } else {
@@ -644,7 +656,7 @@ int compute_roi(ttup_wasb* net, int lo, int hi, int lo2, int hi2) {
         o.y0 = r1[k].y0; o.y1 = r1[k].y1; o.x0 = r1[k].x0; o.x1 = r1[k].x1;
         if (two) { o.sy0 = r2[k].y0; o.sy1 = r2[k].y1; o.sx0 = r2[k].x0; o.sx1 = r2[k].x1; }
     }
-    if (getenv("TTUP_DEBUG_ROI")) {
+    if (env_set("TTUP_DEBUG_ROI")) {
         double full = 0, kept = 0, kept2 = 0;
         for (size_t k = 0; k < net->ops.size(); ++k) {
             const Op& op = net->ops[k];
@@ -688,8 +700,7 @@ int ttup_wasb_create_internal(const void* blob, size_t blob_bytes, int height, i
     net->blob.assign((const char*)blob, (const char*)blob + blob_bytes);
     net->n_out = head_out == 3 ? 1 : head_out;       // ball detector keeps the middle of its 3 channels (wasb.py:606)
     // micro-batch: enough tiles to fill 256 CUs, small enough that layer outputs stay cache-friendly
-    const char* env = getenv("TTUP_MICRO_BATCH");
-    int micro = micro_override > 0 ? micro_override : (env ? atoi(env) : 8);
+    int micro = micro_override > 0 ? micro_override : (int)env_ll("TTUP_MICRO_BATCH", 8);
     if (micro < 1) micro = 1;
     net->micro = micro < max_batch ? micro : max_batch;
     rc = build(net.get(), folded);
@@ -708,8 +719,7 @@ int ttup_wasb_create_internal(const void* blob, size_t blob_bytes, int height, i
     net->refine_ws_bytes = ttup_refine_workspace_bytes(net->micro * net->n_out, height, width);
     if (upsum_head_ws_bytes(net->micro, height, width) > net->refine_ws_bytes) net->refine_ws_bytes = upsum_head_ws_bytes(net->micro, height, width);
     {
-        const char* le = getenv("TTUP_LANES");
-        int n_lanes = lanes_override > 0 ? lanes_override : (le ? atoi(le) : 2);
+        int n_lanes = lanes_override > 0 ? lanes_override : (int)env_ll("TTUP_LANES", 2);
         const int n_micro = (max_batch + net->micro - 1) / net->micro;
         if (n_lanes > n_micro) n_lanes = n_micro;
         if (n_lanes < 1) n_lanes = 1;
@@ -739,10 +749,10 @@ int ttup_wasb_create_internal(const void* blob, size_t blob_bytes, int height, i
     // measurement aid (tools/ops_report_f32.py): TTUP_DEBUG_FORCE_ROI=1 prunes EVERY sample of an fp32 handle to the cone of its central
     // 24-pixel core, as the certified argmax's crop net does for interior crops -- per-op timings of the pruned graph (the flags leak
     // with the process: a debugging switch)
-    if (dtype == TTUP_DTYPE_F32 && getenv("TTUP_DEBUG_FORCE_ROI") && net->H == net->W && net->H >= 2 * 72 + 24) {
+    if (dtype == TTUP_DTYPE_F32 && env_set("TTUP_DEBUG_FORCE_ROI") && net->H == net->W && net->H >= 2 * 72 + 24) {
         int* flags = nullptr;
         TTUP_HIP_CHECK(hipMalloc((void**)&flags, (size_t)max_batch * sizeof(int)));
-        std::vector<int> ones((size_t)max_batch, atoi(getenv("TTUP_DEBUG_FORCE_ROI")) == 2 ? 2 : 1);          // = 2: the class-2 regions (16-pixel core)
+        std::vector<int> ones((size_t)max_batch, env_ll("TTUP_DEBUG_FORCE_ROI", 0) == 2 ? 2 : 1);          // = 2: the class-2 regions (16-pixel core)
         TTUP_HIP_CHECK(hipMemcpy(flags, ones.data(), ones.size() * sizeof(int), hipMemcpyHostToDevice));
         if (int rc = compute_roi(net.get(), 72, net->H - 72, 72, 88)) return rc;
         net->roi_flag = flags;
