@@ -757,7 +757,7 @@ def test_single_lane_handle_equals_the_two_lane_handle():
 def test_hub_table_detector_keypoint_indices_equal_the_fp32_path_on_a_64_frame_soak():
     """VERDICT r3 #6 done-criterion: the hub surface's table keypoints come from the certified argmax.  `TableDetector('hrnet')`
     (seeded stand-in weights with a planted path to every head) on 64 frames of changing content, through the path
-    `predict_keypoints` takes (`_calibrate` + `_certified_peaks`, audits on): all 64 x 13 argmax indices equal the full-frame fp32
+    `predict_keypoints` takes (`calibrate` + `_certified_peaks`, audits on): all 64 x 13 argmax indices equal the full-frame fp32
     path's, and the keypoints `predict_keypoints` returns are the table-variant fit of those peaks."""
     from upliftingtabletennis_amd.interface import TableDetector
     det = TableDetector('hrnet', max_batch=16)

@@ -4,6 +4,7 @@
   bit for bit, and its argument checks;
 * `TableTennisPipeline(ball_aux='vitpose', table_aux='vitpose')`: the overlapped clip path against the detectors' own clip calls
   and the reference's filters (oracle/glue_ref.py) composed on them, and against the serial path;
+* the default `TableTennisPipeline()`: the same two comparisons at clip lengths around the chunk boundaries;
 * the constructor surface (`TableTennisPipeline(ball_aux=, table_aux=)`, `hubconf.full_pipeline_two_detectors`)."""
 import os
 import warnings
@@ -110,20 +111,29 @@ def test_forward_frames_rejections(nets, clips):
 
 # ---------------------------------------------------------------- the two-detector pipeline
 
-@pytest.fixture(scope='module')
-def pipe():
+def _synthetic_pipeline(**kw):
     old = os.environ.get('TTUP_SYNTHETIC_WEIGHTS')
     os.environ['TTUP_SYNTHETIC_WEIGHTS'] = '1'
     try:
         from upliftingtabletennis_amd.interface import TableTennisPipeline
         with warnings.catch_warnings():
             warnings.simplefilter('ignore')
-            yield TableTennisPipeline(ball_aux='vitpose', table_aux='vitpose')
+            yield TableTennisPipeline(**kw)
     finally:
         if old is None:
             os.environ.pop('TTUP_SYNTHETIC_WEIGHTS', None)
         else:
             os.environ['TTUP_SYNTHETIC_WEIGHTS'] = old
+
+
+@pytest.fixture(scope='module')
+def pipe():
+    yield from _synthetic_pipeline(ball_aux='vitpose', table_aux='vitpose')
+
+
+@pytest.fixture(scope='module')
+def default_pipe():
+    yield from _synthetic_pipeline()
 
 
 def _predict_or_error(f):
@@ -188,6 +198,26 @@ def test_two_detector_pipeline_matches_its_composition(pipe, n_frames, monkeypat
     serial = _predict_or_error(lambda: pipe.predict(images, fps))
     print('predict: %s' % ('ValueError in all three' if isinstance(expect[0], str) else '%d positions' % expect[1].shape[0]))
     assert _same_result(got, expect) and _same_result(serial, expect)
+
+
+@pytest.mark.parametrize('n', [3, 25, 96])
+def test_default_pipeline_overlapped_path_at_chunk_boundaries(default_pipe, n, monkeypatch):
+    """The default (single-detector) pipeline's overlapped clip path against the detectors' own clip calls and against the serial
+    path (TTUP_HUB_SERIAL=1, read per call), bit for bit: n = 3 is one triple in one chunk; 25 a second chunk of one frame, whose
+    ball call is a single triple straddling the upload boundary; 96 the long-chunk regime with an 8-frame tail."""
+    p = default_pipe
+    assert p.ball_detector_aux is p.ball_detector and p.table_detector_aux is p.table_detector
+    images = [f for f in synth.synth_frames(n, 720, 1280, seed=100 + n)[0]]
+    monkeypatch.delenv('TTUP_HUB_SERIAL', raising=False)
+    pos, kp = p._clip_detections(images, True)
+    assert pos.shape == (n - 2, 3) and kp.shape == (n, 13, 3)
+    assert np.array_equal(pos, p.ball_detector.predict_clip(images))
+    assert np.array_equal(kp, p.table_detector.predict_keypoints(images))
+    overlapped = _predict_or_error(lambda: p.predict(images, 60.0))
+    monkeypatch.setenv('TTUP_HUB_SERIAL', '1')
+    serial = _predict_or_error(lambda: p.predict(images, 60.0))
+    print('\n%d frames: predict %s' % (n, 'raises ValueError in both modes' if isinstance(serial[0], str) else 'gives %d positions' % serial[1].shape[0]))
+    assert _same_result(overlapped, serial)
 
 
 def test_pipeline_aux_surface(monkeypatch):

@@ -15,6 +15,7 @@ Quirks kept on purpose: BGR frames are fed to the detector as they come (interfa
 *table* variant of the refine is used on the hub surface (interface.py:116); visibility is always 1.
 """
 import os
+import time
 
 import numpy as np
 import torch
@@ -35,56 +36,85 @@ def _weights_dir():
     return hub if os.path.isdir(hub) else ''
 
 
-def _synthetic_or_raise(what, path):
-    """No checkpoint: the reference downloads one or raises RuntimeError (interface.py:61,71).  There is no network here,
-    so the same RuntimeError is raised unless TTUP_SYNTHETIC_WEIGHTS=1 explicitly asks for seeded random weights
-    (benchmarks / smoke tests: the outputs are then meaningless as detections)."""
-    if os.environ.get('TTUP_SYNTHETIC_WEIGHTS') == '1':
-        import warnings
-        warnings.warn('upliftingtabletennis_amd: %s runs on SEEDED RANDOM weights (TTUP_SYNTHETIC_WEIGHTS=1); its outputs '
-                      'are not detections' % what, RuntimeWarning, stacklevel=3)
-        return
-    raise RuntimeError('Failed to download weights: %s not found and there is no network; point TTUP_WEIGHTS at a folder laid '
-                       'out like the reference weight archive, or set TTUP_SYNTHETIC_WEIGHTS=1 for seeded random weights' % (path or what))
+def _seed():
+    return int(os.environ.get('TTUP_SEED', '0'))
+
+
+def _find_checkpoint(task, name, what):
+    """-> (state_dict, additional_info) of <weights dir>/<task>/<name>/model.pt, or None when there is no such file and
+    TTUP_SYNTHETIC_WEIGHTS=1 explicitly asks for seeded random weights (benchmarks / smoke tests: the outputs are then meaningless
+    as detections; said in a warning).  Otherwise no checkpoint is an error: the reference downloads one or raises RuntimeError
+    (interface.py:61,71); there is no network here, so the same RuntimeError is raised."""
+    d = _weights_dir()
+    path = os.path.join(d, task, name, 'model.pt')
+    if d and os.path.exists(path):
+        return weights.load_checkpoint_state_dict(path)
+    if os.environ.get('TTUP_SYNTHETIC_WEIGHTS') != '1':
+        raise RuntimeError('Failed to download weights: %s not found and there is no network; point TTUP_WEIGHTS at a folder laid '
+                           'out like the reference weight archive, or set TTUP_SYNTHETIC_WEIGHTS=1 for seeded random weights' % (path if d else what))
+    import warnings
+    warnings.warn('upliftingtabletennis_amd: %s runs on SEEDED RANDOM weights (TTUP_SYNTHETIC_WEIGHTS=1); its outputs '
+                  'are not detections' % what, RuntimeWarning, stacklevel=3)
+    return None
 
 
 def _load_ball_checkpoint(model_name):
     """-> (state_dict, resolution (W,H), in_frames).  Reference: inference_balldetection.load_model :40-61."""
-    path = os.path.join(_weights_dir(), 'inference_balldetection', model_name, 'model.pt')
-    if _weights_dir() and os.path.exists(path):
-        sd, info = weights.load_checkpoint_state_dict(path)
-        default = vitpose.RESOLUTIONS['vitpose'] if model_name == 'vitpose' else wasb.RESOLUTIONS['wasb']
-        return sd, tuple(info.get('image_resolution', default)), int(info.get('in_frames', 3))
-    _synthetic_or_raise("BallDetector('%s')" % model_name, path if _weights_dir() else '')
+    res = vitpose.RESOLUTIONS['vitpose'] if model_name == 'vitpose' else wasb.RESOLUTIONS['wasb']
+    found = _find_checkpoint('inference_balldetection', model_name, "BallDetector('%s')" % model_name)
+    if found is not None:
+        sd, info = found
+        return sd, tuple(info.get('image_resolution', res)), int(info.get('in_frames', 3))
     if model_name == 'vitpose':
-        res = vitpose.RESOLUTIONS['vitpose']
-        return weights.random_vitpose_state_dict(int(os.environ.get('TTUP_SEED', '0')), in_ch=9, out_ch=1, resolution=res), res, 3
-    return weights.random_wasb_state_dict(int(os.environ.get('TTUP_SEED', '0')), planted=True), wasb.RESOLUTIONS['wasb'], 3
+        return weights.random_vitpose_state_dict(_seed(), in_ch=9, out_ch=1, resolution=res), res, 3
+    return weights.random_wasb_state_dict(_seed(), planted=True), res, 3
+
+
+def _load_table_checkpoint(model_name):
+    """-> (state_dict, resolution (W,H)).  Reference: inference_tabledetection.load_model :40-57."""
+    res = vitpose.RESOLUTIONS['vitpose'] if model_name == 'vitpose' else (1280, 704)
+    found = _find_checkpoint('inference_tabledetection', model_name, "TableDetector('%s')" % model_name)
+    if found is not None:
+        return found[0], tuple(found[1].get('image_resolution', res))
+    if model_name == 'vitpose':
+        return weights.random_vitpose_state_dict(_seed() + 1, in_ch=3, out_ch=13, resolution=res), res
+    # seeded stand-in: a planted path to every keypoint head, so the heatmaps are PEAKED like a trained detector's (one dominant
+    # maximum per keypoint map; on pure noise weights every map is a field of near-ties and the certified argmax degrades to the
+    # full-frame fp32 path -- TTUP_TABLE_NOISE_WEIGHTS=1 selects that regime)
+    noise = os.environ.get('TTUP_TABLE_NOISE_WEIGHTS') == '1'
+    return weights.random_wasb_state_dict(_seed() + 1, planted=not noise, in_ch=3, head_out=13, plant_all_heads=not noise), res
 
 
 def _load_uplift_checkpoint():
     """-> (state_dict, size, transform_mode).  Reference: inference_uplifting.load_model :33-58."""
-    path = os.path.join(_weights_dir(), 'inference_uplifting', 'ours', 'model.pt')
-    if _weights_dir() and os.path.exists(path):
-        sd, info = weights.load_checkpoint_state_dict(path)
-        if info.get('name', 'connectstage') != 'connectstage' or info.get('tabletoken_mode', 'dynamic') != 'dynamic':
-            raise ValueError('only connectstage/dynamic uplift checkpoints are supported')
-        if info.get('time_rotation', 'new') != 'new':       # the reference hands this to get_model (inference_uplifting.py:49-52)
-            raise ValueError("only time_rotation='new' uplift checkpoints are supported (got %r)" % info.get('time_rotation'))
-        return sd, info.get('size', 'large'), info.get('transform_mode', 'global')
-    _synthetic_or_raise('UpliftingModel()', path if _weights_dir() else '')
-    return weights.random_uplift_state_dict(int(os.environ.get('TTUP_SEED', '0')), 'large'), 'large', 'global'
+    found = _find_checkpoint('inference_uplifting', 'ours', 'UpliftingModel()')
+    if found is None:
+        return weights.random_uplift_state_dict(_seed(), 'large'), 'large', 'global'
+    sd, info = found
+    if info.get('name', 'connectstage') != 'connectstage' or info.get('tabletoken_mode', 'dynamic') != 'dynamic':
+        raise ValueError('only connectstage/dynamic uplift checkpoints are supported')
+    if info.get('time_rotation', 'new') != 'new':       # the reference hands this to get_model (inference_uplifting.py:49-52)
+        raise ValueError("only time_rotation='new' uplift checkpoints are supported (got %r)" % info.get('time_rotation'))
+    return sd, info.get('size', 'large'), info.get('transform_mode', 'global')
 
 
 class _HubDetector:
-    """What BallDetector and TableDetector share: `cert`, the certified argmax of their bf16 handle -- a wasb.EpsAudit, where the
-    protocol lives: eps measured on the first input, one sample per 256 audited after it; None when certification is off -- and the
-    detector calls that go through it."""
+    """What the four detectors share: the constructor tail, the frame upload, the peak refine and `cert`, the certified argmax of a
+    bf16 handle -- a wasb.EpsAudit, where the protocol lives: eps measured on the first input, one sample per 256 audited after it;
+    None when certification is off or the handle is fp32 (ViTPose) -- with the detector calls that go through it.  `calibrate`,
+    `enqueue`, `audit`, `settle` and `refine_peaks` are what the pipeline's overlapped clip path drives a detector by; each does the
+    right thing with and without `cert`."""
     NO_CERTIFY_ENV = ('TTUP_NO_CERTIFY',)
+    HEAT_DIV = 1            # the heatmaps are model_resolution / HEAT_DIV
+    CLIP_AUX = False        # whether the clip path can run this detector as an aux detector, beside the primaries and with nothing to settle
 
-    def _init_cert(self):
-        off = self.model.dtype != 'bf16' or any(os.environ.get(k) == '1' for k in self.NO_CERTIFY_ENV)
-        self.cert = None if off else wasb.EpsAudit(self.model, every=0 if os.environ.get('TTUP_NO_AUDIT') == '1' else 256, seed=0)
+    def _init_hub(self, model, res, max_batch):
+        self.device = torch.device('cuda')
+        self.resolution = (WIDTH, HEIGHT)
+        self.KEYPOINT_VISIBLE = KEYPOINT_VISIBLE
+        self.model, self.model_resolution, self.max_batch = model, res, max_batch
+        off = model.dtype != 'bf16' or any(os.environ.get(k) == '1' for k in self.NO_CERTIFY_ENV)
+        self.cert = None if off else wasb.EpsAudit(model, every=0 if os.environ.get('TTUP_NO_AUDIT') == '1' else 256, seed=0)
 
     @property
     def AUDIT_EVERY(self):
@@ -95,15 +125,30 @@ class _HubDetector:
     def AUDIT_EVERY(self, every):
         self.cert.every = self.cert.every_fast = int(every)
 
-    def _calibrate(self, frames_u8=None, x=None):
-        """First eps, on the first input this detector sees (a uint8 clip or a float input); a no-op after it."""
+    @property
+    def heat_hw(self):
+        w, h = self.model_resolution
+        return h // self.HEAT_DIV, w // self.HEAT_DIV
+
+    def _upload(self, images):
+        """A list of BGR uint8 HWC frames (a triple, a batch, a stretch of a clip) -> one (N,h,w,3) uint8 device tensor."""
+        return torch.from_numpy(np.stack([np.asarray(i) for i in images])).to(self.device)
+
+    def refine_peaks(self, idx, win):
+        """Peaks -> (len(idx), 3) float64 device positions [x, y, visibility] in 1920x1080 px: 3x3 Gaussian refine around the argmax,
+        table variant (interface.py:113-116), scaled by the heatmap size."""
+        h, w = self.heat_hw
+        return refine.refine_windows_device(idx.reshape(-1), win.reshape(-1, 9), h, w, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
+
+    def calibrate(self, frames_u8=None, x=None):
+        """First eps, on the first input this detector sees (a uint8 clip or a float input); a no-op after it and when uncertified."""
         if self.cert is not None and not self.model.certified:
             self.model.calibrate(frames_u8, n=4 if x is None else 2, exact_windows=os.environ.get('TTUP_EXACT_WINDOWS') == '1', x=x)
 
     def _certified_forward(self, x):
         """(heat, idx, win) of the float input x (the `self.model(x)` seam of `predict`): the certified argmax -- the fp32 index the
         reference's torch.argmax returns -- or, with certification off, the handle's own."""
-        self._calibrate(x=x)
+        self.calibrate(x=x)
         if self.cert is None:
             return wasb.WASBNet.forward(self.model, x, want_heatmap=True, want_peaks=True)
         c = self.cert.run(x=x)
@@ -116,11 +161,28 @@ class _HubDetector:
         c = self.cert.run(fr)
         return c.idx, c.win
 
-    def _enqueue(self, frames_u8, f0, f1):
-        """One call on frames_u8[f0:f1], enqueued on the current stream (the overlapped clip path) -> wasb.CertCall."""
+    def enqueue(self, frames_u8, f0, f1):
+        """One call on frames_u8[f0:f1], enqueued on the current stream -> wasb.CertCall (without status and info when uncertified)."""
         if self.cert is not None:
             return self.cert.enqueue(frames_u8, f0, f1)
         return wasb.CertCall(f0, f1, *self.model.forward_frames(frames_u8[f0:f1])[1:])
+
+    def audit(self, frames_u8, n, after):
+        """Count the n samples of the clip frames_u8 and enqueue the eps audit of those drawn among them: on the fp32 twin, on its own
+        stream next to the detector calls, once the current stream has seen the event `after` (the clip's last upload).  -> a ticket
+        for `settle`; None when nothing was drawn or the detector is uncertified."""
+        picks = self.cert.picks(n) if self.cert is not None else []
+        if not picks:
+            return None
+        torch.cuda.current_stream(self.device).wait_event(after)
+        return self.cert.audit(picks, frames_u8)
+
+    def settle(self, calls, frames_u8, audit):
+        """The host half of enqueued calls once their stream has drained (`EpsAudit.settle`; a call run again whole is a new, counted
+        call: `EpsAudit.run`) -> the positions of the calls whose peaks changed: none when uncertified."""
+        if self.cert is None:
+            return set()
+        return self.cert.settle(calls, frames_u8, audit=audit, rerun=lambda c: self.cert.run(frames_u8[c.f0:c.f1]))
 
 
 class BallDetector(_HubDetector):
@@ -132,33 +194,23 @@ class BallDetector(_HubDetector):
             raise NotImplementedError("detector '%s' depends on code that is not vendored in the reference "
                                       "(KieDani/SegformerPlusPlus); only 'wasb' and 'vitpose' are built" % model_name)
         _lib.require_gpu()
-        self.device = torch.device('cuda')
-        self.resolution = (WIDTH, HEIGHT)
         sd, res, in_frames = _load_ball_checkpoint(model_name)
-        self.model = wasb.get_model(model_name, in_frames=in_frames, resolution=res, pretraining=False, state_dict=sd,
-                                    max_batch=max_batch, dtype=dtype, lanes=lanes)
-        self._init_cert()
-        self.model_resolution = res
-        self.max_batch = max_batch
+        self._init_hub(wasb.get_model(model_name, in_frames=in_frames, resolution=res, pretraining=False, state_dict=sd,
+                                      max_batch=max_batch, dtype=dtype, lanes=lanes), res, max_batch)
 
     def predict(self, images):
         """images: list (length B) of [prev, curr, next] BGR uint8 HWC arrays.
-        Returns (pred_pos (B,3) float64 [x, y, confidence] in 1920x1080 px, preds (B,1,H,W) float32)."""
+        Returns (pred_pos (B,3) float64 [x, y, confidence] in 1920x1080 px, preds (B,1,H,W) float32; ViTPose: (B,1,H/4,W/4))."""
         pred_pos, preds = [], []
         w, h = self.model_resolution
         for b0 in range(0, len(images), self.max_batch):
-            chunk = images[b0:b0 + self.max_batch]
-            xs = []
-            for imgs in chunk:
-                fr = torch.from_numpy(np.stack([np.asarray(i) for i in imgs])).to(self.device)   # (3,h,w,3) uint8
-                xs.append(wasb.preprocess_triples(fr, (w, h)))
+            xs = [wasb.preprocess_triples(self._upload(imgs), (w, h)) for imgs in images[b0:b0 + self.max_batch]]
             # peaks from the certified argmax (the fp32 index the reference's torch.argmax returns), table-variant fit (interface.py:116)
             heat, idx, win = self._certified_forward(torch.cat(xs))
-            pos = refine.refine_windows_device(idx, win, h, w, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
-            pred_pos.append(pos.cpu().numpy())
+            pred_pos.append(self.refine_peaks(idx, win).cpu().numpy())
             preds.append(heat.cpu().numpy())
         if not pred_pos:
-            return np.zeros((0, 3)), np.zeros((0, 1, h, w), np.float32)
+            return np.zeros((0, 3)), np.zeros((0, 1) + self.heat_hw, np.float32)
         return np.concatenate(pred_pos, axis=0), np.concatenate(preds, axis=0)
 
     def predict_clip(self, images):
@@ -169,35 +221,16 @@ class BallDetector(_HubDetector):
         n = len(images)
         if n < 3:
             return np.zeros((0, 3))
-        w, h = self.model_resolution
         out = []
         step = self.max_batch                      # triples per call; consecutive calls overlap by two frames
         for t0 in range(0, n - 2, step):
-            fr = torch.from_numpy(np.stack([np.asarray(i) for i in images[t0:t0 + step + 2]])).to(self.device)
-            self._calibrate(fr)
-            idx, win = self._certified_peaks(fr)
-            out.append(refine.refine_windows_device(idx, win, h, w, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE).cpu().numpy())
+            fr = self._upload(images[t0:t0 + step + 2])
+            self.calibrate(fr)
+            out.append(self.refine_peaks(*self._certified_peaks(fr)).cpu().numpy())
         return np.concatenate(out, axis=0)
 
     def filter_trajectory(self, ball_positions, ball_positions_aux, fps):
         return glue.filter_trajectory_ball(ball_positions, ball_positions_aux, fps)
-
-
-def _load_table_checkpoint(model_name):
-    """-> (state_dict, resolution (W,H)).  Reference: inference_tabledetection.load_model :40-57."""
-    path = os.path.join(_weights_dir(), 'inference_tabledetection', model_name, 'model.pt')
-    if _weights_dir() and os.path.exists(path):
-        sd, info = weights.load_checkpoint_state_dict(path)
-        return sd, tuple(info.get('image_resolution', vitpose.RESOLUTIONS['vitpose'] if model_name == 'vitpose' else (1280, 704)))
-    _synthetic_or_raise("TableDetector('%s')" % model_name, path if _weights_dir() else '')
-    if model_name == 'vitpose':
-        res = vitpose.RESOLUTIONS['vitpose']
-        return weights.random_vitpose_state_dict(int(os.environ.get('TTUP_SEED', '0')) + 1, in_ch=3, out_ch=13, resolution=res), res
-    # seeded stand-in: a planted path to every keypoint head, so the heatmaps are PEAKED like a trained detector's (one dominant
-    # maximum per keypoint map; on pure noise weights every map is a field of near-ties and the certified argmax degrades to the
-    # full-frame fp32 path -- TTUP_TABLE_NOISE_WEIGHTS=1 selects that regime)
-    noise = os.environ.get('TTUP_TABLE_NOISE_WEIGHTS') == '1'
-    return weights.random_wasb_state_dict(int(os.environ.get('TTUP_SEED', '0')) + 1, planted=not noise, in_ch=3, head_out=13, plant_all_heads=not noise), (1280, 704)
 
 
 class TableDetector(_HubDetector):
@@ -210,44 +243,34 @@ class TableDetector(_HubDetector):
         if 'segformerpp' in model_name:
             raise NotImplementedError("detector '%s' depends on code that is not vendored in the reference; only 'hrnet' and 'vitpose' are built" % model_name)
         _lib.require_gpu()
-        self.device = torch.device('cuda')
-        self.resolution = (WIDTH, HEIGHT)
-        self.KEYPOINT_VISIBLE = KEYPOINT_VISIBLE
         sd, res = _load_table_checkpoint(model_name)
-        self.model = wasb.get_table_model(model_name, resolution=res, pretraining=False, state_dict=sd, max_batch=max_batch, dtype=dtype, lanes=lanes)
-        self._init_cert()
-        self.model_resolution = res
-        self.max_batch = max_batch
+        self._init_hub(wasb.get_table_model(model_name, resolution=res, pretraining=False, state_dict=sd, max_batch=max_batch, dtype=dtype, lanes=lanes),
+                       res, max_batch)
 
     def predict(self, images):
         """images: list (length B) of BGR uint8 HWC frames.
         Returns (pred_pos (B,13,3) float64 [x, y, visibility] in 1920x1080 px, preds (B,1,13,H,W) float32 -- the reference
-        stacks one (1,13,H,W) tensor per frame with np.array, interface.py:165-167)."""
+        stacks one (1,13,H,W) tensor per frame with np.array, interface.py:165-167; ViTPose: (B,1,13,H/4,W/4))."""
         pred_pos, preds = [], []
-        w, h = self.model_resolution
         for b0 in range(0, len(images), self.max_batch):
-            fr = torch.from_numpy(np.stack([np.asarray(i) for i in images[b0:b0 + self.max_batch]])).to(self.device)
+            fr = self._upload(images[b0:b0 + self.max_batch])
             # per-channel peaks from the certified argmax: the reference takes them from fp32 heatmaps (interface.py:148-172 ->
             # tabledetection/helper_tabledetection.py:50-156)
-            heat, idx, win = self._certified_forward(wasb.preprocess_frames(fr, (w, h)))
-            pos = refine.refine_windows_device(idx, win, h, w, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
-            pred_pos.append(pos.cpu().numpy().reshape(-1, 13, 3))
+            heat, idx, win = self._certified_forward(wasb.preprocess_frames(fr, self.model_resolution))
+            pred_pos.append(self.refine_peaks(idx, win).cpu().numpy().reshape(-1, 13, 3))
             preds.append(heat.cpu().numpy()[:, None])
         if not pred_pos:
-            return np.zeros((0, 13, 3)), np.zeros((0, 1, 13, h, w), np.float32)
+            return np.zeros((0, 13, 3)), np.zeros((0, 1, 13) + self.heat_hw, np.float32)
         return np.concatenate(pred_pos, axis=0), np.concatenate(preds, axis=0)
 
     def predict_keypoints(self, images):
         """`predict` without the heatmaps: (B,13,3) keypoints only.  Pre-processing, CNN, per-channel argmax and windows run
         fused on the device; nothing but the 39 numbers per frame comes back to the host."""
-        w, h = self.model_resolution
         out = []
         for b0 in range(0, len(images), self.max_batch):
-            fr = torch.from_numpy(np.stack([np.asarray(i) for i in images[b0:b0 + self.max_batch]])).to(self.device)
-            self._calibrate(fr)
-            idx, win = self._certified_peaks(fr)
-            pos = refine.refine_windows_device(idx.reshape(-1), win.reshape(-1, 9), h, w, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
-            out.append(pos.cpu().numpy().reshape(-1, 13, 3))
+            fr = self._upload(images[b0:b0 + self.max_batch])
+            self.calibrate(fr)
+            out.append(self.refine_peaks(*self._certified_peaks(fr)).cpu().numpy().reshape(-1, 13, 3))
         return np.concatenate(out, axis=0) if out else np.zeros((0, 13, 3))
 
     def calibrate_camera(self, keypoints):
@@ -258,97 +281,35 @@ class TableDetector(_HubDetector):
         return glue.filter_trajectory_table(table_keypoints, table_keypoints_aux)
 
 
-class ViTPoseBallDetector(BallDetector):
+class _ViTPoseHooks:
+    """What a ViTPose detector changes in its base: it runs the uncertified fp32 path (csrc/vitpose.hip) -- there is no bf16 ViTPose to
+    certify, so the peaks come from fp32 heatmaps like the reference's, `cert` is None and nothing is calibrated -- its heatmaps are a
+    quarter of the model resolution, and its clip call (`ViTPoseNet.forward_frames`) takes a frame range of any length."""
+    HEAT_DIV = 4
+    CLIP_AUX = True
+
+    def _certified_forward(self, x):
+        return self.model.forward(x, want_heatmap=True, want_peaks=True)
+
+
+class ViTPoseBallDetector(_ViTPoseHooks, BallDetector):
     """BallDetector('vitpose'): the reference's ViTPose-small ball detector (balldetection/models/vitpose.py, in_frames 3,
-    1152x640, heatmaps at a quarter of that).  It runs the uncertified fp32 path (csrc/vitpose.hip): there is no bf16 ViTPose to
-    certify, so the peaks come from fp32 heatmaps like the reference's and none of the certified-argmax machinery applies."""
+    1152x640, heatmaps at a quarter of that)."""
 
     def __init__(self, model_name='vitpose', max_batch=32, dtype='f32', lanes=0):
         _lib.require_gpu()
-        self.device = torch.device('cuda')
-        self.resolution = (WIDTH, HEIGHT)
         sd, res, in_frames = _load_ball_checkpoint(model_name)
-        self.model = vitpose.ViTPoseNet(sd, in_ch=3 * in_frames, out_ch=1, resolution=res, max_batch=max_batch)
-        self.model_resolution = res
-        self.max_batch = max_batch
-
-    def _peaks(self, x):
-        heat, idx, win = self.model.forward(x, want_heatmap=True, want_peaks=True)
-        return self._refine(idx, win), heat
-
-    def predict(self, images):
-        """images: list (length B) of [prev, curr, next] BGR uint8 HWC arrays.
-        Returns (pred_pos (B,3) float64 [x, y, confidence] in 1920x1080 px, preds (B,1,H/4,W/4) float32)."""
-        w, h = self.model_resolution
-        pred_pos, preds = [], []
-        for b0 in range(0, len(images), self.max_batch):
-            xs = [wasb.preprocess_triples(torch.from_numpy(np.stack([np.asarray(i) for i in imgs])).to(self.device), (w, h))
-                  for imgs in images[b0:b0 + self.max_batch]]
-            pos, heat = self._peaks(torch.cat(xs))
-            pred_pos.append(pos.cpu().numpy())
-            preds.append(heat.cpu().numpy())
-        if not pred_pos:
-            return np.zeros((0, 3)), np.zeros((0, 1, h // 4, w // 4), np.float32)
-        return np.concatenate(pred_pos, axis=0), np.concatenate(preds, axis=0)
-
-    def predict_clip(self, images):
-        """images = list of N BGR uint8 HWC frames -> pred_pos (N-2, 3), the values `predict` returns for the triples
-        (images[i-1], images[i], images[i+1]); every frame is uploaded once and no heatmap comes back to the host."""
-        n = len(images)
-        if n < 3:
-            return np.zeros((0, 3))
-        out = []
-        for t0 in range(0, n - 2, self.max_batch):
-            fr = torch.from_numpy(np.stack([np.asarray(i) for i in images[t0:t0 + self.max_batch + 2]])).to(self.device)
-            out.append(self._refine(*self.model.forward_frames(fr)[1:]).cpu().numpy())
-        return np.concatenate(out, axis=0)
-
-    def _refine(self, idx, win):
-        w, h = self.model_resolution
-        return refine.refine_windows_device(idx, win, h // 4, w // 4, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
+        self._init_hub(vitpose.ViTPoseNet(sd, in_ch=3 * in_frames, out_ch=1, resolution=res, max_batch=max_batch), res, max_batch)
 
 
-class ViTPoseTableDetector(TableDetector):
+class ViTPoseTableDetector(_ViTPoseHooks, TableDetector):
     """TableDetector('vitpose'): the reference's ViTPose-small table-keypoint detector (tabledetection/models/vitpose.py, 13
-    heatmaps at a quarter of 1152x640).  Uncertified fp32 path, for the reason ViTPoseBallDetector gives."""
+    heatmaps at a quarter of 1152x640)."""
 
     def __init__(self, model_name='vitpose', max_batch=8, dtype='f32', lanes=0):
         _lib.require_gpu()
-        self.device = torch.device('cuda')
-        self.resolution = (WIDTH, HEIGHT)
-        self.KEYPOINT_VISIBLE = KEYPOINT_VISIBLE
         sd, res = _load_table_checkpoint(model_name)
-        self.model = vitpose.ViTPoseNet(sd, in_ch=3, out_ch=13, resolution=res, max_batch=max_batch)
-        self.model_resolution = res
-        self.max_batch = max_batch
-
-    def _keypoints(self, images, want_heatmap):
-        pred_pos, preds = [], []
-        for b0 in range(0, len(images), self.max_batch):
-            fr = torch.from_numpy(np.stack([np.asarray(i) for i in images[b0:b0 + self.max_batch]])).to(self.device)
-            heat, idx, win = self.model.forward_frames(fr, want_heatmap=want_heatmap)
-            pred_pos.append(self._refine(idx, win).cpu().numpy().reshape(-1, 13, 3))
-            if want_heatmap:
-                preds.append(heat.cpu().numpy()[:, None])
-        return pred_pos, preds
-
-    def _refine(self, idx, win):
-        # argmax + 3x3 Gaussian refine, table variant (interface.py:113-116), scaled by the heatmap size
-        w, h = self.model_resolution
-        return refine.refine_windows_device(idx, win, h // 4, w // 4, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
-
-    def predict(self, images):
-        """images: list (length B) of BGR uint8 HWC frames -> (pred_pos (B,13,3) float64, preds (B,1,13,H/4,W/4) float32)."""
-        w, h = self.model_resolution
-        pred_pos, preds = self._keypoints(images, True)
-        if not pred_pos:
-            return np.zeros((0, 13, 3)), np.zeros((0, 1, 13, h // 4, w // 4), np.float32)
-        return np.concatenate(pred_pos, axis=0), np.concatenate(preds, axis=0)
-
-    def predict_keypoints(self, images):
-        """`predict` without the heatmaps: (B,13,3) keypoints only."""
-        pred_pos, _ = self._keypoints(images, False)
-        return np.concatenate(pred_pos, axis=0) if pred_pos else np.zeros((0, 13, 3))
+        self._init_hub(vitpose.ViTPoseNet(sd, in_ch=3, out_ch=13, resolution=res, max_batch=max_batch), res, max_batch)
 
 
 class UpliftingModel:
@@ -395,23 +356,18 @@ class UpliftingModel:
             dev = buf.to(self.device, non_blocking=True)
             pred_rotation, pred_position = self.model(dev[:2 * n].view(1, n, 2), dev[2 * n:2 * n + 39].view(1, 13, 3), dev[2 * n + 39:3 * n + 39].view(1, n),
                                                       dev[3 * n + 39:].view(1, n), check_mask=False)
-            pred_rotation_local = uplift.transform_rotationaxes(pred_rotation, pred_position.clone()) if self.transform_mode == 'global' else pred_rotation
-            t_prime = int(m_.sum())
-            return pred_rotation_local.squeeze(0), pred_position[0, :t_prime, :].cpu().numpy()
-        ball_coords, table_coords, mask, times = [torch.as_tensor(a).to(self.device, torch.float32) for a in (ball_coords, table_coords, mask, times)]
-        if ball_coords.dim() == 2:      # (N,2) -> pad to the mask length like the reference's callers do
-            n = mask.shape[-1]
-            b = torch.zeros((1, n, 2), device=self.device); b[0, :ball_coords.shape[0]] = ball_coords
-            t = torch.zeros((1, n), device=self.device); t[0, :times.shape[0]] = times
-            ball_coords, times, mask, table_coords = b, t, mask.reshape(1, n), table_coords.reshape(1, 13, 3)
-        pred_rotation, pred_position = self.model(ball_coords, table_coords, mask, times)
-        if self.transform_mode == 'global':
-            pred_rotation_local = uplift.transform_rotationaxes(pred_rotation, pred_position.clone())
+            mask = m_          # the number of valid steps comes from the host copy
         else:
-            pred_rotation_local = pred_rotation
-        t_prime = int(mask.sum().item())
-        pred_position = pred_position[:, :t_prime, :].cpu().numpy()
-        return pred_rotation_local.squeeze(0), pred_position.squeeze(0)
+            ball_coords, table_coords, mask, times = [torch.as_tensor(a).to(self.device, torch.float32) for a in (ball_coords, table_coords, mask, times)]
+            if ball_coords.dim() == 2:      # (N,2) -> pad to the mask length like the reference's callers do
+                n = mask.shape[-1]
+                b = torch.zeros((1, n, 2), device=self.device); b[0, :ball_coords.shape[0]] = ball_coords
+                t = torch.zeros((1, n), device=self.device); t[0, :times.shape[0]] = times
+                ball_coords, times, mask, table_coords = b, t, mask.reshape(1, n), table_coords.reshape(1, 13, 3)
+            pred_rotation, pred_position = self.model(ball_coords, table_coords, mask, times)
+        pred_rotation_local = uplift.transform_rotationaxes(pred_rotation, pred_position.clone()) if self.transform_mode == 'global' else pred_rotation
+        t_prime = int(mask.sum())          # (a device mask: one read-back)
+        return pred_rotation_local.squeeze(0), pred_position[:, :t_prime, :].cpu().numpy().squeeze(0)
 
 
 def _aux_class(name, vit_cls, what):
@@ -421,6 +377,162 @@ def _aux_class(name, vit_cls, what):
     if isinstance(name, str) and 'segformerpp' in name:
         raise NotImplementedError("%s '%s' depends on code that is not vendored in the reference; only 'vitpose' (or None) is built" % (what, name))
     raise ValueError("%s must be None or 'vitpose', got %r" % (what, name))
+
+
+def clip_schedule(n, chunk, chunk_long, first, max_batch):
+    """The overlapped clip path's schedule for n frames -> (bounds, ball, aux).  bounds: the chunk boundaries -- a short first chunk
+    (`first` frames) gets the GPU going while the host still stages the bulk of the clip; after it, chunks of `chunk` frames, or of
+    `chunk_long` for clips of at least four chunks.  Chunk k, bounds[k]:bounds[k+1], is one upload, one table-detector call and the
+    ball-detector calls ball[k] = [(f0, f1), ...], frame ranges of at most `max_batch` triples each, on the triples whose three
+    frames are resident by then (triple t needs frames t..t+2: everything up to c1-3 can go once c1 frames are up).  aux[k]: the
+    one frame range an aux ball detector takes for the same triples, None where ball[k] is empty."""
+    C = chunk if n < 4 * chunk else chunk_long
+    F0 = min(first, C, n)
+    bounds = sorted(set([0, F0] + list(range(F0 + C, n, C)) + ([n] if n > F0 else [])))
+    ball, aux, t = [], [], 0               # t: first triple not yet submitted
+    for c1 in bounds[1:]:
+        calls = []
+        while t < c1 - 2:
+            nt = min(max_batch, c1 - 2 - t)
+            calls.append((t, t + nt + 2))
+            t += nt
+        ball.append(calls)
+        aux.append((calls[0][0], c1) if calls else None)
+    return bounds, ball, aux
+
+
+def _to_pinned(t):
+    """A pinned host copy of the device tensor t, enqueued on the current stream (the caller records the event to wait for)."""
+    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    host.copy_(t, non_blocking=True)
+    return host
+
+
+class _ClipRun:
+    """One call of `TableTennisPipeline._clip_detections`: the clip on the device, the detector calls enqueued on it and their outputs.
+    ViTPose aux detectors (`CLIP_AUX`) run on a third stream from the same upload."""
+
+    def __init__(self, pipe, images, want_table):
+        self.t00, self.trace = time.perf_counter(), pipe._trace          # tools/hub_trace.py: host time stamps (ms since the call) of the stages
+        self.pipe, self.images, self.n, self.want_table = pipe, images, len(images), want_table
+        self.bd, self.td = pipe.ball_detector, pipe.table_detector
+        self.ba = pipe.ball_detector_aux if pipe.ball_detector_aux.CLIP_AUX else None
+        self.ta = pipe.table_detector_aux if want_table and pipe.table_detector_aux.CLIP_AUX else None
+        self.has_aux = self.ba is not None or self.ta is not None
+        self.frames, self.st, self.cur = pipe._clip_resources(images, self.has_aux)
+        self.ball_calls, self.table_calls, self.table_out, self.ball_aux_out, self.table_aux_out = [], [], [], [], []
+        self.ev = self.ball_audit = self.kp_aux_host = self.ev_kp_aux = None
+
+    def mark(self, name):
+        if self.trace is not None:
+            self.trace.append((name, (time.perf_counter() - self.t00) * 1e3))
+
+    def upload(self, ci, c0, c1):
+        """Stage frames c0:c1 (chunk ci) in pinned memory and copy them to the device; `ev` is the end of that copy.  The first chunk
+        also calibrates the certified detectors (eps: once per detector)."""
+        pipe, k = self.pipe, ci % 2
+        if pipe._pin_free[k] is not None:
+            pipe._pin_free[k].synchronize()          # the copy that last read this staging buffer is done
+        pipe._stage(self.images, c0, c1, pipe._pinned[k])
+        self.mark('staged chunk %d' % ci)
+        with torch.cuda.stream(self.st['copy']):
+            self.frames[c0:c1].copy_(pipe._pinned[k][:c1 - c0], non_blocking=True)
+            self.ev = torch.cuda.Event(); self.ev.record()
+        pipe._pin_free[k] = self.ev
+        if ci == 0:
+            self.cur.wait_event(self.ev)
+            if c1 >= 3:
+                self.bd.calibrate(self.frames[:c1])
+            if self.want_table:
+                self.td.calibrate(self.frames[:c1])
+
+    def enqueue(self, c0, c1, ball_ranges, aux_range):
+        """The detector work on an uploaded chunk: table, ball, aux in that order, each on its own stream behind the upload."""
+        frames, st, ev = self.frames, self.st, self.ev
+        if self.want_table:
+            with torch.cuda.stream(st['table']):
+                st['table'].wait_event(ev)
+                # the keypoints are refined at once from what the call returned -- settled in `finish_table`, after the stream has
+                # drained, and refined again only where a re-certification or repair changed them
+                call = self.td.enqueue(frames, c0, c1)
+                self.table_calls.append(call)
+                self.table_out.append(self.td.refine_peaks(call.idx, call.win))
+        for f0, f1 in ball_ranges:
+            with torch.cuda.stream(st['ball']):
+                st['ball'].wait_event(ev)
+                self.ball_calls.append(self.bd.enqueue(frames, f0, f1))
+        if self.has_aux:
+            with torch.cuda.stream(st['aux']):
+                st['aux'].wait_event(ev)
+                if self.ta is not None:
+                    call = self.ta.enqueue(frames, c0, c1)
+                    self.table_aux_out.append(self.ta.refine_peaks(call.idx, call.win))
+                    if c1 == self.n:           # the aux keypoints go to the host ahead of the last ball pass: the keypoint filter overlaps it
+                        self.kp_aux_host = _to_pinned(torch.cat(self.table_aux_out).reshape(-1, 13, 3))
+                        self.ev_kp_aux = torch.cuda.Event(); self.ev_kp_aux.record()
+                if self.ba is not None and aux_range is not None:
+                    call = self.ba.enqueue(frames, *aux_range)
+                    self.ball_aux_out.append(self.ba.refine_peaks(call.idx, call.win))
+
+    def all_enqueued(self):
+        """After the last chunk: the clip tensor is held until the streams are through with it, and the ball detector's eps audit (a
+        random triple of the clip) is drawn and enqueued."""
+        self.mark('all calls enqueued')
+        self.frames.record_stream(self.st['ball']); self.frames.record_stream(self.st['table'])
+        if self.has_aux:
+            self.frames.record_stream(self.st['aux'])
+        self.ball_audit = self.bd.audit(self.frames, self.n - 2, self.ev)
+
+    def finish_table(self, table_consumer, return_aux):
+        """-> (keypoints or what `table_consumer` makes of them, raw aux keypoints).  The table detector (high-priority streams)
+        finishes first: its keypoints come back and the host-side consumer (the DBSCAN filter) runs while the ball detector is still
+        busy on the GPU."""
+        td, st, calls, frames = self.td, self.st, self.table_calls, self.frames
+        audit = td.audit(frames, self.n, self.ev)
+        certified = calls[0].status is not None
+        with torch.cuda.stream(st['table']):
+            kp_host = _to_pinned(torch.cat(self.table_out).reshape(-1, 13, 3))
+            if certified:          # the calls' status flags and crop / error info in one copy each
+                st_host = _to_pinned(torch.cat([c.status for c in calls]))
+                in_host = _to_pinned(torch.stack([c.info for c in calls]))
+            ev_t = torch.cuda.Event(); ev_t.record()
+        ev_t.synchronize()
+        self.mark('table stream drained')
+        kp_np = kp_host.numpy()
+        if certified:
+            o = 0
+            for k, c in enumerate(calls):
+                nmap = c.idx.shape[0]
+                c.status, c.info = st_host.numpy()[o:o + nmap], in_host.numpy()[k]
+                o += nmap
+            self.cur.wait_stream(st['table'])
+        for k in sorted(td.settle(calls, frames, audit)):          # rare: re-certified / repaired calls are refined again
+            c = calls[k]
+            kp_np[c.f0:c.f1] = td.refine_peaks(c.idx, c.win).cpu().numpy().reshape(-1, 13, 3)
+        self.mark('table calls settled')
+        if self.ta is not None:
+            self.ev_kp_aux.synchronize()
+            self.mark('aux table keypoints on the host')
+            kp_aux = self.kp_aux_host.numpy().copy()
+            kp = table_consumer(kp_np, kp_aux) if table_consumer is not None else kp_np.copy()
+        else:
+            kp_aux = kp_np.copy() if return_aux else None
+            kp = table_consumer(kp_np) if table_consumer is not None else kp_np.copy()
+        self.mark('keypoint filter done')
+        return kp, kp_aux
+
+    def finish_ball(self, return_aux):
+        """-> (positions, raw aux positions if asked for: the primary's where the primary fills the aux slot).  The caller's stream joins every
+        stream here, and the host blocks on it in the downloads."""
+        for s in self.st.values():
+            self.cur.wait_stream(s)
+        self.bd.settle(self.ball_calls, self.frames, self.ball_audit)
+        out = [self.bd.refine_peaks(c.idx, c.win) for c in self.ball_calls]
+        pos = torch.cat(out).cpu().numpy() if out else np.zeros((0, 3))
+        self.mark('ball calls settled, positions on the host')
+        if self.ba is None or not return_aux:
+            return pos, pos
+        return pos, torch.cat(self.ball_aux_out).cpu().numpy() if self.ball_aux_out else np.zeros((0, 3))
 
 
 class TableTennisPipeline:
@@ -475,153 +587,35 @@ class TableTennisPipeline:
         third; the host blocks only at the end.  Same values as `predict_clip` / `predict_keypoints` (same kernels per frame).
         ViTPose aux detectors run on a third stream from the same upload; `table_consumer` then gets (keypoints, aux keypoints).
         return_aux: (pos, kp, pos_aux, kp_aux), the aux values raw (the primary's where the primary fills the aux slot)."""
-        n, dev = len(images), self.device
-        ba = self.ball_detector_aux if isinstance(self.ball_detector_aux, ViTPoseBallDetector) else None
-        ta = self.table_detector_aux if want_table and isinstance(self.table_detector_aux, ViTPoseTableDetector) else None
-        import time as _time
-        tr = self._trace          # tools/hub_trace.py: host time stamps (ms since the call) of the clip path's stages
-        t00 = _time.perf_counter()
-        mark = (lambda name: tr.append((name, (_time.perf_counter() - t00) * 1e3))) if tr is not None else (lambda name: None)
-        C = self.CHUNK if n < 4 * self.CHUNK else self.CHUNK_LONG
-        CP = self.CHUNK_LONG                       # rows of the pinned staging buffers
+        run = _ClipRun(self, images, want_table)
+        bounds, ball, aux = clip_schedule(run.n, self.CHUNK, self.CHUNK_LONG, self.FIRST, self.ball_detector.max_batch)
+        for ci, (c0, c1) in enumerate(zip(bounds[:-1], bounds[1:])):
+            run.upload(ci, c0, c1)
+            run.enqueue(c0, c1, ball[ci], aux[ci])
+        run.all_enqueued()
+        kp, kp_aux = run.finish_table(table_consumer, return_aux) if want_table else (None, None)
+        pos, pos_aux = run.finish_ball(return_aux)
+        return (pos, kp, pos_aux, kp_aux) if return_aux else (pos, kp)
+
+    def _clip_resources(self, images, aux):
+        """-> (the clip's device tensor, the streams, the caller's stream, which the streams start behind).  Streams and pinned staging
+        buffers are created on first use and kept."""
+        dev = self.device
         h0, w0 = np.asarray(images[0]).shape[:2]
-        bd, td = self.ball_detector, self.table_detector
-        bw, bh = bd.model_resolution
-        tw, th = td.model_resolution
-        frames = torch.empty((n, h0, w0, 3), dtype=torch.uint8, device=dev)
+        frames = torch.empty((len(images), h0, w0, 3), dtype=torch.uint8, device=dev)
         if self._streams is None:
             self._streams = {k: torch.cuda.Stream(dev) for k in ('ball', 'table')}
             self._streams['copy'] = self._streams['table']          # uploads ride on the table stream (chunk k+1 behind the table pass of chunk k): one stream fewer
         st = self._streams
-        if self._pinned is None or self._pinned[0].shape[1:] != (h0, w0, 3):
-            self._pinned = [torch.empty((CP, h0, w0, 3), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        if self._pinned is None or self._pinned[0].shape[1:] != (h0, w0, 3):          # CHUNK_LONG rows: the largest chunk
+            self._pinned = [torch.empty((self.CHUNK_LONG, h0, w0, 3), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
             self._pin_free = [None, None]
-        if (ba is not None or ta is not None) and 'aux' not in st:
+        if aux and 'aux' not in st:
             st['aux'] = torch.cuda.Stream(dev)          # the ViTPose passes (the long pole): the HRNet streams run beside them
         cur = torch.cuda.current_stream(dev)
         for s in st.values():
             s.wait_stream(cur)
-        # chunk schedule: a short first chunk (FIRST frames) gets the GPU going while the host still stages the bulk of the clip;
-        # after it, chunks of C frames.  Each chunk = one upload, one table-detector call and one ball-detector call on the triples
-        # whose three frames are resident by then.
-        F0 = min(self.FIRST, C, n)
-        bounds = [0, F0] + list(range(F0 + C, n, C)) + ([n] if n > F0 else [])
-        bounds = sorted(set(bounds))
-        ball_out, table_out, ball_calls, table_calls = [], [], [], []
-        ball_aux_out, table_aux_out, kpa_host, ev_ta = [], [], None, None
-        t_next = a_next = 0               # first triple not yet submitted (primary, aux)
-        ev = None
-        for ci, (c0, c1) in enumerate(zip(bounds[:-1], bounds[1:])):
-            pin = self._pinned[ci % 2]
-            if self._pin_free[ci % 2] is not None:
-                self._pin_free[ci % 2].synchronize()          # the copy that last read this staging buffer is done
-            self._stage(images, c0, c1, pin)
-            mark('staged chunk %d' % ci)
-            with torch.cuda.stream(st['copy']):
-                frames[c0:c1].copy_(pin[:c1 - c0], non_blocking=True)
-                ev = torch.cuda.Event(); ev.record()
-            self._pin_free[ci % 2] = ev
-            if ci == 0:
-                torch.cuda.current_stream(dev).wait_event(ev)
-                if c1 >= 3:          # certified argmax: eps calibrated once per detector
-                    bd._calibrate(frames[:c1])
-                if want_table:
-                    td._calibrate(frames[:c1])
-            if want_table:
-                with torch.cuda.stream(st['table']):
-                    st['table'].wait_event(ev)
-                    # the keypoints are refined at once from what the call returned -- settled below, after the stream has drained, and
-                    # refined again only where a re-certification or repair changed them
-                    table_calls.append(td._enqueue(frames, c0, c1))
-                    table_out.append(refine.refine_windows_device(table_calls[-1].idx.reshape(-1), table_calls[-1].win.reshape(-1, 9), th, tw,
-                                                                  td.resolution[0], td.resolution[1], _lib.REFINE_TABLE))
-            # triples t need frames t..t+2: everything up to c1-3 can go now
-            while t_next < c1 - 2:
-                nt = min(bd.max_batch, c1 - 2 - t_next)
-                with torch.cuda.stream(st['ball']):
-                    st['ball'].wait_event(ev)
-                    ball_calls.append(bd._enqueue(frames, t_next, t_next + nt + 2))
-                t_next += nt
-            if ba is not None or ta is not None:
-                with torch.cuda.stream(st['aux']):
-                    st['aux'].wait_event(ev)
-                    if ta is not None:
-                        table_aux_out.append(ta._refine(*ta.model.forward_frames(frames[c0:c1])[1:]))
-                        if c1 == n:           # the aux keypoints go to the host ahead of the last ball pass: the keypoint filter overlaps it
-                            kpa_dev = torch.cat(table_aux_out).reshape(-1, 13, 3)
-                            kpa_host = torch.empty(kpa_dev.shape, dtype=kpa_dev.dtype, pin_memory=True)
-                            kpa_host.copy_(kpa_dev, non_blocking=True)
-                            ev_ta = torch.cuda.Event(); ev_ta.record()
-                    if ba is not None and a_next < c1 - 2:
-                        ball_aux_out.append(ba._refine(*ba.model.forward_frames(frames[a_next:c1])[1:]))
-                        a_next = c1 - 2
-        mark('all calls enqueued')
-        frames.record_stream(st['ball']); frames.record_stream(st['table'])
-        if ba is not None or ta is not None:
-            frames.record_stream(st['aux'])
-        # eps audit of the certified argmax: a random triple of the clip on the fp32 twin, on its own stream next to the detectors
-        audit = None
-        picks = bd.cert.picks(n - 2) if bd.cert is not None else []
-        if picks:
-            cur.wait_event(ev)
-            audit = bd.cert.audit(picks, frames)
-        kp = None
-        if want_table:
-            # the table detector (high-priority streams) finishes first: its keypoints come back and the host-side DBSCAN filter
-            # runs while the ball detector is still busy on the GPU
-            t_audit = None
-            t_picks = td.cert.picks(n) if td.cert is not None else []
-            if t_picks:
-                cur.wait_event(ev)
-                t_audit = td.cert.audit(t_picks, frames)
-            cert = td.cert is not None and bool(table_calls)
-            with torch.cuda.stream(st['table']):
-                kp_dev = torch.cat(table_out).reshape(-1, 13, 3)
-                kp_host = torch.empty(kp_dev.shape, dtype=kp_dev.dtype, pin_memory=True)
-                kp_host.copy_(kp_dev, non_blocking=True)
-                if cert:          # the calls' status flags and crop / error info in one copy each
-                    st_dev = torch.cat([c.status for c in table_calls])
-                    in_dev = torch.stack([c.info for c in table_calls])
-                    st_host = torch.empty(st_dev.shape, dtype=st_dev.dtype, pin_memory=True); st_host.copy_(st_dev, non_blocking=True)
-                    in_host = torch.empty(in_dev.shape, dtype=in_dev.dtype, pin_memory=True); in_host.copy_(in_dev, non_blocking=True)
-                ev_t = torch.cuda.Event(); ev_t.record()
-            ev_t.synchronize()
-            mark('table stream drained')
-            kp_np = kp_host.numpy()
-            if cert:
-                o = 0
-                for k, c in enumerate(table_calls):
-                    nmap = c.idx.shape[0]
-                    c.status, c.info = st_host.numpy()[o:o + nmap], in_host.numpy()[k]
-                    o += nmap
-                cur.wait_stream(st['table'])
-                # rare: re-certified / repaired calls are refined again (a call run again whole is a new, counted call: `EpsAudit.run`)
-                for k in sorted(td.cert.settle(table_calls, frames, audit=t_audit, rerun=lambda c: td.cert.run(frames[c.f0:c.f1]))):
-                    c = table_calls[k]
-                    pos = refine.refine_windows_device(c.idx.reshape(-1), c.win.reshape(-1, 9), th, tw, td.resolution[0], td.resolution[1], _lib.REFINE_TABLE)
-                    kp_np[c.f0:c.f1] = pos.cpu().numpy().reshape(-1, 13, 3)
-            mark('table calls settled')
-            if ta is not None:
-                ev_ta.synchronize()
-                mark('aux table keypoints on the host')
-                kp_aux = kpa_host.numpy().copy()
-                kp = table_consumer(kp_np, kp_aux) if table_consumer is not None else kp_np.copy()
-            else:
-                kp_aux = kp_np.copy() if return_aux else None
-                kp = table_consumer(kp_np) if table_consumer is not None else kp_np.copy()
-            mark('keypoint filter done')
-        for s in st.values():
-            cur.wait_stream(s)
-        if bd.cert is not None:
-            bd.cert.settle(ball_calls, frames, audit=audit, rerun=lambda c: bd.cert.run(frames[c.f0:c.f1]))
-        for c in ball_calls:
-            ball_out.append(refine.refine_windows_device(c.idx, c.win, bh, bw, bd.resolution[0], bd.resolution[1], _lib.REFINE_TABLE))
-        pos = torch.cat(ball_out).cpu().numpy() if ball_out else np.zeros((0, 3))
-        mark('ball calls settled, positions on the host')
-        if not return_aux:
-            return pos, kp
-        pos_aux = (torch.cat(ball_aux_out).cpu().numpy() if ball_aux_out else np.zeros((0, 3))) if ba is not None else pos
-        return pos, kp, pos_aux, (kp_aux if want_table else None)
+        return frames, st, cur
 
     STAGE_THREADS = 4
 
@@ -641,9 +635,9 @@ class TableTennisPipeline:
         list(self._stage_pool.map(lambda k: np.copyto(dst[k - c0], images[k]), range(c0, c1)))
 
     def _predict(self, images, fps, table_keypoints):
-        # the overlapped clip path feeds an aux detector only when it is ViTPose (or the primary itself)
-        overlapped = ((self.ball_detector_aux is self.ball_detector or isinstance(self.ball_detector_aux, ViTPoseBallDetector))
-                      and (self.table_detector_aux is self.table_detector or isinstance(self.table_detector_aux, ViTPoseTableDetector))
+        # the overlapped clip path feeds an aux detector only when it can run beside the primaries (or is the primary itself)
+        overlapped = ((self.ball_detector_aux is self.ball_detector or self.ball_detector_aux.CLIP_AUX)
+                      and (self.table_detector_aux is self.table_detector or self.table_detector_aux.CLIP_AUX)
                       and len(images) >= 3
                       and self.table_detector.max_batch >= self.CHUNK_LONG and self.ball_detector.max_batch >= self.CHUNK_LONG
                       and os.environ.get('TTUP_HUB_SERIAL') != '1')
