@@ -202,6 +202,28 @@ def test_edge_inputs_behave_as_for_the_default_variant(name, mode, rot):
     assert torch.allclose(rot2, rot_[3:7], rtol=1e-5, atol=1e-6) and torch.allclose(pos2, pos_[3:7], rtol=1e-5, atol=1e-6)
 
 
+@pytest.mark.parametrize('name,mode,rot', [('connectstage', 'dynamic', 'new'), ('singlestage', 'dynamic', 'old')])
+def test_two_chunks_match_one_chunk(name, mode, rot):
+    """The chunk loop at small size.  A handle with max_len 4096 holds 2 097 152 // (4096 * 14) = 36 trajectories in its scratch
+    (about 7.4 GB), so a batch of 40 runs as 36 + 4 and, being over one chunk, never as a graph; a handle with max_len 16 runs the
+    same batch as one chunk.  Both select the same kernels for every row (only the row-tile a trajectory falls in differs), so the
+    bar is that of tests/test_fullsize_configs.py for that situation.  'singlestage' / 'old' is the only cover of the position
+    head's cls-row strip and of the by-index RoPE table across a chunk boundary."""
+    sd = weights.random_uplift_state_dict(17, 'large', name, mode, rot)
+    args = [torch.from_numpy(a).cuda() for a in synth.synth_trajectories(40, 9, seed=17, pad=3)]
+    assert torch.cuda.current_stream() == torch.cuda.default_stream()
+    one = uplift.get_model(name, 'large', mode, rot, state_dict=sd, max_batch=40, max_len=16)
+    rot1, pos1 = one(*args)
+    two = uplift.get_model(name, 'large', mode, rot, state_dict=sd, max_batch=40, max_len=4096)
+    rot2, pos2 = two(*args)
+    torch.cuda.synchronize()
+    info1, info2 = one.graph_info(), two.graph_info()
+    del two
+    assert info2['stage_launches'] == 2 * info1['stage_launches'] > 0 and info1['replays'] == info2['replays'] == 0          # two chunks, no graph
+    assert rot1.shape == (40, 3) and pos1.shape == (40, 12, 3) and bool(torch.isfinite(rot1).all()) and bool(torch.isfinite(pos1).all())
+    assert torch.allclose(rot2, rot1, rtol=2e-6, atol=1e-7) and torch.allclose(pos2, pos1, rtol=2e-6, atol=1e-7)
+
+
 def test_checkpoint_by_path_serves_a_non_default_variant(golden, tmp_path):
     """load_uplifting_model + process_trajectory_uplifting and UpliftingModel(model_path=...) on a singlestage/stacked/old
     checkpoint: with transform_mode 'local' the spin comes back as predicted (the fixture's `rot`), with 'global' turned into the

@@ -90,9 +90,7 @@ struct Ctx {
 };
 
 int reduce_into(const Ctx& c, int slices, long long n, float* out) {
-    hipLaunchKernelGGL(reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.st, c.partial, slices, n, out);
-    TTUP_LAUNCH_CHECK();
-    return TTUP_OK;
+    return launch_1d(reduce_kernel, n, c.st, c.partial, slices, n, out);
 }
 // g[n] += column sums of z (M rows of leading dimension ldz)
 int colsum_into(const Ctx& c, const float* z, long long ldz, long long M, int N, float* g) {
@@ -570,13 +568,7 @@ void make_plan(const ttup_uplift* net, int batch, int len, float* base, Plan* p)
 }
 
 #define GRC(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
-#define LAUNCH1D(kernel, total, ...)                                                                                      \
-    do {                                                                                                                  \
-        if ((total) > 0) {                                                                                                \
-            hipLaunchKernelGGL(kernel, dim3((unsigned)(((total) + 255) / 256)), dim3(256), 0, c.st, __VA_ARGS__);         \
-            TTUP_LAUNCH_CHECK();                                                                                          \
-        }                                                                                                                 \
-    } while (0)
+#define LAUNCH1D(kernel, total, ...) do { if ((total) > 0) GRC(launch_1d(kernel, total, c.st, __VA_ARGS__)); } while (0)
 
 int ln_fwd(const Ctx& c, const float* x, const float* g, const float* b, float* y, long long M, int D) {
     if (M == 0) return TTUP_OK;

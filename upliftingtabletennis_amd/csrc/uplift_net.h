@@ -1,5 +1,5 @@
 // The uplift transformer's handle and weight tables (csrc/uplift.hip builds and runs them; csrc/uplift_grad.hip reads them for the
-// training loss and its gradients).
+// training loss and its gradients), and the 1-D launch both units use.
 #pragma once
 #include "common.h"
 #include <map>
@@ -16,11 +16,11 @@ struct Linear {
     float* b_dev = nullptr;      // [n] or null
     bool mfma = false;
     // K = 128 layers (all of the 'large' model's transformer layers): the weights split into three bf16 parts, packed per
-    // v_mfma_f32_16x16x32_bf16 A fragment: [ntile][k/32][plane][64 lanes][8] (linear_x3_kernel)
+    // v_mfma_f32_16x16x32_bf16 A fragment: [ntile][k/32][plane][64 lanes][8] (linear_x3_kernel, csrc/uplift_linear.h)
     uint16_t* w3_dev = nullptr;
 };
 
-// weight pointers of one layer for stage_x3_kernel (csrc/uplift.hip)
+// weight pointers of one layer for stage_x3_kernel (csrc/uplift_stage.h)
 struct StageLayerW {
     const uint16_t *w_qkv, *w_proj, *w_fc1, *w_fc2;
     const float *b_qkv, *g1, *b1, *g2, *b2, *bias1, *bias2;
@@ -42,6 +42,14 @@ struct Head { Linear fc1, fc2, fc3; };
 enum { NAME_CONNECT = 0, NAME_MULTI = 1, NAME_SINGLE = 2 };
 enum { MODE_DYNAMIC = 0, MODE_STACKED = 1, MODE_ORIGINAL = 2, MODE_FREE = 3 };
 
+// host only: one thread per element, 256 threads a workgroup
+template <typename... P, typename... A>
+int launch_1d(void (*kernel)(P...), long long n, hipStream_t st, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, args...);
+    TTUP_LAUNCH_CHECK();
+    return TTUP_OK;
+}
+
 }  // namespace upl
 }  // namespace ttup
 
@@ -61,6 +69,7 @@ struct ttup_uplift {
     float* cls_dev = nullptr; float* inv_freq_dev = nullptr; float* table_times_dev = nullptr;
     std::vector<StageLayerW> stage_pos, stage_first, stage_second;      // weight pointers of the three stages' layers (stage_x3_kernel); empty = not available
     long long stage_launches = 0;
+    long long* stage_stamps = nullptr;          // TTUP_STAGE_STAMPS: the stage kernel's cycle stamps, allocated on first use
     float2 *rope = nullptr, *table_rope = nullptr;      // (cos, sin) tables: [chunk*max_len][hd/2] per forward, [n_table][hd/2] fixed
     std::vector<void*> allocs;
     // 'connectstage' / 'dynamic' only: every record of the blob after inv_freq as plain fp32, in blob order -- which is the order of
@@ -68,7 +77,7 @@ struct ttup_uplift {
     float* plain = nullptr; long long plain_floats = 0;
     // scratch (sized for `chunk` trajectories of max_len tokens)
     float *x = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *x2 = nullptr, *tok = nullptr, *ttok = nullptr, *h1 = nullptr;
-    float *m1 = nullptr, *m2 = nullptr, *tmask = nullptr, *txy = nullptr, *tmp_small = nullptr;
+    float *m1 = nullptr, *m2 = nullptr, *tmask = nullptr, *txy = nullptr;
     int* flags_dev = nullptr;
     // Small batches (a rally or a handful of them: the hub surface, the pipeline's per-clip uplift) are launch-bound -- about
     // eighty kernels of a few microseconds each.  Their forward is captured once per (batch, length) into a hipGraph that works

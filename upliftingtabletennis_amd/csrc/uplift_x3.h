@@ -1,4 +1,4 @@
-// Building blocks of the uplift transformer's split-bf16 kernels (csrc/uplift.hip), K = 128 features per token.
+// Building blocks of the uplift transformer's split-bf16 kernels (csrc/uplift_linear.h, uplift_blocks.h, uplift_stage.h), K = 128 features per token.
 // The arithmetic (that of csrc/conv_x3.hip): every fp32 weight and every (LayerNorm'd) activation is split exactly into three bf16
 // parts, a product is the sum of six exact partial products (smallest first) accumulated in fp32 -- accurate to below one fp32 fma
 // rounding, at 2.7x the peak rate of v_mfma_f32_16x16x4_f32.

@@ -118,7 +118,7 @@ class MultiStageModel:
 
     def graph_info(self):
         """{'graphs', 'off', 'replays', 'stage_launches'}: the small-batch path (hipGraph replay of a captured forward; all layers
-        of a stage in one stage_x3_kernel launch, csrc/uplift.hip)."""
+        of a stage in one stage_x3_kernel launch, csrc/uplift_stage.h)."""
         out = (ctypes.c_int * 3)()
         _lib.check(self._lib.ttup_uplift_graph_info(self._handle, out))
         st = ctypes.c_longlong(0)
