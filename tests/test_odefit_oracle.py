@@ -25,6 +25,18 @@ def test_magnus_and_drag_signs():
     assert top[2] < none[2] - 0.01
 
 
+def test_a_stamp_not_later_than_the_last_used_one_adds_no_step():
+    # the contract the device kernels share (csrc/odefit.hip header): a missed frame padded with time 0 inside a track, or a
+    # repeated stamp, repeats the position before it, and the next interval starts from the last used stamp
+    full = R.integrate(P0, np.array([0.0, 0.01, 0.02, 0.0, 0.04]), 2e-3)
+    clean = R.integrate(P0, np.array([0.0, 0.01, 0.02, 0.04]), 2e-3)
+    assert np.array_equal(full[[0, 1, 2, 4]], clean)
+    assert np.array_equal(full[3], full[2])
+    assert np.abs(clean[3] - clean[2]).max() > 1e-3          # (the ball does move over the skipped stamp's interval)
+    dup = R.integrate(P0, np.array([0.0, 0.01, 0.01, 0.02, 0.04]), 2e-3)
+    assert np.array_equal(dup[[0, 1, 3, 4]], clean) and np.array_equal(dup[2], dup[1])
+
+
 def test_oracle_fit_recovers_planted_parameters():
     times = np.arange(40) / 60.0
     obs = R.project(CAM, R.integrate(P0, times, 2e-3))

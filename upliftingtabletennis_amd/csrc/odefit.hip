@@ -5,7 +5,10 @@
 //   model      free flight of a 40 mm / 2.7 g ball: gravity, quadratic + Stokes drag, Magnus lift, added mass, viscous spin decay
 //              -- the smooth part of the generator's force model (csrc/trajgen.hip `accel`, constants restated from the MuJoCo
 //              XML of syntheticdataset/helper.py:79-117); contacts are not modelled: one fit = one arc between bounces
-//   integrator classical RK4, fp64; every interval between two time stamps is cut into ceil(dt / h_max) equal steps
+//   integrator classical RK4, fp64; every interval between two time stamps is cut into ceil(dt / h_max) equal steps;
+//              a stamp that is not later than the last used stamp adds no step: the state stays where it was and the next
+//              interval starts from the last used stamp (a missed frame padded with time 0 inside a track, a repeated stamp).
+//              The fit's Jacobian pass, its `pos3d` output, `odeint_kernel` and oracle/odefit_ref.py::integrate share this rule
 //   residuals  pinhole projection (Mint . Mext . r) of the state at every valid time stamp minus the observed pixel
 //   solver     Levenberg-Marquardt on the Gauss-Newton normal equations (9x9, Marquardt scaling with diag(J'J)); the
 //              Jacobian is exact for the discrete flow: the 9 tangent columns d(state)/dp_j are integrated with the SAME RK4
@@ -16,8 +19,9 @@
 // wave shuffles and lane j accumulates row j of J'J.  The 9x9 solve is done redundantly by every lane from LDS.
 // Validation (tests/test_odefit_gpu.py, oracle/odefit_ref.py): 4th-order convergence under step halving, device == numpy
 // oracle to 1e-12, recovery of planted (r0, v0, w0) from their own noiseless projections to 1e-6, agreement with SciPy's
-// least_squares.  Parity with the reference is UNPINNED by construction: the reference's uplift is the transformer
-// (csrc/uplift.hip), this kernel is never wired in its place.
+// least_squares; tests/test_odefit_edges_gpu.py: the lane mapping, masks, stamp rule and track lengths at their edges.
+// Parity with the reference is UNPINNED by construction: the reference's uplift is the transformer (csrc/uplift.hip), this
+// kernel is never wired in its place.
 #include "common.h"
 #include <math.h>
 
@@ -135,8 +139,8 @@ __device__ __forceinline__ void normal_equations(const FitArgs& a, int traj, int
                     const int ns = substeps(dt, a.hmax);
                     const double h = dt / ns;
                     for (int q = 0; q < ns; ++q) rk4<true>(s, d, h);
+                    tprev = t;
                 }
-                tprev = t;
             }
             valid = !a.mask || a.mask[(size_t)traj * a.T + i] != 0.0;
         }
@@ -308,9 +312,9 @@ __global__ void odeint_kernel(const double* params, const double* times, const d
 extern "C" int ttup_odefit_forward(const double* obs_xy_dev, const double* times_dev, const double* mask_dev, const double* cam_dev, int cam_per_traj,
                                    const double* init_dev, int batch, int len, double h_max, int max_iter, double tol,
                                    double* params_dev, double* pos3d_dev, double* cost_dev, int* iters_dev, void* stream) {
-    TTUP_REQUIRE(obs_xy_dev && times_dev && cam_dev && init_dev && params_dev, TTUP_EINVAL, "ttup_odefit_forward: null pointer");
     TTUP_REQUIRE(batch >= 0 && len > 0 && h_max > 0.0 && max_iter > 0 && tol >= 0.0, TTUP_EINVAL, "ttup_odefit_forward: bad argument");
-    if (batch == 0) return TTUP_OK;
+    if (batch == 0) return TTUP_OK;                  // an empty batch has empty (null) buffers: nothing to check, nothing to launch
+    TTUP_REQUIRE(obs_xy_dev && times_dev && cam_dev && init_dev && params_dev, TTUP_EINVAL, "ttup_odefit_forward: null pointer");
     FitArgs a;
     a.obs = obs_xy_dev; a.times = times_dev; a.mask = mask_dev; a.cam = cam_dev; a.cam_per_traj = cam_per_traj ? 1 : 0; a.init = init_dev;
     a.B = batch; a.T = len; a.hmax = h_max; a.max_iter = max_iter; a.tol = tol;
@@ -322,9 +326,9 @@ extern "C" int ttup_odefit_forward(const double* obs_xy_dev, const double* times
 
 extern "C" int ttup_odefit_integrate(const double* params_dev, const double* times_dev, const double* cam_dev, int cam_per_traj, int batch, int len,
                                      double h_max, double* pos3d_dev, double* px_dev, void* stream) {
-    TTUP_REQUIRE(params_dev && times_dev && (cam_dev || !px_dev), TTUP_EINVAL, "ttup_odefit_integrate: null pointer");
     TTUP_REQUIRE(batch >= 0 && len > 0 && h_max > 0.0, TTUP_EINVAL, "ttup_odefit_integrate: bad argument");
     if (batch == 0) return TTUP_OK;
+    TTUP_REQUIRE(params_dev && times_dev && (cam_dev || !px_dev), TTUP_EINVAL, "ttup_odefit_integrate: null pointer");
     hipLaunchKernelGGL(odeint_kernel, dim3(cdiv(batch, 64)), dim3(64), 0, (hipStream_t)stream, params_dev, times_dev, cam_dev, cam_per_traj ? 1 : 0,
                        batch, len, h_max, pos3d_dev, px_dev);
     TTUP_LAUNCH_CHECK();

@@ -39,8 +39,12 @@ def integrate(params, times, cam=None, h_max=H_MAX, device='cuda'):
 
 def fit(ball_xy, times, cam, init, mask=None, h_max=H_MAX, max_iter=80, tol=1e-14, device='cuda'):
     """Levenberg-Marquardt fit of (r0, v0, w0) to pixel tracks.  ball_xy (B,T,2) px, times (B,T) s, cam (21,) or (B,21)
-    (see `_cam21`), init (B,9).  Returns dict of device tensors: params (B,9), pos3d (B,T,3), cost (B) mean squared
-    reprojection error [px^2], iters (B)."""
+    (see `_cam21`), init (B,9), mask (B,T) with 0 at the stamps to ignore.  Returns dict of device tensors: params (B,9),
+    pos3d (B,T,3), cost (B) mean squared reprojection error over the valid stamps [px^2], iters (B) accepted steps.
+
+    Time stamps: the parameters are the state at times[:, 0]; a stamp that is not later than the last used stamp adds no step
+    (a missed frame padded with time 0 inside a track, a repeated stamp): its position is the one before it, and the next
+    interval is integrated from the last used stamp.  `integrate` and oracle/odefit_ref.py::integrate follow the same rule."""
     _lib.require_gpu()
     lib = _lib.load()
     obs, times, camt, init = _dev(ball_xy, device), _dev(times, device), _dev(cam, device), _dev(init, device)
