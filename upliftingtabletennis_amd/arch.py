@@ -7,7 +7,7 @@ Pure-Python description (names, shapes, order) of
 
 The tables are used to (1) build seeded random weights with the reference's state_dict
 names, (2) serialise a reference-format state_dict into the flat blob that the C-ABI
-``ttup_wasb_create`` / ``ttup_uplift_create`` parse (csrc/wasb_net.hip, csrc/uplift.hip walk
+``ttup_wasb_create`` / ``ttup_uplift_create`` parse (csrc/wasb_blob.h, csrc/uplift.hip walk
 the same order and verify every record header).
 """
 from collections import namedtuple

@@ -4,16 +4,9 @@
 //   f32  : fp32 storage, direct fp32 FMA                               (parity / debug path)
 #pragma once
 #include "common.h"
-#include <vector>
+#include "wasb_graph.h"          // FoldedConv
 
 namespace ttup {
-
-// One convolution with eval-mode BatchNorm folded in (scale into the weights, shift into the bias).
-struct FoldedConv {
-    int cout = 0, cin = 0, k = 1, stride = 1;
-    std::vector<float> w;      // [cout][cin][k][k]
-    std::vector<float> bias;   // [cout]
-};
 
 // Device-side packed weights for one conv op (possibly two folded convs concatenated along K).
 struct PackedConv {

@@ -31,7 +31,7 @@ int launch_stem(const PackedConv& p1, const PackedConv& p2, const PackedConv& p3
     constexpr size_t SMEM = (size_t)(5 * 4 * 64 * 8 + 2 * 9 * 4 * 64 * 8 + 2 * 340 * 32 + 432 * 16) * 2;          // (the 4-step form needs 7.5 KB less; one size for all)
     static_assert(SMEM <= 160 * 1024, "LDS budget");
     TTUP_REQUIRE(frames_per_sample == 0 || frames_per_sample == 1 || frames_per_sample == 3, TTUP_EINVAL, "stem: frames per sample must be 0 (X0 records), 1 or 3");
-    const bool k4 = p1.k == 1;          // conv1 packed as 128 slots x 1 tap: the 4-step three-frame form (csrc/wasb_net.hip)
+    const bool k4 = p1.k == 1;          // conv1 packed as 128 slots x 1 tap: the 4-step three-frame form (csrc/wasb_graph.h)
     TTUP_REQUIRE(k4 == (frames_per_sample == 3), TTUP_EINVAL, "stem: the 4-step conv1 packing is the three-frame form");
     // (a two-wave-group pipeline of the stem, round 5: 14 % slower -- git show d528471:upliftingtabletennis_amd/csrc/experiments/rejected_kernels.hip.inc)
     const dim3 grid(persistent_grid(a.total_tiles));

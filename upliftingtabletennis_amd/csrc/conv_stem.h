@@ -29,7 +29,7 @@ struct StemArgs {
 // 3 tap rows x 40 slots (36 + 4 that carry zero weights) = 120 -> 128 = 4 k-steps of 32, a fragment = 8 consecutive slots of one row
 // (two 8-byte LDS reads: the records are 8-byte aligned).  The 16-slot records (each frame's 4 slots + 4 zero slots, two taps per
 // k-step) need 5 k-steps for the 81 real products: 20 % of conv1's MFMAs and 4 KB of its weights gone.  Weights: StemArgs::w1 packed
-// as a "1x1 conv with 128 inputs" in that slot order (csrc/wasb_net.hip).  Another fp32 summation order than the 5-step form (and
+// as a "1x1 conv with 128 inputs" in that slot order (csrc/wasb_graph.h).  Another fp32 summation order than the 5-step form (and
 // than the layer-wise conv): results agree to bf16 rounding flips, like the other fused kernels (tests/test_gpu_parity.py).
 template <int NF, bool K4 = false>
 __global__ __launch_bounds__(512) void stem_kernel(StemArgs a) {

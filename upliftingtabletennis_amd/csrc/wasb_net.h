@@ -1,10 +1,9 @@
-// Internal definition of the CNN handle (ttup_wasb): a static op list over NHWC buffers, shared by csrc/wasb_net.hip (graph
-// construction, forward) and csrc/certify.hip (certified argmax).  Not part of the C ABI.
+// Internal definition of the CNN handle (ttup_wasb): a static op list over NHWC buffers, shared by csrc/wasb_net.hip (create,
+// forward, cone pruning, C ABI) and csrc/certify.hip (certified argmax).  Not part of the C ABI.  The op list itself is planned
+// without a device by csrc/wasb_graph.h (Op, TensorShape, GraphPlan; included through conv.h); csrc/wasb_blob.h (blob parser, BN
+// fold) and csrc/wasb_timing.h (bench.py's timing entry points) are private to csrc/wasb_net.hip.
 #pragma once
 #include "conv.h"
-#include <map>
-#include <string>
-#include <vector>
 
 namespace ttup {
 size_t upsum_head_ws_bytes(int n_maps, int H, int W);
@@ -13,27 +12,7 @@ int launch_upsum_head(const void* base, const void* const* terms, const int* shi
 int refine_argmax(const float* heat, int n_maps, int H, int W, long long* argmax, float* win, void* ws, size_t ws_bytes, hipStream_t st);
 int launch_argmax_finish(const float* heat, int n_maps, int H, int W, int nblk, const float* pv, const long long* pi, long long* argmax, float* win, hipStream_t st);
 
-struct Tensor { void* ptr = nullptr; int c = 0, h = 0, w = 0; int extra = 0; };     // (micro + extra, h, w, c)
-
-struct Op {
-    enum Kind { CONV, UPSUM, BNECK_TRANS, BB_CHAIN, UPSUM_HEAD, STEM } kind = CONV;
-    int chain[4] = {-1, -1, -1, -1}, n_chain = 0;          // BB_CHAIN: packed conv indices
-    int conv = -1;            // index into packed convs
-    int conv2 = -1, conv3 = -1, dst2 = -1;     // BNECK_TRANS: transition convs and second output; CONV: fused 1x1 follower (conv2) -> dst2
-    int src0 = -1, src1 = -1, residual = -1, dst = -1;
-    int relu = 0;
-    int terms[3] = {-1, -1, -1}, shifts[3] = {0, 0, 0}, n_terms = 0;   // UPSUM
-    int res2 = -1, res3 = -1, sh3 = 0;          // CONV (bf16, stride 2): fuse-layer terms folded into the epilogue
-    // BB_CHAIN (16 channels, 4 convs) with the consuming fuse-layer sum in its epilogue: terms/shifts/n_terms as for UPSUM,
-    // dst2 = the summed output; head = 1: stage-4 output, never stored -- the 1x1 head + argmax partials are computed from it
-    // (launched by run_head_op, which knows the output buffers); dst = -1 when the pre-fuse branch tensor has no consumer
-    int head = 0;
-    int conv1f = -1;                            // STEM: conv1 packed for the frames mode (channel slot f*4 + c)
-    // CONV (64 -> 64 3x3, bf16): fuse-layer 1x1 convs on its output riding in its epilogue (packed conv index, output tensor)
-    int lin16 = -1, lin16_dst = -1, lin32 = -1, lin32_dst = -1;
-    // CONV (3x3 s2 16 -> 32, bf16): a second 3x3 s2 16 -> 16 conv on the same input in the same pass (packed conv, output, ReLU)
-    int pair = -1, pair_dst = -1, pair_relu = 0;
-};
+struct Tensor : TensorShape { void* ptr = nullptr; };          // ptr: the buffer of the lane in use (ttup_wasb::use_lane)
 
 // Certified argmax (csrc/certify.hip): state owned by a bf16 ball-detector handle
 struct CertState {
@@ -105,7 +84,7 @@ struct ttup_wasb {
         float* heat_scratch = nullptr; void* refine_ws = nullptr; long long* argmax_scratch = nullptr; float* win_scratch = nullptr;
         hipStream_t stream = nullptr; hipEvent_t done = nullptr;
     };
-    std::vector<Lane> lanes;
+    std::vector<Lane> lanes;            // they own every activation buffer from the start (ttup_wasb_create_internal)
     hipEvent_t fork = nullptr;
     // bf16 / fp32 micro-batches of consecutive forward calls share the lanes' activation and scratch buffers: a call waits for the
     // previous call's last micro-batch (whatever stream that call was issued on) before it touches them

@@ -1,38 +1,18 @@
-// a2: the WASB / HRNet ball-heatmap CNN as a static op list over NHWC buffers.
-// Graph follows balldetection/models/wasb.py: HRNet.forward :445-486, HighResolutionModule.forward :227-245,
-// fuse construction :179-222, transitions :362-396, config :514-573, WASBNet.forward :596-608.
-//
-// What is different from the reference's eager module tree (results unchanged):
-//   * BatchNorm (eval) is folded into every conv at create time;
-//   * Bottleneck conv3 (1x1 32->128) and its 1x1 downsample (64->128) + add + ReLU run as ONE two-source
-//     1x1 conv with K = 32+64 (the 128-channel pre-activation never touches HBM);
-//   * stage-4 fused outputs 1..3 (only consumed when classify_invisible=True, never set by get_model,
-//     balldetection/train.py:268) and head channels 0 and 2 (dropped at wasb.py:606) are not computed;
-//   * the batch is processed in micro-batches so that intermediate tensors stay near the Infinity Cache.
+// a2: the WASB / HRNet ball-heatmap CNN as a static op list over NHWC buffers.  This unit turns a device-free plan of the graph
+// (csrc/wasb_graph.h, from the folded convs of csrc/wasb_blob.h) into a handle, runs it (run_op, run_head_op, forward_micro,
+// forward_impl), prunes the fp32 crop net to a cone (compute_roi) and carries the C ABI; the timing entry points are in
+// csrc/wasb_timing.h.  It launches kernels and holds none.
 #include "wasb_net.h"
+#include "wasb_blob.h"
 #include <string.h>
 #include <stdlib.h>
 #include <memory>
 
 using namespace ttup;
 
-namespace {
-
-const int STAGE_CH[4] = {16, 32, 64, 128};
-
-struct BlobReader {
-    const char* p; size_t left;
-    bool read(void* dst, size_t n) { if (n > left) return false; memcpy(dst, p, n); p += n; left -= n; return true; }
-};
-
-}  // namespace
-
 ttup_wasb::~ttup_wasb() {
     cert_free(this);
     for (auto& c : convs) free_conv(&c);
-    if (lanes.empty()) {       // construction failed before the lanes were set up
-        for (auto& t : tensors) if (t.ptr) (void)hipFree(t.ptr);
-    }
     for (auto& L : lanes) {
         for (void* q : L.ptr) if (q) (void)hipFree(q);
         if (L.heat_scratch) (void)hipFree(L.heat_scratch);
@@ -50,440 +30,64 @@ ttup_wasb::~ttup_wasb() {
 
 namespace {
 
-// ---- parse the blob into folded convs (order = upliftingtabletennis_amd.arch.hrnet_convs)
-int parse_blob(const void* blob, size_t bytes, std::vector<FoldedConv>* out, int* in_ch, int* head_out,
-               std::vector<float>* head_w, std::vector<float>* head_b) {
-    BlobReader r{(const char*)blob, bytes};
-    char magic[8]; int hdr[4];
-    TTUP_REQUIRE(r.read(magic, 8) && memcmp(magic, "TTUPWSB1", 8) == 0, TTUP_EFORMAT, "wasb blob: bad magic");
-    TTUP_REQUIRE(r.read(hdr, sizeof hdr), TTUP_EFORMAT, "wasb blob: truncated header");
-    const int n = hdr[0];
-    *in_ch = hdr[1]; *head_out = hdr[2];
-    TTUP_REQUIRE(n == 72, TTUP_EFORMAT, "wasb blob: expected 72 convs, got %d", n);
-    for (int i = 0; i < n; ++i) {
-        int h[8];
-        TTUP_REQUIRE(r.read(h, sizeof h), TTUP_EFORMAT, "wasb blob: truncated at conv %d", i);
-        FoldedConv c; c.cout = h[0]; c.cin = h[1]; c.k = h[2]; c.stride = h[3];
-        const int has_bn = h[4], has_bias = h[5];
-        TTUP_REQUIRE(c.cout > 0 && c.cout <= 128 && c.cin > 0 && c.cin <= 128 && (c.k == 1 || c.k == 3), TTUP_EFORMAT,
-                     "wasb blob: conv %d has unsupported shape %dx%dx%d", i, c.cout, c.cin, c.k);
-        const size_t nw = (size_t)c.cout * c.cin * c.k * c.k;
-        c.w.resize(nw); c.bias.assign(c.cout, 0.f);
-        TTUP_REQUIRE(r.read(c.w.data(), nw * 4), TTUP_EFORMAT, "wasb blob: truncated weights of conv %d", i);
-        if (has_bias) TTUP_REQUIRE(r.read(c.bias.data(), c.cout * 4), TTUP_EFORMAT, "wasb blob: truncated bias of conv %d", i);
-        if (has_bn) {
-            std::vector<float> bn(4 * c.cout);
-            TTUP_REQUIRE(r.read(bn.data(), bn.size() * 4), TTUP_EFORMAT, "wasb blob: truncated BN of conv %d", i);
-            const float *gamma = bn.data(), *beta = gamma + c.cout, *mean = beta + c.cout, *var = mean + c.cout;
-            const size_t per = (size_t)c.cin * c.k * c.k;
-            for (int o = 0; o < c.cout; ++o) {
-                // y = (conv(x)+b - mean) * gamma / sqrt(var + eps) + beta, eps = 1e-5 (nn.BatchNorm2d default)
-                const double s = (double)gamma[o] / sqrt((double)var[o] + 1e-5);
-                for (size_t j = 0; j < per; ++j) c.w[o * per + j] = (float)((double)c.w[o * per + j] * s);
-                c.bias[o] = (float)(((double)c.bias[o] - (double)mean[o]) * s + (double)beta[o]);
-            }
-        }
-        out->push_back(std::move(c));
-    }
-    TTUP_REQUIRE(r.left == 0, TTUP_EFORMAT, "wasb blob: %zu trailing bytes", r.left);
-    const FoldedConv& head = out->back();
-    TTUP_REQUIRE(head.k == 1 && head.cin == 16 && head.cout == *head_out, TTUP_EFORMAT, "wasb blob: unexpected head shape");
-    *head_w = head.w; *head_b = head.bias;
-    return TTUP_OK;
-}
-
-// The graph switches (README, "knobs"): every net samples them for itself, all together, when its builder is set up -- the tests set
-// them in-process between two handles (never static).
-struct GraphSwitches {
-    bool fuse = !env_set("TTUP_NO_FUSE");                      // any fused kernel at all (bf16 nets)
-    bool fuse_sum = !env_set("TTUP_NO_FUSE_SUM");              // the fuse-layer sum / the head in the 16-channel chain's epilogue
-    bool fuse_lin = !env_set("TTUP_NO_FUSE_LIN");              // the 64 -> 16 / 64 -> 32 fuse convs in conv64's epilogue
-    bool pair = !env_set("TTUP_NO_PAIR");                      // the two stride-2 convs of stage 3's fuse layer in one pass
-    bool stem = !env_set("TTUP_NO_STEM");                      // the fused stem
-    bool frames_mode = !env_set("TTUP_NO_FRAMES_MODE");        // the stem reads per-frame records
-};
-
-struct Builder {
-    ttup_wasb* net;
-    const std::vector<FoldedConv>* folded;
-    const GraphSwitches sw{};          // read here, once per net
-    size_t cursor = 0;     // next folded conv in reference order
-    int rc = TTUP_OK;
-
-    int new_tensor(int c, int h, int w) {
-        Tensor t; t.c = c; t.h = h; t.w = w;
-        const size_t bytes = (size_t)net->micro * h * w * c * net->esize();
-        if (hipMalloc(&t.ptr, bytes) != hipSuccess) { set_error("hipMalloc of %zu bytes failed", bytes); rc = TTUP_ENOMEM; t.ptr = nullptr; }
-        net->tensors.push_back(t);
-        return (int)net->tensors.size() - 1;
-    }
-    const FoldedConv& next(int cout, int cin, int k, int stride) {
-        const FoldedConv& f = (*folded)[cursor++];
-        if (f.cout != cout || f.cin != cin || f.k != k || f.stride != stride) {
-            set_error("wasb blob: conv %zu is %dx%dx%d/s%d, architecture expects %dx%dx%d/s%d", cursor - 1, f.cout, f.cin, f.k, f.stride, cout, cin, k, stride);
-            rc = TTUP_EFORMAT;
-        }
-        return f;
-    }
-    int pack(const FoldedConv& a, const FoldedConv* b, int cin_pad) {
-        PackedConv p;
-        if (rc == TTUP_OK) { const int e = pack_conv(a, b, cin_pad, net->dtype, &p); if (e) rc = e; }
-        net->convs.push_back(p);
-        return (int)net->convs.size() - 1;
-    }
-    // conv op on tensor `src` -> new tensor
-    int conv(int src, int cout, int k, int stride, int relu, int residual = -1, int dst = -1) {
-        const Tensor s = net->tensors[src];
-        const FoldedConv& f = next(cout, s.c, k, stride);
-        const int pc = pack(f, nullptr, s.c);
-        if (dst < 0) dst = new_tensor(cout, (s.h + stride - 1) / stride, (s.w + stride - 1) / stride);
-        Op op; op.kind = Op::CONV; op.conv = pc; op.src0 = src; op.residual = residual; op.dst = dst; op.relu = relu;
-        net->ops.push_back(op);
-        return dst;
-    }
-    int basic_block(int x) {       // wasb.py:48-64
-        const int c = net->tensors[x].c;
-        const int t = conv(x, c, 3, 1, 1);
-        return conv(t, c, 3, 1, 1, /*residual*/ x);
-    }
-    Op bb_chain_op(int x, int n_convs, bool need_dst) {      // n_convs/2 BasicBlocks fused (bf16 path); not yet in the op list
-        const Tensor s = net->tensors[x];
-        Op op; op.kind = Op::BB_CHAIN; op.src0 = x; op.n_chain = n_convs;
-        for (int i = 0; i < n_convs; ++i) op.chain[i] = pack(next(s.c, s.c, 3, 1), nullptr, s.c);
-        op.dst = need_dst ? new_tensor(s.c, s.h, s.w) : -1;
-        return op;
-    }
-    int bb_chain(int x, int n_convs) {
-        const Op op = bb_chain_op(x, n_convs, true);
-        net->ops.push_back(op);
-        return op.dst;
-    }
-    // HighResolutionModule (wasb.py:227-245); returns fused outputs 0..n_out-1
-    std::vector<int> stage(std::vector<int> xs, int n_out, bool head_mode = false) {
-        const int nb = (int)xs.size();
-        const bool fuse = net->dtype == TTUP_DTYPE_BF16 && sw.fuse;
-        // the full-resolution branch's fuse-layer sum rides in the epilogue of its two-block chain, which is therefore emitted
-        // AFTER the lower branches and their 1x1 fuse convs (deferred below); its weights are still consumed in reference order
-        const bool fuse_sum = fuse && sw.fuse_sum && net->tensors[xs[0]].c == 16;
-        Op deferred; bool has_deferred = false;
-        const int x0_in = xs[0];
-        for (int b = 0; b < nb; ++b) {
-            const Tensor xt = net->tensors[xs[b]];
-            if (b == 0 && fuse_sum) { deferred = bb_chain_op(xs[0], 4, /*pre-fuse tensor has consumers*/ n_out > 1); has_deferred = true; xs[0] = deferred.dst; }
-            else if (fuse && xt.c == 16) xs[b] = bb_chain(xs[b], 4);                       // both blocks in one kernel
-            else if (fuse && xt.c == 32) { xs[b] = bb_chain(xs[b], 2); xs[b] = bb_chain(xs[b], 2); }
-            else { xs[b] = basic_block(xs[b]); xs[b] = basic_block(xs[b]); }
-        }
-        // reference order of the fuse convs in the state_dict: i major, j minor, chain index k
-        struct Term { int i, j; std::vector<const FoldedConv*> chain; };
-        std::vector<Term> terms;
-        for (int i = 0; i < nb; ++i)
-            for (int j = 0; j < nb; ++j) {
-                if (j == i) continue;
-                Term t; t.i = i; t.j = j;
-                if (j > i) t.chain.push_back(&next(STAGE_CH[i], STAGE_CH[j], 1, 1));
-                else for (int k = 0; k < i - j; ++k) t.chain.push_back(&next(k == i - j - 1 ? STAGE_CH[i] : STAGE_CH[j], STAGE_CH[j], 3, 2));
-                terms.push_back(t);
-            }
-        std::vector<int> outs;
-        for (int i = 0; i < n_out; ++i) {
-            const Tensor xi = net->tensors[i == 0 ? x0_in : xs[i]];       // same shape as x_i (xs[0] is -1 when the branch tensor is not stored)
-            // running sum: starts at x_i (identity term) or at the j=0 chain for i>0, in reference order
-            int acc = -1;
-            bool acc_is_xi = false;
-            std::vector<int> up_t; std::vector<int> up_s;
-            int last_chain_op = -1;               // index in net->ops of the conv that completes the running sum (j = i-1 chain)
-            // emission order: the 1x1 convs of the lower branches (j > i) first, so that a later conv's epilogue can add them
-            for (int pass = 0; pass < 2; ++pass)
-            for (int j = 0; j < nb; ++j) {
-                if ((pass == 0) != (j > i)) continue;
-                if (j == i) {
-                    if (acc < 0) { acc = xs[i]; acc_is_xi = true; }
-                    else {
-                        // x_i enters the sum after at least one chain term: fold it in as the residual of ... nothing to
-                        // run, so add it through an UPSUM term with shift 0 below
-                        up_t.push_back(xs[i]); up_s.push_back(0);
-                    }
-                    continue;
-                }
-                const Term* tm = nullptr;
-                for (auto& t : terms) if (t.i == i && t.j == j) tm = &t;
-                if (j > i) {        // 1x1 conv + BN at the low resolution, upsampled when summed
-                    const int pc = pack(*tm->chain[0], nullptr, 0);
-                    const Tensor sj = net->tensors[xs[j]];
-                    const int dst = new_tensor(STAGE_CH[i], sj.h, sj.w);
-                    // 32 -> 16 on the output of a fused 32-channel block: rides in that kernel's epilogue (one MFMA per pixel group)
-                    bool attached = false;
-                    if (fuse && sj.c == 32 && STAGE_CH[i] == 16) {
-                        for (int k = (int)net->ops.size() - 1; k >= 0 && !attached; --k) {
-                            Op& po = net->ops[k];
-                            if (po.dst != xs[j]) continue;
-                            if (po.kind == Op::BB_CHAIN && po.n_chain == 2 && po.conv2 < 0) { po.conv2 = pc; po.dst2 = dst; attached = true; }
-                            break;
-                        }
-                    }
-                    // 64 -> 16 / 64 -> 32 on the output of the branch's last 64 -> 64 conv: rides in that conv's epilogue
-                    if (!attached && fuse && sj.c == 64 && (STAGE_CH[i] == 16 || STAGE_CH[i] == 32) && sw.fuse_lin) {
-                        for (int k = (int)net->ops.size() - 1; k >= 0 && !attached; --k) {
-                            Op& po = net->ops[k];
-                            if (po.dst != xs[j]) continue;
-                            const PackedConv& pp = net->convs[po.conv >= 0 ? po.conv : 0];
-                            if (po.kind == Op::CONV && po.conv >= 0 && po.conv2 < 0 && pp.k == 3 && pp.stride == 1 && pp.cout == 64 && pp.cin_total == 64 && pp.c0 == 64 && po.src1 < 0) {
-                                if (STAGE_CH[i] == 16 && po.lin16 < 0) { po.lin16 = pc; po.lin16_dst = dst; attached = true; }
-                                else if (STAGE_CH[i] == 32 && po.lin32 < 0) { po.lin32 = pc; po.lin32_dst = dst; attached = true; }
-                            }
-                            break;
-                        }
-                    }
-                    Op op; op.kind = Op::CONV; op.conv = pc; op.src0 = xs[j]; op.dst = dst; op.relu = 0;
-                    if (!attached) net->ops.push_back(op);
-                    up_t.push_back(dst); up_s.push_back(j - i);
-                } else {            // chain of stride-2 3x3 convs; the last one adds the running sum
-                    int cur = xs[j];
-                    for (size_t k = 0; k < tm->chain.size(); ++k) {
-                        const bool last = k + 1 == tm->chain.size();
-                        const FoldedConv& f = *tm->chain[k];
-                        const int pc = pack(f, nullptr, 0);
-                        const Tensor sc = net->tensors[cur];
-                        const int dst = new_tensor(f.cout, (sc.h + 1) / 2, (sc.w + 1) / 2);
-                        Op op; op.kind = Op::CONV; op.conv = pc; op.src0 = cur; op.dst = dst; op.relu = last ? 0 : 1;
-                        if (last && acc >= 0) op.residual = acc;
-                        // 16 -> 16 on the full-resolution branch while an earlier fuse chain took the same tensor down 16 -> 32: both
-                        // convs in one pass over it (conv_s2_pair_kernel)
-                        bool paired = false;
-                        if (fuse && !last && f.cout == 16 && sc.c == 16 && sw.pair) {
-                            for (int q = (int)net->ops.size() - 1; q >= 0 && !paired; --q) {
-                                Op& po = net->ops[q];
-                                if (po.kind != Op::CONV || po.src0 != cur || po.conv < 0) continue;
-                                const PackedConv& pp = net->convs[po.conv];
-                                if (pp.k == 3 && pp.stride == 2 && pp.cout == 32 && pp.cin_total == 16 && po.pair < 0 && po.conv2 < 0 && po.src1 < 0) {
-                                    po.pair = pc; po.pair_dst = dst; po.pair_relu = op.relu; paired = true;
-                                }
-                            }
-                        }
-                        if (!paired) net->ops.push_back(op);
-                        if (last) last_chain_op = (int)net->ops.size() - 1;
-                        cur = dst;
-                    }
-                    acc = cur; acc_is_xi = false;
-                }
-            }
-            (void)acc_is_xi;
-            // the reference adds the terms in branch order j (wasb.py:236-243): x_i (shift 0) before the upsampled lower branches
-            for (size_t k = 1; k < up_t.size(); ++k)
-                for (size_t q = k; q > 0 && up_s[q] < up_s[q - 1]; --q) { std::swap(up_s[q], up_s[q - 1]); std::swap(up_t[q], up_t[q - 1]); }
-            if (i == 0 && has_deferred) {
-                // y_0 = relu(x_0 + sum_j up(1x1(x_j))) in the epilogue of the branch's block chain
-                deferred.n_terms = (int)up_t.size();
-                if (up_t.size() > 3) { set_error("fuse: more than 3 upsample terms"); rc = TTUP_EINVAL; }
-                for (size_t k = 0; k < up_t.size() && k < 3; ++k) { deferred.terms[k] = up_t[k]; deferred.shifts[k] = up_s[k]; }
-                if (head_mode) { deferred.head = 1; deferred.dst2 = -1; }
-                else deferred.dst2 = new_tensor(xi.c, xi.h, xi.w);
-                net->ops.push_back(deferred);
-                outs.push_back(deferred.dst2);
-                continue;
-            }
-            // bf16: y_i = relu(chains + x_i + up(...)) finishes in the epilogue of the last chain conv (one same-resolution term
-            // and one upsampled term fit): the element-wise pass over the branch disappears
-            if (fuse && i > 0 && last_chain_op >= 0 && up_t.size() <= 2 && net->ops[last_chain_op].dst == acc) {
-                int same = -1, upt = -1, ups = 0;
-                bool ok = true;
-                for (size_t k = 0; k < up_t.size(); ++k) {
-                    if (up_s[k] == 0 && same < 0) same = up_t[k];
-                    else if (up_s[k] > 0 && upt < 0) { upt = up_t[k]; ups = up_s[k]; }
-                    else ok = false;
-                }
-                if (ok) {
-                    Op& lc = net->ops[last_chain_op];
-                    lc.res2 = same; lc.res3 = upt; lc.sh3 = ups; lc.relu = 1;
-                    outs.push_back(lc.dst);
-                    continue;
-                }
-            }
-            // y = relu(acc + sum of upsampled / late identity terms)
-            const int dst = new_tensor(xi.c, xi.h, xi.w);
-            Op op; op.kind = Op::UPSUM; op.src0 = acc; op.dst = dst; op.n_terms = (int)up_t.size();
-            if (up_t.size() > 3) { set_error("fuse: more than 3 upsample terms"); rc = TTUP_EINVAL; }
-            for (size_t k = 0; k < up_t.size() && k < 3; ++k) { op.terms[k] = up_t[k]; op.shifts[k] = up_s[k]; }
-            net->ops.push_back(op);
-            outs.push_back(dst);
-        }
-        // convs of dead fused outputs (i >= n_out) are skipped but stay consumed from the cursor
-        return outs;
-    }
-};
-
-int build(ttup_wasb* net, const std::vector<FoldedConv>& folded) {
-    Builder b; b.net = net; b.folded = &folded;
-    const int H = net->H, W = net->W;
-    net->t_input = b.new_tensor(16, H, W);
-    // stem (wasb.py:446-451)
-    int x;
-    const bool fuse_c1 = net->dtype == TTUP_DTYPE_BF16 && b.sw.fuse;
-    int stem_a1 = -1;
-    if (fuse_c1 && b.sw.stem) {
-        // conv1 + conv2 + Bottleneck conv1 in one persistent kernel; the first 64-channel tensor never reaches HBM
-        const FoldedConv& c1 = b.next(64, net->in_ch, 3, 1);
-        const int p1 = b.pack(c1, nullptr, 16);
-        // the same conv for the stem's frames mode: input slot f*4 + c holds colour c of frame f (slot 3 of every frame and the
-        // slots past the last frame carry zero weights)
-        FoldedConv c1f = c1;
-        c1f.cin = 16; c1f.w.assign((size_t)64 * 16 * 9, 0.f);
-        for (int co = 0; co < 64 && b.rc == TTUP_OK; ++co)
-            for (int ci = 0; ci < net->in_ch; ++ci)
-                for (int t = 0; t < 9; ++t) c1f.w[((size_t)co * 16 + (ci / 3) * 4 + ci % 3) * 9 + t] = c1.w[((size_t)co * net->in_ch + ci) * 9 + t];
-        int p1f = b.pack(c1f, nullptr, 16);
-        // ... and, for triples, the 4-k-step form of that conv (csrc/conv_stem.h stem_kernel<3, true>): K = 3 tap rows x 40 slots, slot
-        // o of a row = pixel dx = o / 12, frame (o % 12) / 4, colour o % 4 (colour 3 and o >= 36: zero weights), packed as a
-        // "1x1 conv with 128 inputs" so that k-step s, lane group g, element j holds k = 32 s + 8 g + j
-        if (net->in_ch == 9) {
-            FoldedConv c1k = c1;
-            c1k.cin = 128; c1k.k = 1; c1k.w.assign((size_t)64 * 128, 0.f);
-            for (int co = 0; co < 64; ++co)
-                for (int r = 0; r < 3; ++r)
-                    for (int o = 0; o < 36; ++o) {
-                        const int dx = o / 12, f = (o % 12) / 4, col = o % 4;
-                        if (col < 3) c1k.w[(size_t)co * 128 + r * 40 + o] = c1.w[((size_t)co * net->in_ch + f * 3 + col) * 9 + r * 3 + dx];
-                    }
-            p1f = b.pack(c1k, nullptr, 0);
-        }
-        const int p2 = b.pack(b.next(64, 64, 3, 1), nullptr, 0);
-        const int p3 = b.pack(b.next(32, 64, 1, 1), nullptr, 0);
-        x = b.new_tensor(64, H, W); net->taps["stem2"] = x;
-        stem_a1 = b.new_tensor(32, H, W);
-        Op op; op.kind = Op::STEM; op.conv = p1; op.conv2 = p2; op.conv3 = p3; op.src0 = net->t_input; op.dst = x; op.dst2 = stem_a1;
-        op.conv1f = p1f;
-        net->ops.push_back(op);
-        if (b.sw.frames_mode) {
-            // (micro + nf - 1) frames of (H, W, 4) bf16: allocated through the tensor list so that every lane gets its own copy
-            Tensor t; t.c = 4; t.h = H; t.w = W; t.extra = net->in_ch / 3 - 1;
-            const size_t bytes = (size_t)(net->micro + net->in_ch / 3 - 1) * H * W * 4 * 2;
-            if (hipMalloc(&t.ptr, bytes) != hipSuccess) { set_error("hipMalloc of %zu bytes failed", bytes); b.rc = TTUP_ENOMEM; t.ptr = nullptr; }
-            net->tensors.push_back(t);
-            net->t_frames = (int)net->tensors.size() - 1;
-        }
-    } else {
-        {
-            const FoldedConv& f = b.next(64, net->in_ch, 3, 1);
-            const int pc = b.pack(f, nullptr, 16);
-            const int dst = b.new_tensor(64, H, W);
-            Op op; op.conv = pc; op.src0 = net->t_input; op.dst = dst; op.relu = 1; net->ops.push_back(op);
-            x = dst; net->taps["stem1"] = x;
-        }
-        x = b.conv(x, 64, 3, 1, 1); net->taps["stem2"] = x;
-    }
-    const size_t stem2_op = net->ops.size() - 1;
-    // layer1: Bottleneck(64 -> 32 -> 128) (wasb.py:85-105), conv3 + downsample fused into one two-source 1x1 conv;
-    // transition1 (wasb.py:454-459).  bf16: both run in one kernel and the 128-channel tensor stays in LDS.
-    std::vector<int> xs(2);
-    {
-        int a1;
-        if (stem_a1 >= 0) a1 = stem_a1;
-        else if (fuse_c1) {       // Bottleneck conv1 (1x1 64->32 + ReLU) rides in the epilogue of stem conv2
-            const int pc1 = b.pack(b.next(32, 64, 1, 1), nullptr, 0);
-            a1 = b.new_tensor(32, H, W);
-            net->ops[stem2_op].conv2 = pc1; net->ops[stem2_op].dst2 = a1;
-        } else a1 = b.conv(x, 32, 1, 1, 1);
-        const int a2 = b.conv(a1, 32, 3, 1, 1);
-        const FoldedConv& c3 = b.next(128, 32, 1, 1);
-        const FoldedConv& ds = b.next(128, 64, 1, 1);
-        const int pc = b.pack(c3, &ds, 0);
-        const bool fuse = net->dtype == TTUP_DTYPE_BF16 && b.sw.fuse && H % 2 == 0 && W % 2 == 0;
-        if (fuse) {
-            const int p5 = b.pack(b.next(16, 128, 3, 1), nullptr, 0);
-            const int p6 = b.pack(b.next(32, 128, 3, 2), nullptr, 0);
-            xs[0] = b.new_tensor(16, H, W);
-            xs[1] = b.new_tensor(32, H / 2, W / 2);
-            Op op; op.kind = Op::BNECK_TRANS; op.conv = pc; op.conv2 = p5; op.conv3 = p6; op.src0 = a2; op.src1 = x; op.dst = xs[0]; op.dst2 = xs[1];
-            net->ops.push_back(op);
-        } else {
-            const int dst = b.new_tensor(128, H, W);
-            Op op; op.conv = pc; op.src0 = a2; op.src1 = x; op.dst = dst; op.relu = 1; net->ops.push_back(op);
-            x = dst; net->taps["layer1"] = x;
-            xs[0] = b.conv(x, 16, 3, 1, 1);
-            xs[1] = b.conv(x, 32, 3, 2, 1);
-        }
-        net->taps["trans1_0"] = xs[0]; net->taps["trans1_1"] = xs[1];
-    }
-    std::vector<int> ys = b.stage(xs, 2);
-    net->taps["stage2_0"] = ys[0]; net->taps["stage2_1"] = ys[1];
-    // transition2: new branch from the last output (wasb.py:462-467)
-    xs = {ys[0], ys[1], b.conv(ys[1], 64, 3, 2, 1)};
-    ys = b.stage(xs, 3);
-    net->taps["stage3_0"] = ys[0]; net->taps["stage3_1"] = ys[1]; net->taps["stage3_2"] = ys[2];
-    xs = {ys[0], ys[1], ys[2], b.conv(ys[2], 128, 3, 2, 1)};
-    const bool head_in_chain = net->dtype == TTUP_DTYPE_BF16 && net->n_out == 1 && b.sw.fuse && b.sw.fuse_sum;
-    ys = b.stage(xs, 1, head_in_chain);
-    net->t_out = ys[0];
-    if (head_in_chain && net->ops.back().kind == Op::BB_CHAIN && net->ops.back().head) {
-        net->fused_head = true;                       // stage-4 output 0 lives only in the registers of the last block chain
-    } else if (net->dtype == TTUP_DTYPE_BF16 && net->n_out == 1 && b.sw.fuse && net->ops.back().kind == Op::UPSUM && net->ops.back().dst == ys[0]) {
-        net->ops.back().kind = Op::UPSUM_HEAD;        // stage-4 output 0 is consumed in registers and never stored
-        net->fused_head = true;
-    } else {
-        net->taps["stage4_0"] = ys[0];
-    }
-    if (b.rc) return b.rc;
-    TTUP_REQUIRE(b.cursor == folded.size() - 1, TTUP_EFORMAT, "wasb: consumed %zu of %zu convs", b.cursor, folded.size() - 1);
-    return TTUP_OK;
+// the packed convs of a block chain and the terms of the fuse-layer sum in its epilogue
+void chain_args(const ttup_wasb* net, const Op& op, const PackedConv* cv[4], BBSum* sum) {
+    for (int k = 0; k < 4; ++k) cv[k] = k < op.n_chain ? &net->convs[op.chain[k]] : nullptr;
+    sum->n_terms = op.n_terms;
+    for (int k = 0; k < op.n_terms; ++k) { sum->terms[k] = net->tensors[op.terms[k]].ptr; sum->shifts[k] = op.shifts[k]; }
 }
 
 int run_op(ttup_wasb* net, const Op& op, int mb, hipStream_t st) {
-    {
-        if (op.kind == Op::CONV) {
-            const Tensor& s = net->tensors[op.src0];
-            ConvLaunch l;
-            l.src0 = s.ptr; l.src1 = op.src1 >= 0 ? net->tensors[op.src1].ptr : nullptr;
-            l.residual = op.residual >= 0 ? net->tensors[op.residual].ptr : nullptr;
-            l.dst = net->tensors[op.dst].ptr; l.batch = mb; l.h = s.h; l.w = s.w; l.relu = op.relu; l.n_active = net->n_active;
-            if (!net->op_roi.empty() && net->roi_flag) { l.roi = net->op_roi[&op - net->ops.data()]; l.roi.flag = net->roi_flag; }
-            if (op.conv2 >= 0) { l.follow = &net->convs[op.conv2]; l.dst2 = net->tensors[op.dst2].ptr; }
-            if (op.lin16 >= 0) { l.lin16 = &net->convs[op.lin16]; l.lin16_dst = net->tensors[op.lin16_dst].ptr; }
-            if (op.lin32 >= 0) { l.lin32 = &net->convs[op.lin32]; l.lin32_dst = net->tensors[op.lin32_dst].ptr; }
-            if (op.pair >= 0) { l.pair = &net->convs[op.pair]; l.pair_dst = net->tensors[op.pair_dst].ptr; l.pair_relu = op.pair_relu; }
-            if (op.res2 >= 0) l.res2 = net->tensors[op.res2].ptr;
-            if (op.res3 >= 0) { l.res3 = net->tensors[op.res3].ptr; l.sh3 = op.sh3; }
-            const int rc = launch_conv(net->convs[op.conv], l, net->dtype, st);
-            if (rc) return rc;
-        } else if (op.kind == Op::STEM) {
-            const Tensor& s = net->tensors[op.src0];
-            const bool fm = net->frames_mode && net->t_frames >= 0 && op.conv1f >= 0;
-            const int rc = launch_stem(net->convs[fm ? op.conv1f : op.conv], net->convs[op.conv2], net->convs[op.conv3], fm ? net->tensors[net->t_frames].ptr : s.ptr,
-                                       net->tensors[op.dst].ptr, net->tensors[op.dst2].ptr, mb, s.h, s.w, st, fm ? net->in_ch / 3 : 0);
-            if (rc) return rc;
-        } else if (op.kind == Op::UPSUM_HEAD) {
-            return TTUP_OK;       // launched by forward_micro (run_head_op), which knows the output buffers
-        } else if (op.kind == Op::BB_CHAIN) {
-            if (op.head) return TTUP_OK;      // launched by forward_micro (run_head_op), which knows the output buffers
-            const Tensor& s = net->tensors[op.src0];
-            const PackedConv* cv[4] = {nullptr, nullptr, nullptr, nullptr};
-            for (int k = 0; k < op.n_chain; ++k) cv[k] = &net->convs[op.chain[k]];
-            int rc;
-            if (op.n_chain == 4 && op.n_terms > 0) {          // fuse-layer sum in the epilogue: dst2 = relu(dst + sum up(terms))
-                BBSum sum;
-                sum.n_terms = op.n_terms;
-                for (int k = 0; k < op.n_terms; ++k) { sum.terms[k] = net->tensors[op.terms[k]].ptr; sum.shifts[k] = op.shifts[k]; }
-                sum.ysum = net->tensors[op.dst2].ptr;
-                rc = launch_bb_chain(cv, 4, s.ptr, op.dst >= 0 ? net->tensors[op.dst].ptr : nullptr, mb, s.h, s.w, nullptr, nullptr, st, &sum);
-            } else {
-                rc = launch_bb_chain(cv, op.n_chain, s.ptr, net->tensors[op.dst].ptr, mb, s.h, s.w,
-                                     op.conv2 >= 0 ? &net->convs[op.conv2] : nullptr, op.dst2 >= 0 ? net->tensors[op.dst2].ptr : nullptr, st);
-            }
-            if (rc) return rc;
-        } else if (op.kind == Op::BNECK_TRANS) {
-            const Tensor& s = net->tensors[op.src0];
-            const int rc = launch_bneck_trans(net->convs[op.conv], net->convs[op.conv2], net->convs[op.conv3], s.ptr, net->tensors[op.src1].ptr,
-                                              net->tensors[op.dst].ptr, net->tensors[op.dst2].ptr, mb, s.h, s.w, st);
-            if (rc) return rc;
+    if (op.kind == Op::CONV) {
+        const Tensor& s = net->tensors[op.src0];
+        ConvLaunch l;
+        l.src0 = s.ptr; l.src1 = op.src1 >= 0 ? net->tensors[op.src1].ptr : nullptr;
+        l.residual = op.residual >= 0 ? net->tensors[op.residual].ptr : nullptr;
+        l.dst = net->tensors[op.dst].ptr; l.batch = mb; l.h = s.h; l.w = s.w; l.relu = op.relu; l.n_active = net->n_active;
+        if (!net->op_roi.empty() && net->roi_flag) { l.roi = net->op_roi[&op - net->ops.data()]; l.roi.flag = net->roi_flag; }
+        if (op.conv2 >= 0) { l.follow = &net->convs[op.conv2]; l.dst2 = net->tensors[op.dst2].ptr; }
+        if (op.lin16 >= 0) { l.lin16 = &net->convs[op.lin16]; l.lin16_dst = net->tensors[op.lin16_dst].ptr; }
+        if (op.lin32 >= 0) { l.lin32 = &net->convs[op.lin32]; l.lin32_dst = net->tensors[op.lin32_dst].ptr; }
+        if (op.pair >= 0) { l.pair = &net->convs[op.pair]; l.pair_dst = net->tensors[op.pair_dst].ptr; l.pair_relu = op.pair_relu; }
+        if (op.res2 >= 0) l.res2 = net->tensors[op.res2].ptr;
+        if (op.res3 >= 0) { l.res3 = net->tensors[op.res3].ptr; l.sh3 = op.sh3; }
+        const int rc = launch_conv(net->convs[op.conv], l, net->dtype, st);
+        if (rc) return rc;
+    } else if (op.kind == Op::STEM) {
+        const Tensor& s = net->tensors[op.src0];
+        const bool fm = net->frames_mode && net->t_frames >= 0 && op.conv1f >= 0;
+        const int rc = launch_stem(net->convs[fm ? op.conv1f : op.conv], net->convs[op.conv2], net->convs[op.conv3], fm ? net->tensors[net->t_frames].ptr : s.ptr,
+                                   net->tensors[op.dst].ptr, net->tensors[op.dst2].ptr, mb, s.h, s.w, st, fm ? net->in_ch / 3 : 0);
+        if (rc) return rc;
+    } else if (op.kind == Op::UPSUM_HEAD) {
+        return TTUP_OK;       // launched by forward_micro (run_head_op), which knows the output buffers
+    } else if (op.kind == Op::BB_CHAIN) {
+        if (op.head) return TTUP_OK;      // launched by forward_micro (run_head_op), which knows the output buffers
+        const Tensor& s = net->tensors[op.src0];
+        const PackedConv* cv[4]; BBSum sum;
+        chain_args(net, op, cv, &sum);
+        int rc;
+        if (op.n_chain == 4 && op.n_terms > 0) {          // fuse-layer sum in the epilogue: dst2 = relu(dst + sum up(terms))
+            sum.ysum = net->tensors[op.dst2].ptr;
+            rc = launch_bb_chain(cv, 4, s.ptr, op.dst >= 0 ? net->tensors[op.dst].ptr : nullptr, mb, s.h, s.w, nullptr, nullptr, st, &sum);
         } else {
-            const Tensor& d = net->tensors[op.dst];
-            const void* terms[3] = {nullptr, nullptr, nullptr};
-            for (int k = 0; k < op.n_terms; ++k) terms[k] = net->tensors[op.terms[k]].ptr;
-            Roi roi;
-            if (!net->op_roi.empty() && net->roi_flag) { roi = net->op_roi[&op - net->ops.data()]; roi.flag = net->roi_flag; }
-            const int rc = launch_upsum(net->tensors[op.src0].ptr, terms, op.shifts, op.n_terms, d.ptr, mb, d.h, d.w, d.c, net->dtype, st, net->n_active, &roi);
-            if (rc) return rc;
+            rc = launch_bb_chain(cv, op.n_chain, s.ptr, net->tensors[op.dst].ptr, mb, s.h, s.w,
+                                 op.conv2 >= 0 ? &net->convs[op.conv2] : nullptr, op.dst2 >= 0 ? net->tensors[op.dst2].ptr : nullptr, st);
         }
+        if (rc) return rc;
+    } else if (op.kind == Op::BNECK_TRANS) {
+        const Tensor& s = net->tensors[op.src0];
+        const int rc = launch_bneck_trans(net->convs[op.conv], net->convs[op.conv2], net->convs[op.conv3], s.ptr, net->tensors[op.src1].ptr,
+                                          net->tensors[op.dst].ptr, net->tensors[op.dst2].ptr, mb, s.h, s.w, st);
+        if (rc) return rc;
+    } else {
+        const Tensor& d = net->tensors[op.dst];
+        const void* terms[3] = {nullptr, nullptr, nullptr};
+        for (int k = 0; k < op.n_terms; ++k) terms[k] = net->tensors[op.terms[k]].ptr;
+        Roi roi;
+        if (!net->op_roi.empty() && net->roi_flag) { roi = net->op_roi[&op - net->ops.data()]; roi.flag = net->roi_flag; }
+        const int rc = launch_upsum(net->tensors[op.src0].ptr, terms, op.shifts, op.n_terms, d.ptr, mb, d.h, d.w, d.c, net->dtype, st, net->n_active, &roi);
+        if (rc) return rc;
     }
     return TTUP_OK;
 }
@@ -499,13 +103,10 @@ int run_head_op(ttup_wasb* net, int mb, float* heat, long long* am, float* wn, h
     if (op.kind == Op::BB_CHAIN) {
         // last block chain of the full-resolution branch + stage-4 fuse sum + 1x1 head + per-tile argmax partials
         const Tensor& s = net->tensors[op.src0];
-        const PackedConv* cv[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (int k = 0; k < op.n_chain; ++k) cv[k] = &net->convs[op.chain[k]];
         const int nblk = bb_chain_tiles_per_img(s.h, s.w);
         TTUP_REQUIRE(net->refine_ws && net->refine_ws_bytes >= (size_t)mb * nblk * 12, TTUP_EINVAL, "head: workspace too small");
-        BBSum sum;
-        sum.n_terms = op.n_terms;
-        for (int k = 0; k < op.n_terms; ++k) { sum.terms[k] = net->tensors[op.terms[k]].ptr; sum.shifts[k] = op.shifts[k]; }
+        const PackedConv* cv[4]; BBSum sum;
+        chain_args(net, op, cv, &sum);
         sum.heat = heat; sum.head_w = net->head_w_dev; sum.head_bias = net->head_bias;
         sum.pi = (long long*)net->refine_ws; sum.pv = (float*)(sum.pi + (size_t)mb * nblk);
         int rc = launch_bb_chain(cv, 4, s.ptr, nullptr, mb, s.h, s.w, nullptr, nullptr, st, &sum);
@@ -686,15 +287,15 @@ int ttup_wasb_create_internal(const void* blob, size_t blob_bytes, int height, i
                  "ttup_wasb_create: input size %dx%d must be positive multiples of 8", height, width);
     TTUP_REQUIRE(max_batch > 0, TTUP_EINVAL, "ttup_wasb_create: max_batch must be positive");
     TTUP_REQUIRE(dtype == TTUP_DTYPE_BF16 || dtype == TTUP_DTYPE_F32, TTUP_EINVAL, "ttup_wasb_create: unknown dtype %d", dtype);
-    int ndev = 0;
-    TTUP_HIP_CHECK(hipGetDeviceCount(&ndev));
-    TTUP_REQUIRE(ndev > 0, TTUP_EHIP, "ttup_wasb_create: no HIP device");
     std::vector<FoldedConv> folded;
     std::vector<float> head_w, head_b;
     int in_ch = 0, head_out = 0;
     int rc = parse_blob(blob, blob_bytes, &folded, &in_ch, &head_out, &head_w, &head_b);
     if (rc) return rc;
     TTUP_REQUIRE((in_ch == 9 || in_ch == 3) && head_out >= 1 && head_out <= 16, TTUP_EFORMAT, "wasb blob: in_ch=%d head_out=%d unsupported (ball detector 9/3, table detector 3/13)", in_ch, head_out);
+    int ndev = 0;
+    TTUP_HIP_CHECK(hipGetDeviceCount(&ndev));
+    TTUP_REQUIRE(ndev > 0, TTUP_EHIP, "ttup_wasb_create: no HIP device");
     std::unique_ptr<ttup_wasb> net(new ttup_wasb);
     net->H = height; net->W = width; net->max_batch = max_batch; net->dtype = dtype; net->in_ch = in_ch;
     net->blob.assign((const char*)blob, (const char*)blob + blob_bytes);
@@ -703,8 +304,23 @@ int ttup_wasb_create_internal(const void* blob, size_t blob_bytes, int height, i
     int micro = micro_override > 0 ? micro_override : (int)env_ll("TTUP_MICRO_BATCH", 8);
     if (micro < 1) micro = 1;
     net->micro = micro < max_batch ? micro : max_batch;
-    rc = build(net.get(), folded);
-    if (rc) return rc;
+    GraphSwitches sw;          // sampled here, once per net
+    sw.fuse = !env_set("TTUP_NO_FUSE"); sw.fuse_sum = !env_set("TTUP_NO_FUSE_SUM"); sw.fuse_lin = !env_set("TTUP_NO_FUSE_LIN");
+    sw.pair = !env_set("TTUP_NO_PAIR"); sw.stem = !env_set("TTUP_NO_STEM"); sw.frames_mode = !env_set("TTUP_NO_FRAMES_MODE");
+    const GraphPlan plan = build_graph(folded, in_ch, net->n_out, height, width, net->micro, dtype, sw);
+    if (plan.rc) return plan.rc;
+    net->ops = plan.ops; net->taps = plan.taps;
+    net->t_input = plan.t_input; net->t_out = plan.t_out; net->t_frames = plan.t_frames; net->fused_head = plan.fused_head;
+    for (const TensorShape& s : plan.tensors) { Tensor t; static_cast<TensorShape&>(t) = s; net->tensors.push_back(t); }
+    for (const ConvRequest& r : plan.convs) {
+        net->convs.emplace_back();          // in the list before it is filled: the destructor frees a partly packed conv as well
+        PackedConv& p = net->convs.back();
+        rc = pack_conv(plan.source_a(r, folded), r.b >= 0 ? &folded[r.b] : nullptr, r.cin_pad, dtype, &p);
+        if (rc) return rc;
+        TTUP_REQUIRE(p.cout == r.cout && p.cin_total == r.cin_total && p.c0 == r.c0 && p.k == r.k && p.stride == r.stride, TTUP_EINVAL,
+                     "wasb: conv %zu was packed as %d x %d+%d, k %d / s%d; the plan has %d x %d+%d, k %d / s%d", net->convs.size() - 1,
+                     p.cout, p.c0, p.cin_total - p.c0, p.k, p.stride, r.cout, r.c0, r.cin_total - r.c0, r.k, r.stride);
+    }
     // head weights of the returned channels: the ball detector keeps only channel 1 of its 3 (wasb.py:606), the table
     // detector all 13 (tabledetection/models/hrnet.py:586-589)
     {
@@ -729,9 +345,8 @@ int ttup_wasb_create_internal(const void* blob, size_t blob_bytes, int height, i
             ttup_wasb::Lane& L = net->lanes[l];
             L.ptr.assign(net->tensors.size(), nullptr);
             for (size_t i = 0; i < net->tensors.size(); ++i) {
-                const Tensor& t = net->tensors[i];
-                if (l == 0) { L.ptr[i] = t.ptr; continue; }      // lane 0 adopts the buffers the builder allocated
-                TTUP_HIP_CHECK(hipMalloc(&L.ptr[i], (size_t)(net->micro + t.extra) * t.h * t.w * t.c * net->esize()));
+                const size_t bytes = plan.tensor_bytes(i);
+                if (hipMalloc(&L.ptr[i], bytes) != hipSuccess) { L.ptr[i] = nullptr; set_error("hipMalloc of %zu bytes failed", bytes); return TTUP_ENOMEM; }
             }
             TTUP_HIP_CHECK(hipMalloc((void**)&L.heat_scratch, (size_t)net->micro * net->n_out * hw * sizeof(float)));
             TTUP_HIP_CHECK(hipMalloc(&L.refine_ws, net->refine_ws_bytes));
@@ -819,146 +434,7 @@ extern "C" int ttup_wasb_read_tap(ttup_wasb* net, const char* name, int batch, f
     return launch_nhwc_to_nchw(t.ptr, out_dev, batch, t.c, t.h, t.w, net->dtype, (hipStream_t)stream);
 }
 
-// ---- measurement aids for bench.py
-// info: 8 ints per op {kind(0 conv,1 upsum,2 bneck_trans,3 bb_chain,4 stem,5 upsum_head), algorithmic MACs per output element
-// (or cin), cout, k, stride, out_h, out_w, cin_padded / chain length}; name: the HIP kernel the op launches.
-namespace {
-void op_info(const ttup_wasb* net, int i, int* o, char* name) {
-    const Op& op = net->ops[i];
-    const Tensor& d = net->tensors[op.dst >= 0 ? op.dst : op.src0];
-    const bool bf = net->dtype == TTUP_DTYPE_BF16;
-    char nm[64] = "";
-    if (op.kind == Op::STEM) {
-        o[0] = 4; o[1] = 9 * 9 * 64 + 9 * 64 * 64 + 64 * 32; o[2] = 1; o[3] = 1; o[4] = 1; o[5] = d.h; o[6] = d.w; o[7] = 0;
-        snprintf(nm, sizeof nm, "stem_kernel");
-    } else if (op.kind == Op::BB_CHAIN) {
-        o[0] = 3; o[1] = op.n_chain * d.c * 9; o[2] = d.c; o[3] = 1; o[4] = 1; o[5] = d.h; o[6] = d.w; o[7] = op.n_chain;
-        if (op.n_chain == 4) snprintf(nm, sizeof nm, "bb_chain2_kernel<16>%s", op.head ? "+sum+head" : op.n_terms > 0 ? "+sum" : "");
-        else snprintf(nm, sizeof nm, "bb_chain_kernel<%d,1>%s", d.c, op.conv2 >= 0 ? "+1x1" : "");
-        if (op.conv2 >= 0) o[1] += 16;          // fused 1x1 32->16 follower: 32*16 MACs per pixel = 16 per output element of the block
-    } else if (op.kind == Op::BNECK_TRANS) {
-        // algorithmic MACs per output pixel of B0: 96*128 (1x1) + 1152*16 (3x3 s1) + 1152*32/4 (3x3 s2 at quarter density)
-        o[0] = 2; o[1] = 96 * 128 + 1152 * 16 + 1152 * 8; o[2] = 1; o[3] = 1; o[4] = 1; o[5] = d.h; o[6] = d.w; o[7] = 0;
-        snprintf(nm, sizeof nm, "bneck_trans_kernel");
-    } else if (op.kind == Op::CONV) {
-        const PackedConv& pc = net->convs[op.conv];
-        o[0] = 0; o[1] = (i == 0) ? net->in_ch : pc.cin_total; o[2] = pc.cout; o[3] = pc.k; o[4] = pc.stride; o[5] = d.h; o[6] = d.w; o[7] = pc.cin_total;
-        if (!bf) snprintf(nm, sizeof nm, "conv_direct_f32_kernel");
-        else if (pc.k == 3 && pc.stride == 1 && pc.cout == 64 && pc.cin_total == 64 && op.conv2 < 0) snprintf(nm, sizeof nm, "conv64_kernel%s", (op.lin16 >= 0 || op.lin32 >= 0) ? "+1x1" : "");
-        else if (op.pair >= 0) { snprintf(nm, sizeof nm, "conv_s2_pair_kernel"); o[2] = pc.cout + net->convs[op.pair].cout; }      // both convs' outputs count
-        else snprintf(nm, sizeof nm, "conv_mfma_kernel<%d,%d,%d,%d>", pc.ck, pc.cout, pc.k, pc.stride);
-    } else {
-        o[0] = op.kind == Op::UPSUM_HEAD ? 5 : 1; o[1] = op.n_terms; o[2] = d.c; o[3] = 0; o[4] = 0; o[5] = d.h; o[6] = d.w; o[7] = d.c;
-        snprintf(nm, sizeof nm, op.kind == Op::UPSUM_HEAD ? "upsum_head_kernel" : bf ? "upsum_bf16x8_kernel" : "upsum_kernel<float>");
-    }
-    if (name) { memset(name, 0, 64); memcpy(name, nm, strlen(nm)); }
-}
-}  // namespace
-
-// Every op on its own: `reps` back-to-back launches of one op between two HIP events on `stream` (inputs warm in the caches).
-extern "C" int ttup_wasb_time_ops(ttup_wasb* net, int batch, int reps, int max_ops, float* ms_out, int* info_out, int* n_ops_out, void* stream) {
-    TTUP_REQUIRE(net && ms_out && info_out && n_ops_out, TTUP_EINVAL, "ttup_wasb_time_ops: null pointer");
-    TTUP_REQUIRE(batch > 0 && batch <= net->micro && reps > 0, TTUP_EINVAL, "ttup_wasb_time_ops: batch must be in [1,%d]", net->micro);
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)net->ops.size();
-    TTUP_REQUIRE(n <= max_ops, TTUP_EINVAL, "ttup_wasb_time_ops: %d ops exceed max_ops %d", n, max_ops);
-    hipEvent_t e0, e1;
-    TTUP_HIP_CHECK(hipEventCreate(&e0));
-    TTUP_HIP_CHECK(hipEventCreate(&e1));
-    int rc = TTUP_OK;
-    net->use_lane(0);
-    for (int i = 0; i < n && rc == TTUP_OK; ++i) {
-        const Op& op = net->ops[i];
-        auto once = [&]() { return (op.kind == Op::UPSUM_HEAD || op.head) ? run_head_op(net, batch, net->heat_scratch, net->argmax_scratch, net->win_scratch, st) : run_op(net, op, batch, st); };
-        rc = once();                       // warm-up launch of this op
-        if (rc == TTUP_OK) {
-            (void)hipEventRecord(e0, st);
-            for (int r = 0; r < reps && rc == TTUP_OK; ++r) rc = once();
-            (void)hipEventRecord(e1, st);
-            (void)hipEventSynchronize(e1);
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, e0, e1);
-            ms_out[i] = ms / reps;
-        }
-        op_info(net, i, info_out + 8 * i, nullptr);
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *n_ops_out = n;
-    return rc;
-}
-
-// The whole graph in order, as the forward pass launches it (one micro-batch on lane 0, `stream`), with a HIP event between
-// consecutive ops: ms_out[i] = average time from the end of op i-1 to the end of op i over `reps` passes, i.e. the launch
-// duration of op i with the cache state it really sees.  This is what bench.py's `roofline` is computed from and what the
-// rocprofv3 kernel trace of the same run (TTUP_LANES=1) reports per kernel.  names_out: max_ops x 64 chars.
-extern "C" int ttup_wasb_time_graph(ttup_wasb* net, int batch, int reps, int max_ops, float* ms_out, int* info_out, char* names_out,
-                                    int* n_ops_out, void* stream) {
-    TTUP_REQUIRE(net && ms_out && info_out && n_ops_out, TTUP_EINVAL, "ttup_wasb_time_graph: null pointer");
-    TTUP_REQUIRE(batch > 0 && batch <= net->micro && reps > 0, TTUP_EINVAL, "ttup_wasb_time_graph: batch must be in [1,%d]", net->micro);
-    hipStream_t st = (hipStream_t)stream;
-    const int n = (int)net->ops.size();
-    TTUP_REQUIRE(n <= max_ops, TTUP_EINVAL, "ttup_wasb_time_graph: %d ops exceed max_ops %d", n, max_ops);
-    std::vector<hipEvent_t> ev(n + 1);
-    for (auto& e : ev) TTUP_HIP_CHECK(hipEventCreate(&e));
-    std::vector<double> acc(n, 0.0);
-    std::vector<std::string> exact(n);          // the device kernel each op launched (kernel_note of its launcher), as rocprofv3 names it
-    int rc = TTUP_OK;
-    net->use_lane(0);
-    for (int r = -1; r < reps && rc == TTUP_OK; ++r) {          // pass -1 = warm-up
-        (void)hipEventRecord(ev[0], st);
-        for (int i = 0; i < n && rc == TTUP_OK; ++i) {
-            const Op& op = net->ops[i];
-            kernel_note_reset();
-            rc = (op.kind == Op::UPSUM_HEAD || op.head) ? run_head_op(net, batch, net->heat_scratch, net->argmax_scratch, net->win_scratch, st) : run_op(net, op, batch, st);
-            (void)hipEventRecord(ev[i + 1], st);
-            if (r < 0) exact[i] = kernel_noted();
-        }
-        (void)hipEventSynchronize(ev[n]);
-        if (r >= 0) for (int i = 0; i < n; ++i) { float ms = 0.f; (void)hipEventElapsedTime(&ms, ev[i], ev[i + 1]); acc[i] += ms; }
-    }
-    for (int i = 0; i < n; ++i) {
-        ms_out[i] = (float)(acc[i] / reps);
-        char nm[64];
-        op_info(net, i, info_out + 8 * i, nm);
-        if (names_out) {
-            // "<device kernel template-id><+epilogue variant>": the op-level label keeps only its '+...' suffix when the launcher left a note
-            std::string full = exact[i].empty() ? std::string(nm) : exact[i] + (strchr(nm, '+') ? strchr(nm, '+') : "");
-            memset(names_out + 64 * i, 0, 64);
-            memcpy(names_out + 64 * i, full.c_str(), full.size() < 63 ? full.size() : 63);
-        }
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
-    *n_ops_out = n;
-    return rc;
-}
-
-// The same launches back to back, `reps` passes between ONE pair of events (no event between the ops: an event record between two
-// kernels is a packet of its own on the queue, and the per-op intervals of ttup_wasb_time_graph each include one).  ms_out[0] = the
-// average duration of a pass: what one lane of the pipeline spends on a micro-batch.
-extern "C" int ttup_wasb_time_replay(ttup_wasb* net, int batch, int reps, float* ms_out, void* stream) {
-    TTUP_REQUIRE(net && ms_out, TTUP_EINVAL, "ttup_wasb_time_replay: null pointer");
-    TTUP_REQUIRE(batch > 0 && batch <= net->micro && reps > 0, TTUP_EINVAL, "ttup_wasb_time_replay: batch must be in [1,%d]", net->micro);
-    hipStream_t st = (hipStream_t)stream;
-    hipEvent_t e0, e1;
-    TTUP_HIP_CHECK(hipEventCreate(&e0));
-    TTUP_HIP_CHECK(hipEventCreate(&e1));
-    int rc = TTUP_OK;
-    net->use_lane(0);
-    for (int r = -1; r < reps && rc == TTUP_OK; ++r) {          // pass -1 = warm-up
-        if (r == 0) (void)hipEventRecord(e0, st);
-        for (const Op& op : net->ops) {
-            rc = (op.kind == Op::UPSUM_HEAD || op.head) ? run_head_op(net, batch, net->heat_scratch, net->argmax_scratch, net->win_scratch, st) : run_op(net, op, batch, st);
-            if (rc != TTUP_OK) break;
-        }
-    }
-    (void)hipEventRecord(e1, st);
-    (void)hipEventSynchronize(e1);
-    float ms = 0.f;
-    if (rc == TTUP_OK) { (void)hipEventElapsedTime(&ms, e0, e1); ms_out[0] = ms / reps; }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return rc;
-}
+#include "wasb_timing.h"
 
 extern "C" int ttup_preprocess_triples(const uint8_t* frames_dev, int n_frames, int src_h, int src_w, int dst_h, int dst_w,
                                        float* out_dev, void* stream) {
