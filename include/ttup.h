@@ -33,6 +33,8 @@ extern "C" {
 #define TTUP_ENOMEM      4
 #define TTUP_EMASK       5   /* uplift mask is not {0,1} with at least one 0: the reference's
                                 ValueError at uplifting/model.py:541-546                */
+#define TTUP_ESTALE      6   /* the handle's weights were trained (ttup_uplift_opt_step): its packed
+                                forward weights are stale, build an inference model from the trainer */
 
 /* activation / arithmetic type of the CNN */
 #define TTUP_DTYPE_BF16  0   /* bf16 storage, bf16 MFMA, fp32 accumulate (production)   */
@@ -49,6 +51,7 @@ extern "C" {
 typedef struct ttup_wasb   ttup_wasb;
 typedef struct ttup_uplift ttup_uplift;
 typedef struct ttup_vitpose ttup_vitpose;
+typedef struct ttup_uplift_opt ttup_uplift_opt;
 
 int         ttup_version(void);
 /* 16 hex digits: the hash of the sources (every .hip and .h under csrc/, include/ttup.h) and compiler flags this library was built
@@ -295,7 +298,7 @@ int ttup_uplift_stage_info(ttup_uplift* net, long long* out_host);
  * reference trains, get_model('connectstage', size, 'dynamic', time_rotation):
  *   loss_rot = sum_b ||pred_rot_b - rot_b||_2,  loss_pos = sum (pred_pos - r_world)^2 mask / sum mask,  loss = loss_rot + loss_pos.
  * A handle that holds any other variant is refused with TTUP_EINVAL before anything touches a device.  Clipping, the optimizer and
- * the EMA are not part of it.
+ * the EMA follow in ttup_uplift_opt_step (below).
  *
  * ttup_uplift_grad_layout: the flat gradient buffer holds the tensors of arch.uplift_variant_schema(name, size, mode) in that
  * order, without the `*.rotary_emb.inv_freq` buffers.  *n_floats = its length, *n_tensors = the number of tensors; offsets_host /
@@ -322,6 +325,51 @@ size_t ttup_uplift_grad_workspace_bytes(ttup_uplift* net, int batch, int len);
 int    ttup_uplift_loss_grad(ttup_uplift* net, const float* ball_dev, const float* table_dev, const float* mask_dev, const float* times_dev,
                              const float* r_world_dev, const float* rotation_dev, int batch, int len, int flags, void* workspace,
                              size_t workspace_bytes, float* grad_dev, float* loss_dev, float* rot_dev, float* pos_dev, void* stream);
+
+/* ---------------------------------------------------------------- uplift optimizer step: clip, Adam, EMA (csrc/uplift_opt.hip)
+ * Replaces, for one batch, what uplifting/train.py:129-132 does after loss.backward():
+ *   torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm); optimizer.step() (torch.optim.Adam, no weight decay, no amsgrad);
+ *   model_ema = update_ema(model, model_ema, ema_decay).
+ *
+ * ttup_opt_flat_step: the raw step on flat device buffers of any length.  param, m (exp_avg), v (exp_avg_sq), ema: n floats each,
+ * updated in place; grad: n + hole_len floats, read only.  Element i of the four pairs with gradient element
+ * i + (i >= hole_begin ? hole_len : 0), 0 <= hole_begin <= n: the relation between a handle's plain weights and the gradient layout,
+ * whose embed.* block the plain weights lack.  The hole's gradient entries count towards the norm (the layout holds zeros there)
+ * and touch no parameter.  step: the 1-based count of this step (bias corrections and step size are computed from it on the host in
+ * double, as torch.optim.Adam does).  scratch: ttup_opt_flat_scratch_bytes() bytes, 8-byte aligned, private to the call while it
+ * runs.  norm_out (nullable): receives the gradient's total L2 norm before clipping, one float.  Buffers must be 4-byte aligned;
+ * 16-byte aligned ones are accessed 16 bytes at a time.  Three launches on `stream`, no synchronisation:
+ *   norm = sqrt(sum g^2) with fp64 partial sums in a fixed tree;  c = min(1, max_norm / (norm + 1e-6));  g = c g;
+ *   m += (1 - beta1) (g - m);  v = v beta2 + (1 - beta2) g g;  denom = sqrt(v) / sqrt(1 - beta2^step) + eps;
+ *   param += -(lr / (1 - beta1^step)) m / denom;  ema = ema_decay ema + (1 - ema_decay) param
+ * in fp32, in the operation order of torch's own kernels.  No floating-point atomics: two calls on equal inputs return equal bits.
+ * A non-finite gradient propagates as in torch (error_if_nonfinite=False).
+ *
+ * ttup_uplift_opt_create: optimizer state for the weights of a 'connectstage' / 'dynamic' handle (any other variant: TTUP_EINVAL
+ * before a device is touched): m and v zero, ema a copy of the weights (train.py:58), step count 0.  The handle must outlive it.
+ * ttup_uplift_opt_step: one step on the handle's plain fp32 weights -- the weights ttup_uplift_loss_grad reads, so gradients ->
+ * step -> gradients is consistent -- from grad_flat_dev, the buffer ttup_uplift_loss_grad filled (ttup_uplift_grad_layout).  The
+ * handle's PACKED weights, which ttup_uplift_forward reads, are not updated: from the first step on the handle is marked trained
+ * and ttup_uplift_forward on it returns TTUP_ESTALE without running.  To serve trained weights, read them back
+ * (ttup_uplift_opt_read) and create a new handle from them (uplift.UpliftTrainer.model).
+ * ttup_uplift_opt_read / _load: copy one of the four buffers (TTUP_OPT_*) to / from a caller-allocated device buffer in
+ * gradient-layout order (ttup_uplift_grad_layout: n_floats entries); read writes zeros to the embed.* slots, load ignores them.
+ * ttup_uplift_opt_set_step / _get_step: the number of steps taken so far (resume). */
+#define TTUP_OPT_PARAM 0
+#define TTUP_OPT_EMA   1
+#define TTUP_OPT_M     2
+#define TTUP_OPT_V     3
+size_t ttup_opt_flat_scratch_bytes(void);
+int    ttup_opt_flat_step(float* param_dev, const float* grad_dev, float* m_dev, float* v_dev, float* ema_dev, long long n, long long hole_begin,
+                          long long hole_len, double lr, double beta1, double beta2, double eps, double ema_decay, double max_norm, long long step,
+                          void* scratch_dev, float* norm_out_dev, void* stream);
+int    ttup_uplift_opt_create(ttup_uplift* net, double lr, double beta1, double beta2, double eps, double ema_decay, double max_norm, ttup_uplift_opt** out);
+void   ttup_uplift_opt_destroy(ttup_uplift_opt* opt);
+int    ttup_uplift_opt_step(ttup_uplift_opt* opt, const float* grad_flat_dev, float* norm_out_dev, void* stream);
+int    ttup_uplift_opt_read(ttup_uplift_opt* opt, int which, float* out_dev, void* stream);
+int    ttup_uplift_opt_load(ttup_uplift_opt* opt, int which, const float* in_dev, void* stream);
+int    ttup_uplift_opt_set_step(ttup_uplift_opt* opt, long long step);
+int    ttup_uplift_opt_get_step(ttup_uplift_opt* opt, long long* step_host);
 
 /* ---------------------------------------------------------------- a7: spin frame change
  * Replaces transform_rotationaxes (uplifting/helper.py:394-420): rot (B,3), pos (B,T,3) -> out (B,3). */

@@ -6,8 +6,9 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TTUP_LIB', os.path.join(_HERE, 'libttup.so'))     # TTUP_LIB: alternative build (ablation experiments)
 
-OK, EINVAL, EFORMAT, EHIP, ENOMEM, EMASK = 0, 1, 2, 3, 4, 5
+OK, EINVAL, EFORMAT, EHIP, ENOMEM, EMASK, ESTALE = 0, 1, 2, 3, 4, 5, 6
 DTYPE_BF16, DTYPE_F32 = 0, 1
+OPT_PARAM, OPT_EMA, OPT_M, OPT_V = 0, 1, 2, 3
 REFINE_BALL, REFINE_TABLE = 0, 1
 
 _c = ctypes
@@ -60,6 +61,15 @@ SIGNATURES = {
     'ttup_uplift_grad_layout': (_i, [_vp, _vp, _vp, _vp, _vp, _i]),
     'ttup_uplift_grad_workspace_bytes': (_sz, [_vp, _i, _i]),
     'ttup_uplift_loss_grad': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    'ttup_opt_flat_scratch_bytes': (_sz, []),
+    'ttup_opt_flat_step': (_i, [_vp, _vp, _vp, _vp, _vp, _c.c_longlong, _c.c_longlong, _c.c_longlong] + [_c.c_double] * 6 + [_c.c_longlong, _vp, _vp, _vp]),
+    'ttup_uplift_opt_create': (_i, [_vp] + [_c.c_double] * 6 + [_c.POINTER(_vp)]),
+    'ttup_uplift_opt_destroy': (None, [_vp]),
+    'ttup_uplift_opt_step': (_i, [_vp, _vp, _vp, _vp]),
+    'ttup_uplift_opt_read': (_i, [_vp, _i, _vp, _vp]),
+    'ttup_uplift_opt_load': (_i, [_vp, _i, _vp, _vp]),
+    'ttup_uplift_opt_set_step': (_i, [_vp, _c.c_longlong]),
+    'ttup_uplift_opt_get_step': (_i, [_vp, _c.POINTER(_c.c_longlong)]),
     'ttup_transform_rotationaxes': (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     'ttup_trajgen_max_samples': (_i, []),
     'ttup_trajgen_workspace_bytes': (_sz, [_i]),

@@ -190,6 +190,24 @@ def uplift_grad_layout(size='large'):
     return out, off
 
 
+def uplift_grad_hole(size='large'):
+    """(begin, length) of the one stretch of the gradient layout the handle's plain device weights lack: the `embed.*` tensors,
+    right after `cls_token`.  Plain element i pairs with layout element i + (length if i >= begin else 0); the plain weights hold
+    n_floats - length entries (csrc/uplift_opt.hip walks the two side by side)."""
+    layout, n = uplift_grad_layout(size)
+    hole = [(off, _numel(shape)) for _, shape, off, used in layout if not used]
+    begin, end = hole[0][0], hole[-1][0] + hole[-1][1]
+    assert sum(c for _, c in hole) == end - begin, 'the unused tensors are not one contiguous stretch'
+    return begin, end - begin
+
+
+def _numel(shape):
+    n = 1
+    for s in shape:
+        n *= s
+    return n
+
+
 def uplift_layers(size='large'):
     """Layer-prefix lists (pos_layers, layers, secondstage) for a 'connectstage' model."""
     return uplift_variant_layers('connectstage', size, 'dynamic')

@@ -620,6 +620,7 @@ extern "C" int ttup_uplift_forward(ttup_uplift* net, const float* ball_dev, cons
     TTUP_REQUIRE(net && ball_dev && table_dev && mask_dev && times_dev && rot_dev && pos_dev, TTUP_EINVAL, "ttup_uplift_forward: null pointer");
     TTUP_REQUIRE(batch >= 0 && batch <= net->max_batch, TTUP_EINVAL, "ttup_uplift_forward: batch %d outside [0,%d]", batch, net->max_batch);
     TTUP_REQUIRE(len > 0 && len <= net->max_len, TTUP_EINVAL, "ttup_uplift_forward: sequence length %d outside [1,%d]", len, net->max_len);
+    TTUP_REQUIRE(!net->trained, TTUP_ESTALE, "ttup_uplift_forward: this handle's weights were trained, its packed weights are stale: build an inference model from the trainer");
     hipStream_t st = (hipStream_t)stream;
     if (batch == 0) return TTUP_OK;
     TTUP_HIP_CHECK(hipMemsetAsync(net->flags_dev, 0, sizeof(int), st));

@@ -75,6 +75,7 @@ struct ttup_uplift {
     // 'connectstage' / 'dynamic' only: every record of the blob after inv_freq as plain fp32, in blob order -- which is the order of
     // arch.uplift_variant_schema without the inv_freq buffers and the embed.* tensors (csrc/uplift_grad.hip: dX needs W itself)
     float* plain = nullptr; long long plain_floats = 0;
+    bool trained = false;          // ttup_uplift_opt_step has changed `plain` (csrc/uplift_opt.hip): the packed weights below no longer match it
     // scratch (sized for `chunk` trajectories of max_len tokens)
     float *x = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *x2 = nullptr, *tok = nullptr, *ttok = nullptr, *h1 = nullptr;
     float *m1 = nullptr, *m2 = nullptr, *tmask = nullptr, *txy = nullptr;

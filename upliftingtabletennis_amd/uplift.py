@@ -126,6 +126,115 @@ class MultiStageModel:
         return {'graphs': int(out[0]), 'off': bool(out[1]), 'replays': int(out[2]), 'stage_launches': int(st.value)}
 
 
+class UpliftTrainer:
+    """The reference's training step (uplifting/train.py:113-132) on the device: `loss_and_grad`, then gradient clipping, torch.optim.Adam
+    and the EMA of the weights in one native step (csrc/uplift_opt.hip).  Defaults: uplifting/config.py and train.py:73, :129.
+
+    It owns a private MultiStageModel whose plain fp32 weights the step updates in place; that model's packed forward weights go
+    stale with the first step, so it is never handed out: `model()` builds a fresh inference model from the current weights
+    (parameters -> host -> weights.pack_uplift_blob -> ttup_uplift_create, the route every model takes).  `ema_state_dict` starts the
+    EMA from other weights than `state_dict` (resume); by default it is a copy, as train.py:58.
+    Only connectstage/dynamic is trained (arch.UPLIFT_GRAD_VARIANT): `name` / `mode` exist so that another variant is refused with
+    a ValueError before the native library is touched, as loss_and_grad refuses it.
+    Not here: the epoch loop, the val / val_real metrics, checkpoint selection."""
+
+    def __init__(self, state_dict, size='large', time_rotation='new', lr=1e-4, betas=(0.9, 0.999), eps=1e-8, ema_decay=0.999, max_grad_norm=5.0,
+                 transform_mode='global', max_batch=64, max_len=128, device='cuda:0', ema_state_dict=None, name='connectstage', mode='dynamic'):
+        arch.check_uplift_variant(name, size, mode, time_rotation)
+        arch.check_uplift_grad_variant(name, mode)
+        if transform_mode not in ('global', 'local'):
+            raise ValueError("transform_mode should be 'global' or 'local'")
+        self.size, self.time_rotation, self.transform_mode = size, time_rotation, transform_mode
+        self.hyper = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), ema_decay=float(ema_decay), max_grad_norm=float(max_grad_norm))
+        self._model = MultiStageModel(state_dict, size=size, max_batch=max_batch, max_len=max_len, device=device, time_rotation=time_rotation)
+        self.device, self._lib = self._model.device, self._model._lib
+        self._layout, self._n = self._model.grad_layout()
+        # what no step changes: the embed.* tensors (held, never read: no gradient, so Adam skips them) and the inv_freq buffers
+        self._fixed = {k: torch.as_tensor(weights._np(state_dict[k])).clone() for k, _ in arch.uplift_schema(size)
+                       if k.endswith('.inv_freq') or k.startswith('embed.')}
+        self._opt = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.ttup_uplift_opt_create(self._model._handle, self.hyper['lr'], *self.hyper['betas'], self.hyper['eps'], self.hyper['ema_decay'],
+                                                        self.hyper['max_grad_norm'], ctypes.byref(self._opt)))
+        if ema_state_dict is not None:
+            self._load(_lib.OPT_EMA, ema_state_dict)
+
+    def __del__(self):
+        h, self._opt = getattr(self, '_opt', None), None
+        if h:
+            self._lib.ttup_uplift_opt_destroy(h)          # before the model's handle, which it points to
+        self._model = None
+
+    def step(self, ball_pos, table_pos, mask, times, r_world, rotation, check_mask=True):
+        """One training step on a batch (arguments as MultiStageModel.loss_and_grad) -> (loss_rot, loss_pos, grad_norm): 0-d device
+        tensors, the losses of the weights BEFORE the step and the gradient's total norm before clipping.  Everything runs on the
+        current stream; with check_mask=False nothing synchronises with the host."""
+        loss_rot, loss_pos, grads = self._model.loss_and_grad(ball_pos, table_pos, mask, times, r_world, rotation, self.transform_mode, check_mask)
+        norm = torch.empty((1,), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.ttup_uplift_opt_step(self._opt, _lib.ptr(grads.flat), _lib.ptr(norm), _lib.stream_ptr()))
+        return loss_rot, loss_pos, norm[0]
+
+    @property
+    def steps(self):
+        n = ctypes.c_longlong(0)
+        _lib.check(self._lib.ttup_uplift_opt_get_step(self._opt, ctypes.byref(n)))
+        return int(n.value)
+
+    def _read(self, which):
+        """One of the four device buffers in gradient-layout order -> {parameter name: CPU tensor} (embed.* slots: zeros)."""
+        flat = torch.empty((self._n,), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.ttup_uplift_opt_read(self._opt, which, _lib.ptr(flat), _lib.stream_ptr()))
+        flat = flat.cpu()
+        return {k: flat[off:off + _numel(shape)].view(shape).clone() for k, shape, off, _ in self._layout}
+
+    def _load(self, which, tensors):
+        flat = torch.zeros((self._n,), dtype=torch.float32)
+        for k, shape, off, used in self._layout:
+            if used:
+                t = torch.as_tensor(weights._np(tensors[k]), dtype=torch.float32)
+                if tuple(t.shape) != tuple(shape):
+                    raise ValueError('%s: expected shape %s, got %s' % (k, tuple(shape), tuple(t.shape)))
+                flat[off:off + _numel(shape)] = t.reshape(-1)
+        flat = flat.to(self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.ttup_uplift_opt_load(self._opt, which, _lib.ptr(flat), _lib.stream_ptr()))
+            torch.cuda.current_stream().synchronize()          # `flat` dies with this call
+
+    def state_dict(self, ema=False):
+        """The reference's names -> CPU tensors, in its order: loadable strict=True by get_model('connectstage', size, 'dynamic', .).
+        embed.* and the inv_freq buffers are the initial dict's, for the EMA too (the reference's update_ema moves them
+        by rounding alone)."""
+        got = self._read(_lib.OPT_EMA if ema else _lib.OPT_PARAM)
+        return {k: (self._fixed[k].clone() if k in self._fixed else got[k]) for k, _ in arch.uplift_schema(self.size)}
+
+    def model(self, ema=True, **kw):
+        """A fresh MultiStageModel for inference on the current (EMA) weights, packed on the host like any other model."""
+        kw = dict(dict(max_batch=self._model.max_batch, max_len=self._model.max_len, device=self.device), **kw)
+        return MultiStageModel(self.state_dict(ema), size=self.size, time_rotation=self.time_rotation, **kw)
+
+    def optimizer_state(self):
+        """{'step', 'exp_avg': {name: tensor}, 'exp_avg_sq': {name: tensor}} of the parameters Adam holds state for (not embed.*)."""
+        used = [k for k, _, _, u in self._layout if u]
+        m, v = self._read(_lib.OPT_M), self._read(_lib.OPT_V)
+        return {'step': self.steps, 'exp_avg': {k: m[k] for k in used}, 'exp_avg_sq': {k: v[k] for k in used}}
+
+    def load_optimizer_state(self, state):
+        self._load(_lib.OPT_M, state['exp_avg'])
+        self._load(_lib.OPT_V, state['exp_avg_sq'])
+        _lib.check(self._lib.ttup_uplift_opt_set_step(self._opt, int(state['step'])))
+
+    def save(self, path, ema=True, epoch=0):
+        """Write the reference's checkpoint format (uplifting/helper.py:371-391 save_model): what inference.load_uplifting_model and
+        interface.UpliftingModel(model_path=...) open, and the reference's own inference_uplifting.load_model."""
+        h = self.hyper
+        info = {'epoch': int(epoch), 'lr': h['lr'], 'name': 'connectstage', 'size': self.size, 'ema_decay': h['ema_decay'], 'tabletoken_mode': 'dynamic',
+                'time_rotation': self.time_rotation, 'transform_mode': self.transform_mode}
+        ident = 'lr:%.2e_name:connectstage_mode:dynamic_size:%s_tr:%s_trans:%s' % (h['lr'], self.size, self.time_rotation, self.transform_mode)
+        torch.save({'model_state_dict': self.state_dict(ema), 'identifier': ident, 'additional_info': info}, path)
+
+
 def get_model(name='connectstage', size='large', mode='dynamic', time_rotation='new', state_dict=None, **kw):
     """Mirror of uplifting/model.py:574-603: every (name, size, mode, time_rotation) the reference builds, and its AssertionError /
     ValueError for the rest -- raised before the native library is touched."""
