@@ -1,8 +1,10 @@
-"""fp32 torch restatement of the reference ViTPose-small forward (balldetection/models/vitpose.py over
+"""Torch restatement (fp32, or fp64 with ``dtype=torch.float64``) of the reference ViTPose-small forward (balldetection/models/vitpose.py over
 vit_pose/vit_models/backbone/vit.py and head/topdown_heatmap_simple_head.py), written from the contract so that the CPU tests can
 check it against the goldens the reference itself produced: Conv2d(k16,s16,p2: vit.py:222 with ratio 1) patch embedding, + pos_embed[1:] + pos_embed[:1],
 12 pre-LN blocks (LayerNorm eps 1e-6, 12 heads of 32, exact-erf GELU), last_norm, two ConvTranspose2d(k4,s2,p1) + BN (eps 1e-5,
-running statistics) + ReLU, final 1x1 conv with bias."""
+running statistics) + ReLU, final 1x1 conv with bias.  Both precisions are pinned to the reference's heatmaps: at the golden
+shapes of tests/golden/vitpose.npz (test_vitpose_oracle.py, fp32) and at the token-count and border edges of
+tests/golden/vitpose_edges.npz (test_vitpose_edges_host.py, fp32 and fp64)."""
 import torch
 import torch.nn.functional as F
 

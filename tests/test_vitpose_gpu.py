@@ -15,14 +15,19 @@ HEAT_BAR = 5.3e-6
 CASES = ['ball_160x288', 'ball_96x176', 'table_96x176', 'ball_640x1152']
 
 
-def _run(g, name, micro_batch=0, batch=None):
+def _net_and_input(g, name, micro_batch=0):
     ws, xs, b, cin, cout, h, w, full = [int(v) for v in g[name + '/meta']]
     sd = weights.random_vitpose_state_dict(ws, in_ch=cin, out_ch=cout, resolution=(w, h))
     x, _ = synth.vitpose_inputs(xs, b, cin, h, w)
     net = vitpose.ViTPoseNet(sd, in_ch=cin, out_ch=cout, resolution=(w, h), max_batch=b, micro_batch=micro_batch)
-    heat, idx, win = net.forward(torch.from_numpy(x[:batch]).cuda(), want_heatmap=True, want_peaks=True)
+    return net, torch.from_numpy(x).cuda(), (b, cin, cout, h, w, full)
+
+
+def _run(g, name, micro_batch=0, batch=None):
+    net, x, meta = _net_and_input(g, name, micro_batch)
+    heat, idx, win = net.forward(x[:batch], want_heatmap=True, want_peaks=True)
     torch.cuda.synchronize()
-    return heat, idx, win, (b, cin, cout, h, w, full)
+    return heat, idx, win, meta
 
 
 def _heat_err(g, name, heat, full):
@@ -60,14 +65,20 @@ def test_heatmaps_argmax_refine_match_reference(golden, name):
 
 @pytest.mark.parametrize('micro,batch', [(2, 3), (2, 1), (1, 3)])
 def test_batch_tails(golden, micro, batch):
-    """batch 1, an odd batch, and batches larger than the handle's micro-batch give the full batch's per-sample results."""
+    """batch 1, an odd batch, and batches larger than the handle's micro-batch give the full batch's per-sample results: the
+    reference's within the bar, and the one-sample call's bit for bit (no output row's reduction order depends on the batch)."""
     g = golden('vitpose.npz')
     name = 'ball_96x176'
-    heat, idx, _, (b, cin, cout, h, w, _) = _run(g, name, micro_batch=micro, batch=batch)
+    net, x, (b, cin, cout, h, w, _) = _net_and_input(g, name, micro_batch=micro)
+    heat, idx, win = net.forward(x[:batch], want_heatmap=True, want_peaks=True)
+    torch.cuda.synchronize()
     ref = g[name + '/heat'][:batch]
     assert heat.shape == ref.shape
     assert np.abs(heat.cpu().numpy() - ref).max() <= HEAT_BAR * (ref.max() - ref.min())
     assert np.array_equal(idx.cpu().numpy(), g[name + '/argmax'][:batch * cout])
+    for i in range(batch):
+        h1, i1, w1 = net.forward(x[i:i + 1], want_heatmap=True, want_peaks=True)
+        assert torch.equal(h1, heat[i:i + 1]) and torch.equal(i1, idx[i * cout:(i + 1) * cout]) and torch.equal(w1, win[i * cout:(i + 1) * cout])
 
 
 def test_rejects_bad_sizes():
