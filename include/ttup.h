@@ -188,9 +188,9 @@ int ttup_wasb_certify_flags(ttup_wasb* net, int batch, int* flags_dev, void* str
  * (float32 (batch); +inf where there was one candidate or the heatmap was not resolved).  A margin below the accuracy of the fp32
  * path against the reference's own fp32 arithmetic marks a heatmap whose argmax the reference itself does not determine. */
 int ttup_wasb_certify_margins(ttup_wasb* net, int batch, float* margin_dev, void* stream);
-/* crops the following forward calls may use (default: max_batch, i.e. one per heatmap): the call enqueues ceil(budget / 64) fp32
- * passes sized on the device, so a caller that knows its typical crop count (stats / status of earlier calls) saves the empty
- * passes; heatmaps beyond the budget are flagged 2 (64: 128 since ABI 103, TTUP_CERT_CH) */
+/* crops the following forward calls may use (default: max_batch, i.e. one per sample): the call enqueues ceil(budget / CH) fp32
+ * passes sized on the device (CH = min(max_batch, 128) crops per pass; 64 before ABI 103; TTUP_CERT_CH), so a caller that knows its
+ * typical crop count (stats / status of earlier calls) saves the empty passes; heatmaps beyond the budget are flagged 2 */
 int ttup_wasb_certify_budget(ttup_wasb* net, int max_crops);
 /* running counters of the handle since creation / the last reset, copied to TWELVE long longs on the host (synchronises): [0] heatmaps,
  * [1] single candidate (status 0, audit picks included), [2] resolved on fp32 crops (status 1), [3] not certified (status 2, = [8] + [9]

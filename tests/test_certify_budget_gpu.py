@@ -19,7 +19,7 @@ if has_gpu():
 
 W, H = 640, 352
 K_CAND = 256                  # candidates kept per heatmap (csrc/wasb_net.h CertState::K)
-FRAME_CROPS = 32              # crops one frame may use in all (csrc/certify.hip CERT_MAX_FRAME_CROPS)
+FRAME_CROPS = 32              # crops one frame may use in all (csrc/certify_plan.h CERT_MAX_FRAME_CROPS)
 HEAD = 'model.final_layers.0'
 N_NOISE_ROWS = 9              # mixed / dot table weights: head channels 0..8 differ from the planted ones, 9..12 are planted
 

@@ -10,6 +10,12 @@ OK, EINVAL, EFORMAT, EHIP, ENOMEM, EMASK, ESTALE = 0, 1, 2, 3, 4, 5, 6
 DTYPE_BF16, DTYPE_F32 = 0, 1
 OPT_PARAM, OPT_EMA, OPT_M, OPT_V = 0, 1, 2, 3
 REFINE_BALL, REFINE_TABLE = 0, 1
+# certified argmax (csrc/certify_plan.h; tests/test_certify_plan_host.py compares): per-heatmap status, the guard bit of the flags,
+# the masks of ttup_wasb_certify_status / _flags, and the counters of ttup_wasb_certify_stats in ABI order
+CERT_SINGLE, CERT_RESOLVED, CERT_NOT_CERTIFIED, CERT_GUARD = 0, 1, 2, 4
+CERT_STATUS_MASK, CERT_FLAGS_MASK = 3, 7
+CERT_STATS = ('heatmaps', 'single', 'resolved', 'not_certified', 'crops', 'candidates', 'max_candidate_err', 'exact_singles', 'over_candidates',
+              'over_crops_per_map', 'over_crop_list', 'small_crops')
 
 _c = ctypes
 _vp, _i, _sz = _c.c_void_p, _c.c_int, _c.c_size_t

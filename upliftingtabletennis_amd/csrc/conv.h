@@ -5,6 +5,7 @@
 #pragma once
 #include "common.h"
 #include "wasb_graph.h"          // FoldedConv
+#include "certify_plan.h"        // CropRec
 
 namespace ttup {
 
@@ -110,7 +111,7 @@ int launch_preprocess(const uint8_t* frames, int n_frames, int src_h, int src_w,
                       void* out, int out_layout, int dtype, int first_triple, int n_triples, int frames_per_sample, hipStream_t stream);
 
 int launch_preprocess_crops(const uint8_t* frames, int n_frames, int src_h, int src_w, int dst_h, int dst_w, float* out,
-                            const int* crops_dev, int crop0, const int* n_active_dev, int max_crops, int crop_h, int crop_w,
+                            const CropRec* crops_dev, int crop0, const int* n_active_dev, int max_crops, int crop_h, int crop_w,
                             int frames_per_sample, hipStream_t stream);
 
 }  // namespace ttup

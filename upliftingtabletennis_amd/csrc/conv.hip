@@ -288,7 +288,7 @@ int launch_preprocess(const uint8_t* frames, int n_frames, int src_h, int src_w,
 
 // crop mode: fp32 NHWC16 windows of the pre-processed triples, chosen on the device (csrc/certify.hip)
 int launch_preprocess_crops(const uint8_t* frames, int n_frames, int src_h, int src_w, int dst_h, int dst_w, float* out,
-                            const int* crops_dev, int crop0, const int* n_active_dev, int max_crops, int crop_h, int crop_w,
+                            const CropRec* crops_dev, int crop0, const int* n_active_dev, int max_crops, int crop_h, int crop_w,
                             int frames_per_sample, hipStream_t stream) {
     PreArgs a;
     a.frames = frames; a.out = out; a.src_h = src_h; a.src_w = src_w; a.dst_h = dst_h; a.dst_w = dst_w;

@@ -158,9 +158,9 @@ struct PreArgs {
     double scale_x, scale_y;
     int nf;                // frames per sample: 3 (ball triples t,t+1,t+2) or 1 (table detector, single frame)
     const float* lut;      // [3][256]: (v/255 - mean[c]) / std[c] evaluated in fp64 on the host, rounded to fp32
-    // crop mode (certified argmax): output sample j is the crop_h x crop_w window at (y0, x0) of triple `map`, records
-    // {map, y0, x0, -} at crops[4*(crop0+j)], only the first *n_active samples are produced
-    const int* crops; const int* n_active; int crop0, crop_h, crop_w;
+    // crop mode (certified argmax): output sample j is the crop_h x crop_w window at (y0, x0) of sample `frame`, as crops[crop0 + j]
+    // (csrc/certify_plan.h CropRec) says; only the first *n_active samples are produced
+    const CropRec* crops; const int* n_active; int crop0, crop_h, crop_w;
 };
 
 __device__ __forceinline__ int cv_round(float v) { return (int)rintf(v); }
@@ -197,8 +197,8 @@ __global__ void preprocess_kernel(PreArgs a) {
         const int cy = (int)(p % (unsigned)a.crop_h);
         const int j = (int)(p / (unsigned)a.crop_h);
         if (j >= *a.n_active) return;
-        const int* rec = a.crops + 4 * (a.crop0 + j);
-        t = rec[0]; y = rec[1] + cy; x = rec[2] + cx;
+        const CropRec rec = a.crops[a.crop0 + j];
+        t = rec.frame; y = rec.y0 + cy; x = rec.x0 + cx;
         opix = ((size_t)j * a.crop_h + cy) * a.crop_w + cx;
     } else {
         x = blockIdx.x * blockDim.x + threadIdx.x; y = blockIdx.y; t = blockIdx.z;

@@ -1,5 +1,6 @@
 // Internal definition of the CNN handle (ttup_wasb): a static op list over NHWC buffers, shared by csrc/wasb_net.hip (create,
-// forward, cone pruning, C ABI) and csrc/certify.hip (certified argmax).  Not part of the C ABI.  The op list itself is planned
+// forward, cone pruning, C ABI) and csrc/certify.hip (certified argmax; its device-free decisions: csrc/certify_plan.h, included
+// through conv.h).  Not part of the C ABI.  The op list itself is planned
 // without a device by csrc/wasb_graph.h (Op, TensorShape, GraphPlan; included through conv.h); csrc/wasb_blob.h (blob parser, BN
 // fold) and csrc/wasb_timing.h (bench.py's timing entry points) are private to csrc/wasb_net.hip.
 #pragma once
@@ -19,11 +20,11 @@ struct CertState {
     bool enabled = false;
     float eps = 0.f;                     // bound on |bf16 heatmap - fp32 heatmap| (absolute, calibrated by the caller)
     static constexpr float GUARD = 1.25f;   // a heatmap with an empty guard band stays certified when eps is widened by up to this factor
-    int R = 72;                          // receptive-field radius of one heatmap pixel (measured: 71)
+    int R = CERT_R;                      // receptive-field radius of one heatmap pixel (measured: 71)
     int small = 0;                       // class-2 crops: candidates that fit the core positions R + 1 .. R + small get a crop pruned to that core's cone (0 = off)
-    int K = 256;                         // candidates kept per heatmap (<= CERT_MAX_K, csrc/certify.hip): the flat top of a saturated blob fits
+    int K = 256;                         // candidates kept per heatmap (<= CERT_MAX_K, csrc/certify_plan.h): the flat top of a saturated blob fits
     int maxc = 8;                        // new crops a heatmap may add (ttup.h: max_crops_per_map, 0 = 8)
-    int maxf = 8;                        // crops per frame, set by ttup_wasb_set_certify to min(16, maxc * channels): the channels of a frame share them
+    int maxf = 8;                        // crops per frame, set by ttup_wasb_set_certify to min(CERT_MAX_FRAME_CROPS, maxc * channels): the channels of a frame share them
     int CH = 0, nchunks = 0, max_crops = 0, Hc = 0, Wc = 0;
     int budget = 0;                      // crops the next forward may use (<= max_crops): ceil(budget / CH) fp32 passes are enqueued
     bool exact_windows = false;          // every heatmap gets an fp32 crop (also single-candidate ones): all 3x3 windows are fp32 values
@@ -32,11 +33,14 @@ struct CertState {
     // Per-call state, two slots used alternately: the fp32 passes of call k run on the handle's own stream (`stream`) while the
     // bf16 micro-batches of call k+1 -- issued on another caller stream -- already fill slot (k+1)&1
     struct Slot {
-        int* cand_idx = nullptr; int* cand_cnt = nullptr; int* cand_crop = nullptr; float* cand_val = nullptr; float* cand_win = nullptr;
-        float* cand_bf = nullptr;           // the bf16 path's value of every candidate (audit: |bf16 - fp32| at the candidates is free)
+        void* mem = nullptr;                // the one allocation that the arrays below are carved from (csrc/certify.hip carve_slot)
+        int* cand_cnt = nullptr;            // zeroed together by cert_begin, back to back: cand_cnt, guard_cnt, status, n_crops
         int* guard_cnt = nullptr;           // pixels per heatmap in the guard band below the candidate band
-        int* crop_rec = nullptr; int* n_crops = nullptr; int* n_active = nullptr; int* status = nullptr;
-        int* roi_flag = nullptr;            // per crop: 1 = interior crop (the pruned op regions of the crop net apply to it)
+        int* status = nullptr; int* n_crops = nullptr;
+        int* cand_idx = nullptr; int* cand_crop = nullptr; float* cand_val = nullptr; float* cand_win = nullptr;
+        float* cand_bf = nullptr;           // the bf16 path's value of every candidate (audit: |bf16 - fp32| at the candidates is free)
+        CropRec* crop_rec = nullptr; int* n_active = nullptr;
+        int* roi_flag = nullptr;            // per crop: 0 = computed in full, 1 / 2 = interior crop (the pruned op regions of the crop net apply to it; cert_roi_class)
         float* margin = nullptr;            // fp32 top-2 margin among the candidates of a resolved heatmap (+inf: one candidate / not resolved)
         hipEvent_t done = nullptr;          // fp32 passes of the call that last used the slot have finished
         // the caller's copies of this slot's status / crop count (ttup_wasb_certify_status / _flags / _info, on whatever stream the

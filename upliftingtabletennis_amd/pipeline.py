@@ -9,7 +9,7 @@ float32 -- a few KB per stream, latency-bound on any xGMI topology (``gather_rec
 import numpy as np
 import torch
 
-from . import wasb
+from . import _lib, wasb
 
 TRAJ_LEN_DEFAULT = 32
 
@@ -240,7 +240,7 @@ class StreamWorker:
         xyv, call, audit = self._pass(frames_u8, counted)
         if call.status is not None and self._settle(call, frames_u8, audit):
             xyv = self._xyv(call.idx, call.win)
-        return (xyv, call.idx, call.win, None if call.status is None else call.status & 3) if full else xyv
+        return (xyv, call.idx, call.win, None if call.status is None else call.status & _lib.CERT_STATUS_MASK) if full else xyv
 
     def uplift_segments(self, positions, table_px, fps):
         """Cut the detections into rallies of `traj_len` frames, filter / normalise / pad each like the reference
@@ -330,7 +330,7 @@ class StreamWorker:
                 ticket['xyv'] = self._xyv(call.idx, call.win)
                 ticket['host'].copy_(ticket['xyv'])
             ticket['idx'], ticket['win'] = call.idx, call.win
-            status_host = call.status & 3          # 0 / 1 / 2 (guard bit dropped)
+            status_host = call.status & _lib.CERT_STATUS_MASK          # 0 / 1 / 2 (guard bit dropped)
         # the uplift (about a hundred small launches for a handful of trajectories) runs on a side stream, so it shares
         # the GPU with the detector of the clip submitted in the meantime instead of queueing behind it
         if self._side is None:

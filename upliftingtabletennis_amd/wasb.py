@@ -103,7 +103,7 @@ class WASBNet:
         _lib.check(rc)
         return heat, idx, win
 
-    # ---- certified argmax (csrc/certify.hip): the fp32 path's argmax indices from the bf16 path, GIVEN an error bound eps
+    # ---- certified argmax (csrc/certify.hip, csrc/certify_plan.h): the fp32 path's argmax indices from the bf16 path, GIVEN an error bound eps
     # The guarantee is conditional: an index is the fp32 argmax whenever |bf16 heatmap - fp32 heatmap| <= eps on that frame.  eps is
     # an empirical bound, measured and then audited for as long as the handle runs: `EpsAudit` (below) drives these primitives.
     SAFETY = 1.5           # an observed error within this factor of eps triggers a widening (and a re-run of the affected work)
@@ -262,12 +262,12 @@ class WASBNet:
         return int(a[0]), float(a[1:2].view(np.float32)[0])
 
     def certify_stats(self, reset=False):
-        out = np.zeros(12, np.int64)
+        out = np.zeros(len(_lib.CERT_STATS), np.int64)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.ttup_wasb_certify_stats(self._handle, out.ctypes.data_as(ctypes.c_void_p), 1 if reset else 0))
-        return dict(heatmaps=int(out[0]), single=int(out[1]), resolved=int(out[2]), not_certified=int(out[3]), crops=int(out[4]), candidates=int(out[5]),
-                    max_candidate_err=float(out[6:7].astype(np.uint32).view(np.float32)[0]), exact_singles=int(out[7]),
-                    over_candidates=int(out[8]), over_crops_per_map=int(out[9]), over_crop_list=int(out[10]), small_crops=int(out[11]))
+        stats = {k: int(v) for k, v in zip(_lib.CERT_STATS, out)}
+        stats['max_candidate_err'] = float(out[_lib.CERT_STATS.index('max_candidate_err'):][:1].astype(np.uint32).view(np.float32)[0])          # a float's bits
+        return stats
 
     def fix_uncertified(self, idx, win, frames_u8=None, x=None, status=None):
         """Heatmaps the certified argmax flagged 2 (candidate / crop budget exceeded) are re-run on the full-frame fp32 path, so that
@@ -280,8 +280,8 @@ class WASBNet:
             raise ValueError('fix_uncertified covers one forward call of at most max_batch=%d samples' % self.max_batch)
         if status is None:
             status = self.certify_status(idx.shape[0])
-        st = _host(status) & 3
-        bad = np.nonzero(st == 2)[0]
+        st = _host(status) & _lib.CERT_STATUS_MASK
+        bad = np.nonzero(st == _lib.CERT_NOT_CERTIFIED)[0]
         samples = np.unique(bad // K)
         if samples.size:
             twin = self._twin()
@@ -305,7 +305,7 @@ class WASBNet:
         if self.eps > eps_used * self.GUARD * (1 - 1e-6):
             return None
         st = _host(status_raw)
-        todo = np.nonzero((st & 4) != 0)[0]
+        todo = np.nonzero((st & _lib.CERT_GUARD) != 0)[0]
         if todo.size == 0:
             return todo
         if todo.size > self.SUBSET_MAX_SHARE * st.size:
@@ -327,13 +327,13 @@ class WASBNet:
             t = int(t)
             fr = frames_u8[t:t + self.NF]
             _, i1, w1 = h.forward_frames(fr, want_heatmap=False)
-            s1 = h.certify_status(K).cpu().numpy() & 3
+            s1 = h.certify_status(K).cpu().numpy() & _lib.CERT_STATUS_MASK
             h.fix_uncertified(i1, w1, frames_u8=fr, status=s1)
             for m in todo[todo // K == t]:
                 idx[int(m)] = i1[int(m) - t * K]
                 win[int(m)] = w1[int(m) - t * K]
                 if isinstance(status_raw, np.ndarray):
-                    status_raw[int(m)] = 0 if s1[int(m) - t * K] == 0 else 1
+                    status_raw[int(m)] = _lib.CERT_SINGLE if s1[int(m) - t * K] == _lib.CERT_SINGLE else _lib.CERT_RESOLVED
         return todo
 
     def internal_streams(self):
@@ -520,7 +520,7 @@ class EpsAudit:
                 self.recertified_heatmaps += int(todo.size)
                 if todo.size:
                     changed.add(k)          # (c.status[todo] holds the re-runs' own status now: 0 or 1)
-            if ((c.status & 3) == 2).any():
+            if ((c.status & _lib.CERT_STATUS_MASK) == _lib.CERT_NOT_CERTIFIED).any():
                 self.fp32_reruns += net.fix_uncertified(c.idx, c.win, frames_u8=fr, x=x, status=c.status)
                 changed.add(k)
         return changed
