@@ -278,7 +278,11 @@ int ttup_refine_windows(const int64_t* argmax_dev, const float* win_dev, int n_m
 int  ttup_uplift_create(const void* blob, size_t blob_bytes, int max_batch, int max_len, ttup_uplift** out);
 void ttup_uplift_destroy(ttup_uplift* net);
 /* ball (B,T,2), table (B,13,3), mask (B,T) in {0,1}, times (B,T) seconds -> rot (B,3), pos (B,T,3); all float32 dev.
- * check_mask != 0 reproduces the reference's ValueError (TTUP_EMASK) and costs one stream synchronisation. */
+ * check_mask != 0 reproduces the reference's ValueError (TTUP_EMASK) and costs one stream synchronisation.
+ * len is refused with TTUP_EINVAL, before anything is launched or captured, when it exceeds max_len or when the len + 1 tokens of the
+ * cls stage exceed what the handle's attention kernels serve: 512 tokens for dim 128 / 4 heads (the matrix-pipe kernels), else the scalar
+ * kernel's 64 KB of LDS -- 962 / 496 / 334 / 251 tokens for head dims 8 / 16 / 24 / 32 (the last one under TTUP_UPLIFT_SCALAR_ATTENTION
+ * or TTUP_F32_EXACT).  ttup_uplift_create accepts a larger max_len; it sizes the scratch only. */
 int ttup_uplift_forward(ttup_uplift* net, const float* ball_dev, const float* table_dev, const float* mask_dev,
                         const float* times_dev, int batch, int len, float* rot_dev, float* pos_dev,
                         int check_mask, void* stream);

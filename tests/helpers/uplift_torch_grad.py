@@ -3,8 +3,12 @@ forward (uplifting/model.py:529-571, as oracle/uplift_ref.py restates it under n
 and `loss.backward()`.  fp32 on the CPU; tests/golden/uplift_grad.npz (the reference's own autograd) pins it, and it gives the GPU
 tests full gradients at shapes the fixture only samples.
 
-Do not run it in float64 as a "ground truth": pos = round(t * 500) rounds differently there for time stamps such as 0.025 s, which
-makes it another function."""
+Do not run ALL of it in float64 as a "ground truth": pos = round(t * 500) rounds differently there for time stamps such as 0.025 s,
+which makes it another function.  `forward_np(..., high_precision=True)` is the high-precision mode that keeps the function: weights
+and activations in float64, while the time stamps stay float32 so that the RoPE index round(times / (1/500)) (and the table tokens'
+arange(13) / 100) is evaluated in float32 exactly as the reference does and only then cast.  `forward` takes the working type from
+`ball`; in float32 every operation is what it was before that mode existed (a `.to()` of a tensor to its own type returns it).
+tests/test_uplift_grad_oracle.py holds the float32 path to the fixtures."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -53,7 +57,7 @@ def rope(x, times, head_dim, time_rotation):
         pos = torch.round(times / (1 / MAX_FPS))
     else:
         pos = torch.arange(x.shape[2], dtype=x.dtype)[None].expand(x.shape[0], -1)
-    freqs = torch.einsum('bi,j->bij', pos, inv_freq).unsqueeze(1)
+    freqs = torch.einsum('bi,j->bij', pos.to(x.dtype), inv_freq.to(x.dtype)).unsqueeze(1)          # (index and inv_freq are float32 values in either mode)
     cos, sin = torch.cos(freqs), torch.sin(freqs)
     a, b = x[..., 0::2], x[..., 1::2]
     return torch.stack((a * cos - b * sin, a * sin + b * cos), -1).flatten(-2)
@@ -92,13 +96,15 @@ def _count(sd, prefix):
 
 
 def forward(ball, table, mask, times, sd, heads, time_rotation='new'):
-    """MultiStageModel.forward (use_skipconnection=True, mode='dynamic'), model.py:529-571 -> rot (B,3), pos (B,T,3)."""
+    """MultiStageModel.forward (use_skipconnection=True, mode='dynamic'), model.py:529-571 -> rot (B,3), pos (B,T,3).
+    Works in ball.dtype (sd, table and mask must have it); `times` is float32 in either mode (module docstring)."""
     B, T, _ = ball.shape
-    mask = torch.where(mask == 0, torch.tensor(float('-inf')), torch.tensor(0.0))
+    dt = ball.dtype
+    mask = torch.where(mask == 0, torch.tensor(float('-inf'), dtype=dt), torch.tensor(0.0, dtype=dt))
     x = _mlp2(ball, sd, 'firststage.ball_embed')
     D = x.shape[-1]
-    tmask = torch.where(table[:, :, 2] == 1, 0.0, float('-inf'))
-    tmask = torch.cat((torch.zeros((B, 1)), tmask), 1)
+    tmask = torch.where(table[:, :, 2] == 1, 0.0, float('-inf')).to(dt)
+    tmask = torch.cat((torch.zeros((B, 1), dtype=dt), tmask), 1)
     tmask = tmask[:, None, :].expand(B, T, -1).reshape(B * T, -1)
     N = table.shape[1]
     ttimes = (torch.arange(N, dtype=torch.float32) / (MAX_FPS / 5))[None].expand(B * T, -1)
@@ -112,10 +118,20 @@ def forward(ball, table, mask, times, sd, heads, time_rotation='new'):
     pos = _head(x, sd, 'firststage.position_head')
     x = x.detach()          # full_backprop is False (model.py:525, :553-555): the spin loss does not reach the first stage
     x = torch.cat((sd['cls_token'].expand(B, 1, D), x), 1)
-    m2 = torch.cat((torch.zeros((B, 1)), mask), 1)
+    m2 = torch.cat((torch.zeros((B, 1), dtype=dt), mask), 1)
     for i in range(_count(sd, 'secondstage')):
         x = layer(x, sd, 'secondstage.%d' % i, m2, times, 1, heads, time_rotation)
     return _head(x[:, 0], sd, 'rotation_head'), pos
+
+
+def forward_np(sd_np, size, ball, table, mask, times, time_rotation='new', high_precision=False):
+    """`forward` under no_grad on numpy inputs -> (rot, pos) numpy, float32, or float64 with high_precision (module docstring)."""
+    dt = torch.float64 if high_precision else torch.float32
+    sd = {k: torch.tensor(np.asarray(v), dtype=torch.float32).to(dt) for k, v in sd_np.items()}
+    ball, table, mask = [torch.as_tensor(np.asarray(a), dtype=torch.float32).to(dt) for a in (ball, table, mask)]
+    with torch.no_grad():
+        rot, pos = forward(ball, table, mask, torch.as_tensor(np.asarray(times), dtype=torch.float32), sd, SIZES[size][2], time_rotation)
+    return rot.numpy(), pos.numpy()
 
 
 def transform_rotationaxes(rot, pos):

@@ -280,7 +280,7 @@ def test_uplift_graph_replay_on_a_side_stream_equals_eager():
 
 def test_uplift_stage_kernel_against_the_per_layer_kernels():
     """Sequences of at most 64 tokens run all layers of a stage in one launch (stage_x3_kernel: tokens resident in LDS).  Same
-    arithmetic as the per-layer kernels apart from where the softmax is normalised, so: within 2e-6 relative of the per-layer path
+    arithmetic as the per-layer kernels (which all normalise the softmax after P V now, as it does), so: within 2e-6 relative of the per-layer path
     (TTUP_UPLIFT_NO_STAGE=1, child process) and within the 1e-4 bar of the oracle, on lengths around the tile boundaries (15/16/17
     query tiles, 63 -> a 64-token spin sequence, 64 -> the spin stage falls back), ragged masks, several sequences per launch."""
     import subprocess, sys, tempfile

@@ -13,6 +13,13 @@ Cases: all 18 (name, mode, time_rotation) at `small`; at `large` eight variants 
 11, 50 and 121; one `base` and one `huge`.
 
     python tools/make_goldens_uplift_family.py
+
+With --edges it writes tests/golden/uplift_family_edges.npz instead and leaves the two files above alone: the cases `FAMILY` of
+tests/helpers/uplift_forward_cases.py (every non-default variant at a length, tile or mask edge of its kernels, on
+``synth.edge_uplift_batch``; four default-variant cases that pin the torch restatement the forward's edge sweep is compared with),
+inputs built by that module's ``make_inputs``.  Stored per case: ``rot``, ``pos``, ``meta``, ``variant`` and ``kind`` only.
+
+    python tools/make_goldens_uplift_family.py --edges
 """
 import json
 import os
@@ -27,6 +34,7 @@ OUT = os.path.join(ROOT, 'tests', 'golden')
 sys.path.insert(0, ROOT)
 sys.path.insert(0, REF)
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 from upliftingtabletennis_amd import arch, synth, weights  # noqa: E402
 
@@ -51,6 +59,31 @@ CASES = [('small', n, m, r, SEED_SMALL.get((n, m), 100 + i // 2), 3, 17, 3) for 
 
 def case_name(size, name, mode, rot, t, pad):
     return '%s_%s_%s_%s_T%d' % (size, name, mode, rot, t + pad)
+
+
+def edges():
+    import make_goldens
+    make_goldens.install_stubs()
+    from helpers import uplift_forward_cases as C
+    from uplifting.model import get_model
+    torch.set_num_threads(min(16, os.cpu_count() or 1))
+    out = {}
+    for c in C.FAMILY:
+        sd = weights.random_uplift_state_dict(c.seed, c.size, c.name, c.mode, c.rot)
+        m = get_model(c.name, c.size, c.mode, c.rot)
+        m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+        m.eval()
+        with torch.no_grad():
+            rot, pos = [a.numpy() for a in m(*[torch.from_numpy(a) for a in C.make_inputs(c)])]
+        assert np.isfinite(rot).all() and np.isfinite(pos).all(), 'non-finite reference output: %s' % C.key(c)
+        key = C.key(c)
+        assert key + '/rot' not in out, key
+        out[key + '/rot'], out[key + '/pos'] = rot, pos
+        out[key + '/meta'] = np.array([c.seed, c.b, c.t, c.pad], np.int64)
+        out[key + '/variant'] = np.array([c.size, c.name, c.mode, c.rot])
+        out[key + '/kind'] = np.array(c.kind)
+        print('%-56s max|rot| %.3e max|pos| %.3e' % (key, np.abs(rot).max(), np.abs(pos).max()), flush=True)
+    np.savez_compressed(os.path.join(OUT, 'uplift_family_edges.npz'), **out)
 
 
 def main():
@@ -93,4 +126,6 @@ def main():
 
 
 if __name__ == '__main__':
-    main()
+    if sys.argv[1:] not in ([], ['--edges']):
+        sys.exit('usage: make_goldens_uplift_family.py [--edges]')
+    edges() if sys.argv[1:] else main()

@@ -238,12 +238,22 @@ void launch_attention(const AttnArgs& a, hipStream_t st) {
     }
 }
 
+// The longest sequence run_attention serves for this handle: 512 tokens (32 key tiles, 148 KB of LDS) on the matrix-pipe kernels, which
+// take D = 128 / head_dim 32 unless a switch selects the scalar kernel; else what fits attention_kernel's 64 KB of LDS with one sequence
+// per workgroup, (2 S hd + 16 + S) floats: 962 / 496 / 334 / 251 tokens for head dims 8 / 16 / 24 / 32.
+constexpr int ATTN_MFMA_MAX_S = 512;
+int max_attention_seq(const ttup_uplift* net) {
+    const Switches& sw = switches();
+    if (net->hd == 32 && net->D == 128 && !sw.scalar_attention && !sw.f32_exact) return ATTN_MFMA_MAX_S;
+    return (64 * 1024 / (int)sizeof(float) - 16) / (2 * net->hd + 1);
+}
+
 int run_attention(ttup_uplift* net, const float* qkv, float* out, int n_seq, const SeqView& sv, hipStream_t st) {
     const int S = sv.S;
     const AttnArgs a{qkv, out, n_seq, net->D, net->heads, net->hd, sv};
     const Switches& sw = switches();
     const bool scalar_attn = sw.scalar_attention || sw.f32_exact;
-    if (net->hd == 32 && net->D == 128 && S > 16 && S <= 512 && !scalar_attn) {
+    if (net->hd == 32 && net->D == 128 && S > 16 && S <= ATTN_MFMA_MAX_S && !scalar_attn) {
         const AttnMArgs m{qkv, out, sv, n_seq};
         const int KT = (S + 15) / 16;
         if (KT <= 8 && !sw.attention_2pass) {
@@ -530,10 +540,13 @@ int alloc_scratch(ttup_uplift* net) {
     if (fit > net->max_batch) fit = net->max_batch;
     net->chunk = (int)fit;
     const size_t chunk = (size_t)fit, tokmax = chunk * per_traj, bt = chunk * (net->max_len + 1);
+    // h1 holds the hidden rows of BOTH embeddings in turn: a ball token per step, then 13 table tokens per trajectory -- more rows than
+    // steps when max_len < 12 (it used to be sized by the steps alone: the table embedding of a short model wrote past its end)
+    const size_t h1_rows = bt > chunk * NT ? bt : chunk * NT;
     const size_t index_rows = net->rot_old ? (size_t)net->max_len + 64 : 0;          // (the attention kernels' padded key tiles stay inside the table)
     if (int rc = dev_alloc(net, {{(void**)&net->x, tokmax * D}, {(void**)&net->qkv, tokmax * 3 * D}, {(void**)&net->att, tokmax * D},
                                  {(void**)&net->hid, tokmax * D}, {(void**)&net->x2, tokmax * D}, {(void**)&net->tok, bt * D},
-                                 {(void**)&net->h1, bt * D}, {(void**)&net->ttok, chunk * NT * D}, {(void**)&net->m1, bt},
+                                 {(void**)&net->h1, h1_rows * D}, {(void**)&net->ttok, chunk * NT * D}, {(void**)&net->m1, bt},
                                  {(void**)&net->m2, bt}, {(void**)&net->tmask, chunk * (NT + 1)}, {(void**)&net->txy, chunk * NT * 2},
                                  {(void**)&net->rope, bt * hd}, {(void**)&net->rope_index, index_rows * hd},
                                  {(void**)&net->pos_rows, net->name == NAME_SINGLE ? bt * 3 : 0}, {(void**)&net->flags_dev, 4}}))
@@ -559,8 +572,10 @@ int alloc_graph_buffers(ttup_uplift* net) {
 // forward_chunk on the handle's own buffers, every later one replays.  *done = false: the caller runs this call eagerly.
 int forward_graph(ttup_uplift* net, const float* ball_dev, const float* table_dev, const float* mask_dev, const float* times_dev, int batch, int len,
                   float* rot_dev, float* pos_dev, hipStream_t st, bool* done) {
-    ttup_uplift::GraphEntry& ge = net->graphs[{batch, len}];
     *done = false;
+    // (a length no attention kernel serves would fail inside the capture and be taken for a runtime that cannot capture)
+    TTUP_REQUIRE(len + 1 <= max_attention_seq(net), TTUP_EINVAL, "uplift graph: sequence length %d + 1 exceeds the %d tokens the attention kernels serve", len, max_attention_seq(net));
+    ttup_uplift::GraphEntry& ge = net->graphs[{batch, len}];
     if (!ge.exec && ge.seen++ == 0) return TTUP_OK;          // first call with this shape
     const size_t bt = (size_t)batch * len;
     TTUP_HIP_CHECK(hipMemcpyAsync(net->g_ball, ball_dev, bt * 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -620,6 +635,9 @@ extern "C" int ttup_uplift_forward(ttup_uplift* net, const float* ball_dev, cons
     TTUP_REQUIRE(net && ball_dev && table_dev && mask_dev && times_dev && rot_dev && pos_dev, TTUP_EINVAL, "ttup_uplift_forward: null pointer");
     TTUP_REQUIRE(batch >= 0 && batch <= net->max_batch, TTUP_EINVAL, "ttup_uplift_forward: batch %d outside [0,%d]", batch, net->max_batch);
     TTUP_REQUIRE(len > 0 && len <= net->max_len, TTUP_EINVAL, "ttup_uplift_forward: sequence length %d outside [1,%d]", len, net->max_len);
+    // every variant ends in a stage of cls + len tokens: refused here, before anything is launched or captured
+    TTUP_REQUIRE(len + 1 <= max_attention_seq(net), TTUP_EINVAL, "ttup_uplift_forward: sequence length %d too long: with the cls token it exceeds the %d tokens this model's attention kernels serve",
+                 len, max_attention_seq(net));
     TTUP_REQUIRE(!net->trained, TTUP_ESTALE, "ttup_uplift_forward: this handle's weights were trained, its packed weights are stale: build an inference model from the trainer");
     hipStream_t st = (hipStream_t)stream;
     if (batch == 0) return TTUP_OK;

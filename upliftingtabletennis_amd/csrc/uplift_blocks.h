@@ -527,6 +527,11 @@ __global__ __launch_bounds__(512) void attn_block_x3_kernel(AttnBlockArgs a) {
         den += __shfl_xor(den, 16, 64);
         den += __shfl_xor(den, 32, 64);
         const float inv = den > 0.f ? 1.f / den : 0.f;       // a fully masked query row yields zeros (torch SDPA semantics)
+        // the sums are normalised AFTER P V, as in stage_x3_kernel and the attention_mfma kernels (it used to be p * inv before: the
+        // one place where this path and the stage kernel rounded differently).  Query 4q + r is lane 4q + r's (its c).
+        float invr[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) invr[r] = __shfl(inv, 4 * q + r, 64);
         // out = P V, k index (step s, lane group q) <-> key j = 4q + s: the A operand of step s is the lane's own pr[s]
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
@@ -535,13 +540,13 @@ __global__ __launch_bounds__(512) void attn_block_x3_kernel(AttnBlockArgs a) {
             for (int s2_ = 0; s2_ < 4; ++s2_) {
                 const int j = 4 * q + s2_;
                 const float vv = (j < S) ? base[j * QS + 64 + dt * 16 + c] : 0.f;
-                o = __builtin_amdgcn_mfma_f32_16x16x4f32(pr[s2_] * inv, vv, o, 0, 0, 0);
+                o = __builtin_amdgcn_mfma_f32_16x16x4f32(pr[s2_], vv, o, 0, 0, 0);
             }
             // o[r] = out[query 4q + r][dim dt*16 + c]
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int i = 4 * q + r;
-                if (i < S) a.att[(m0 + sl * S + i) * K + h * HD + dt * 16 + c] = o[r];
+                if (i < S) a.att[(m0 + sl * S + i) * K + h * HD + dt * 16 + c] = o[r] * invr[r];
             }
         }
         }

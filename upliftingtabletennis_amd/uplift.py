@@ -50,7 +50,9 @@ class MultiStageModel:
 
     def forward(self, ball_pos, table_pos, mask, times, check_mask=True):
         """ball (B,T,2), table (B,13,3), mask (B,T) in {0,1} with at least one 0, times (B,T) -> rot (B,3), pos (B,T,3).
-        Raises ValueError for a mask that is not {0,1} with both values present (model.py:541-546)."""
+        Raises ValueError for a mask that is not {0,1} with both values present (model.py:541-546), and -- before anything is
+        launched -- for a T beyond max_len or beyond what the attention kernels serve (T + 1 <= 512 at `large`, 962 / 496 / 334 at
+        `small` / `base` / `huge`)."""
         args = [t.to(self.device, torch.float32).contiguous() for t in (ball_pos, table_pos, mask, times)]
         ball, table, mask, times = args
         b, t, _ = ball.shape
