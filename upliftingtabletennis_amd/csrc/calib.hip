@@ -14,22 +14,18 @@
 // quadratic majoriser of the objective, so the objective never increases); thread 0 then picks the winner and refines it on
 // its inliers.  Same objective, same subsets (the host draws them with numpy's PCG64 exactly as the reference does), same
 // selection rule -- a different minimiser: results agree with the reference to the accuracy SciPy's BFGS reaches on this
-// non-smooth objective (tests/test_calib_gpu.py states the measured bars).
+// non-smooth objective (tests/test_calib_gpu.py states the measured bars).  The keypoints' world coordinates: scene.h.
 #include "common.h"
+#include "scene.h"
 #include <math.h>
 
 using namespace ttup;
 
 namespace {
 
-constexpr int NK = 13, NPAR = 8, MAX_SUB = 128;
+using scene::TABLE_PTS;          // the 13 table keypoints in world coordinates
+constexpr int NK = scene::N_KEYPOINTS, NPAR = 8, MAX_SUB = 128;
 constexpr double DELTA = 1e-7, INLIER_PX = 3.5;
-constexpr double TL = 2.74, TW = 1.525, TH = 0.76, NETX = 0.1525;
-// the 13 table keypoints in world coordinates (uplifting/helper.py:36-50)
-__constant__ double TABLE_PTS[NK][3] = {
-    {-TL / 2, TW / 2, TH}, {-TL / 2, -TW / 2, TH}, {0.0, TW / 2, TH}, {0.0, -TW / 2, TH}, {TL / 2, TW / 2, TH}, {TL / 2, -TW / 2, TH},
-    {0.0, TW / 2 + NETX, TH}, {0.0, -(TW / 2 + NETX), TH}, {0.0, 0.0, TH}, {0.0, TW / 2 + NETX, TH + NETX}, {0.0, -(TW / 2 + NETX), TH + NETX},
-    {-TL / 2, 0.0, TH}, {TL / 2, 0.0, TH}};
 
 struct Cam8 { double p[NPAR]; };       // fx, fy, tx, ty, tz, a, b, c
 
@@ -248,7 +244,7 @@ __device__ bool dlt_start(const double* kp, unsigned vis, double (*M)[12], doubl
     // extrinsic xyz Euler angles of R = Rz(c) Ry(b) Rx(a), wrapped to [-pi, pi) (regress_cameramatrices.py:84-91)
     double sb = -R[2][0];
     sb = sb > 1.0 ? 1.0 : (sb < -1.0 ? -1.0 : sb);
-    const double PI = 3.141592653589793238462643383279502884;
+    using scene::PI;
     double ang[3] = {atan2(R[2][1], R[2][2]), asin(sb), atan2(R[1][0], R[0][0])};
     for (int q = 0; q < 3; ++q) { double w = fmod(ang[q] + PI, 2.0 * PI); if (w < 0) w += 2.0 * PI; ang[q] = w - PI; }
     out->p[0] = K[0][0]; out->p[1] = K[1][1]; out->p[2] = t[0]; out->p[3] = t[1]; out->p[4] = t[2];

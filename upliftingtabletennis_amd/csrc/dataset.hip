@@ -1,12 +1,12 @@
 // Uplift training samples from generated trajectories (reference uplifting/data.py::TableTennisDataset.__getitem__ and the train
-// transforms of uplifting/transformations.py), fp64; the per-sample arithmetic is dataset_core.h.
+// transforms of uplifting/transformations.py), fp64; the per-sample arithmetic is dataset_core.h, the two streams mt19937.h.
 //   seed_kernel    one lane per sample: both MT19937 states (CPython random.seed(s), np.random.seed(s)) into the workspace
 //   build_kernel   one lane per sample: frame rate, resampling, camera rejection loop, transforms, the nine outputs
 //   draws_kernel   tests: the next `count` raw words of one of the two streams
 // Mapping: a sample is one sequential chain (every draw's place in its stream depends on the rejections before it: the camera
 // loop, the masked-rejection `choice` / `randint`, the polar method), so a sample is a lane and the batch supplies the parallelism.
 // Workspace: [2][624][n] state words, word-major -- the lanes of a wave read and write neighbouring words as long as their
-// stream positions agree, and a state element is renewed when its word is drawn (dataset_core.h), never 624 at a time.
+// stream positions agree, and a state element is renewed when its word is drawn (mt19937.h), never 624 at a time.
 // The per-sample arrays (50 image points, 50 times, 13 keypoints, <= 128 frame indices) are private to the lane.
 #include "common.h"
 #include "dataset_core.h"

@@ -5,13 +5,12 @@
 // because every draw's place in the two MT19937 streams depends on how the rejections before it went.
 //
 // Randomness: the sample's two streams are CPython's `random` after random.seed(s) (init_by_array) and numpy's legacy global
-// stream after np.random.seed(s) (init_genrand).  Their 624-word states live in caller memory with a stride between words
-// (device: word-major over the samples of a launch, so that the lanes of a wave touch neighbouring addresses; host: stride 1).
-// A state element is renewed at the moment its word is drawn: that is the usual whole-state regeneration done one element at
-// a time (it walks the state in this very order), so no draw ever waits for 624 updates.
+// stream after np.random.seed(s) (init_genrand): both are mt19937.h, which csrc/trajgen.hip seeds from as well.  The table
+// keypoints are scene.h's.
 //
-// No fma contraction anywhere in this file: the time grid, the nearest-frame differences, RandomStop's |times - hit|, the
-// doubles built from MT words and the polar method's r2 decide integer outputs and must round like numpy's separate operations.
+// No fma contraction anywhere in this file: the time grid, the nearest-frame differences and RandomStop's |times - hit| decide
+// integer outputs and must round like numpy's separate operations (mt19937.h switches it off for the doubles built from MT
+// words and the polar method's r2 on its own).
 //
 // The same source compiles for gfx950 (hipcc, the product: csrc/dataset.hip runs it one lane per sample) and for the host
 // (g++, test infrastructure only: tests/helpers/host_dataset.cpp, compared with the reference's fixture on the CPU).
@@ -19,12 +18,8 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
-
-#if defined(__HIPCC__)
-#define TTUP_DS_HD __host__ __device__
-#else
-#define TTUP_DS_HD
-#endif
+#include "mt19937.h"
+#include "scene.h"
 
 #pragma clang fp contract(off)
 
@@ -32,13 +27,13 @@ namespace ttup {
 namespace ds {
 
 constexpr int SEQ = 50;               // sequence_len: crop or pad to this
-constexpr int NTAB = 13;              // table keypoints
+constexpr int NTAB = scene::N_KEYPOINTS;
 constexpr int MAX_T = 128;            // frames kept for the camera test (the generator's 1 s at 65 fps gives at most 65)
 constexpr int MAX_TRIES = 100;
 constexpr double IMG_W = 2560.0, IMG_H = 1440.0;          // uplifting/helper.py WIDTH, HEIGHT
 constexpr double ORIG_W = 2560.0, ORIG_H = 1440.0;        // original_resolution of the simulated frames
-constexpr double TABLE_HEIGHT = 0.76, TABLE_WIDTH = 1.525, TABLE_LENGTH = 2.74;
-constexpr double PI = 3.141592653589793;
+using scene::PI;
+using scene::TABLE_HEIGHT;
 // np.rad2deg(math.atan2(TABLE_WIDTH / 2, TABLE_LENGTH / 2)), printed with 17 significant digits
 constexpr double PHI_LO = 29.098971272734509, PHI_HI = PHI_LO + 180.0;
 constexpr double FX_LO = 0.6 * 2710, FX_HI = 2.0 * 2710, FY_LO = 0.6 * 2907, FY_HI = 2.0 * 2907;
@@ -68,83 +63,6 @@ struct Args {
     int* record;                      // (N, RECORD_INTS) or null
 };
 
-struct MT {
-    unsigned* s;
-    size_t stride;
-    int pos;
-    TTUP_DS_HD unsigned& at(int i) { return s[(size_t)i * stride]; }
-    TTUP_DS_HD unsigned next() {
-        const int i = pos, i1 = i + 1 < 624 ? i + 1 : 0, im = i + 397 < 624 ? i + 397 : i + 397 - 624;
-        const unsigned y = (at(i) & 0x80000000u) | (at(i1) & 0x7fffffffu);
-        unsigned v = at(im) ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-        at(i) = v;
-        pos = i1;
-        v ^= v >> 11; v ^= (v << 7) & 0x9d2c5680u; v ^= (v << 15) & 0xefc60000u; v ^= v >> 18;
-        return v;
-    }
-    // genrand_res53: CPython's random() and numpy's legacy random_sample()
-    TTUP_DS_HD double dbl() {
-        const unsigned a = next() >> 5, b = next() >> 6;
-        return ((double)a * 67108864.0 + (double)b) / 9007199254740992.0;
-    }
-    TTUP_DS_HD double uniform(double lo, double hi) { return lo + (hi - lo) * dbl(); }
-    // numpy legacy randint(0, count): masked rejection on single words; no word is drawn for count == 1
-    TTUP_DS_HD int below(int count) {
-        const unsigned rng = (unsigned)(count - 1);
-        if (rng == 0) return 0;
-        unsigned mask = rng;
-        mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
-        unsigned v = next() & mask;
-        while (v > rng) v = next() & mask;
-        return (int)v;
-    }
-    // legacy_gauss: polar method; numpy returns f * x2 first and keeps f * x1 for the next call
-    TTUP_DS_HD void gauss_pair(double* first, double* second) {
-        double x1, x2, r2;
-        do {
-            x1 = 2.0 * dbl() - 1.0;
-            x2 = 2.0 * dbl() - 1.0;
-            r2 = x1 * x1 + x2 * x2;
-        } while (r2 >= 1.0 || r2 == 0.0);
-        const double f = sqrt(-2.0 * log(r2) / r2);
-        *first = f * x2;
-        *second = f * x1;
-    }
-};
-
-TTUP_DS_HD inline void init_genrand(MT& m, unsigned seed) {
-    unsigned prev = seed;
-    m.at(0) = prev;
-    for (int i = 1; i < 624; ++i) {
-        prev = 1812433253u * (prev ^ (prev >> 30)) + (unsigned)i;
-        m.at(i) = prev;
-    }
-    m.pos = 0;
-}
-
-// CPython random.seed(int): init_by_array over the 32-bit little-endian words of abs(seed)
-TTUP_DS_HD inline void init_by_array(MT& m, unsigned long long a) {
-    init_genrand(m, 19650218u);
-    const unsigned key[2] = {(unsigned)(a & 0xffffffffu), (unsigned)(a >> 32)};
-    const int keylen = key[1] ? 2 : 1;
-    int i = 1, j = 0;
-    for (int k = 0; k < 624; ++k) {
-        const unsigned p = m.at(i - 1);
-        m.at(i) = (m.at(i) ^ ((p ^ (p >> 30)) * 1664525u)) + key[j] + (unsigned)j;
-        ++i; ++j;
-        if (i >= 624) { m.at(0) = m.at(623); i = 1; }
-        if (j >= keylen) j = 0;
-    }
-    for (int k = 0; k < 623; ++k) {
-        const unsigned p = m.at(i - 1);
-        m.at(i) = (m.at(i) ^ ((p ^ (p >> 30)) * 1566083941u)) - (unsigned)i;
-        ++i;
-        if (i >= 624) { m.at(0) = m.at(623); i = 1; }
-    }
-    m.at(0) = 0x80000000u;
-    m.pos = 0;
-}
-
 // world2cam + cam2img (uplifting/helper.py:137-204) of one point: homogeneous product with the 4x4, division by its fourth
 // component, product with the 3x3, division by the third
 TTUP_DS_HD inline void project(const double* ex, const double* in, const double* p, double* u, double* v) {
@@ -168,11 +86,7 @@ TTUP_DS_HD inline int upper_bound(const double* t, int n, double x) {        // 
 }
 
 TTUP_DS_HD inline void table_point(int k, double* p) {
-    const double hl = TABLE_LENGTH / 2, hw = TABLE_WIDTH / 2, nw = TABLE_WIDTH / 2 + 0.1525;
-    const double xs[NTAB] = {-hl, -hl, 0.0, 0.0, hl, hl, 0.0, 0.0, 0.0, 0.0, 0.0, -hl, hl};
-    const double ys[NTAB] = {hw, -hw, hw, -hw, hw, -hw, nw, -nw, 0.0, nw, -nw, 0.0, 0.0};
-    p[0] = xs[k]; p[1] = ys[k];
-    p[2] = (k == 9 || k == 10) ? TABLE_HEIGHT + 0.1525 : TABLE_HEIGHT;
+    p[0] = scene::TABLE_PTS[k][0]; p[1] = scene::TABLE_PTS[k][1]; p[2] = scene::TABLE_PTS[k][2];
 }
 
 TTUP_DS_HD inline double norm3(const double* a) { return sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); }

@@ -3,8 +3,8 @@
 //
 //   unknowns   p = (r0, v0, w0): position [m], velocity [m/s], spin [rad/s] at the first time stamp (9 numbers)
 //   model      free flight of a 40 mm / 2.7 g ball: gravity, quadratic + Stokes drag, Magnus lift, added mass, viscous spin decay
-//              -- the smooth part of the generator's force model (csrc/trajgen.hip `accel`, constants restated from the MuJoCo
-//              XML of syntheticdataset/helper.py:79-117); contacts are not modelled: one fit = one arc between bounces
+//              -- the smooth part of the generator's force model (csrc/trajgen.hip `accel`; the MuJoCo XML's ball and air
+//              constants are csrc/scene.h for both); contacts are not modelled: one fit = one arc between bounces
 //   integrator classical RK4, fp64; every interval between two time stamps is cut into ceil(dt / h_max) equal steps;
 //              a stamp that is not later than the last used stamp adds no step: the state stays where it was and the next
 //              interval starts from the last used stamp (a missed frame padded with time 0 inside a track, a repeated stamp).
@@ -23,26 +23,18 @@
 // Parity with the reference is UNPINNED by construction: the reference's uplift is the transformer (csrc/uplift.hip), this
 // kernel is never wired in its place.
 #include "common.h"
-#include <math.h>
+#include "scene.h"
 
 using namespace ttup;
+using namespace ttup::scene;
 
 namespace {
 
-constexpr double PI = 3.141592653589793238462643383279502884;
-constexpr double R_BALL = 0.02, M_BALL = 0.0027, RHO = 1.225, MU_AIR = 0.000018, GRAV = 9.81;
-constexpr double C_BLUNT = 0.235, C_MAGNUS = 1.0;
 constexpr double VOL = 4.0 / 3.0 * PI * R_BALL * R_BALL * R_BALL, AREA = PI * R_BALL * R_BALL, I_BALL = 0.4 * M_BALL * R_BALL * R_BALL;
 constexpr double K_STOKES = 6.0 * PI * MU_AIR * R_BALL, K_QUAD = RHO * C_BLUNT * AREA;
 constexpr double K_MAG = C_MAGNUS * RHO * VOL - 0.5 * RHO * VOL;          // cm w x v + ca v x w = (cm - ca) w x v
 constexpr double K_SPIN = 8.0 * PI * MU_AIR * R_BALL * R_BALL * R_BALL / I_BALL;
 constexpr int NP = 9, GROUPS = 7;           // parameters = lanes per trajectory; trajectories per wave
-
-struct V3 { double x, y, z; };
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator*(double s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 
 // acceleration of the flight model and its directional derivative along (dv, dw)
 __device__ __forceinline__ V3 accel(V3 v, V3 w) {

@@ -1,121 +1,35 @@
 // f2: batched synthetic-trajectory generator (reference syntheticdataset/mujocosimulation.py + helper.py), fp64.
-//   init_kernel      seed -> MT19937 state exactly as CPython's random.Random(seed) builds it -> the nine uniform draws of
-//                    _init_simulation (mujocosimulation.py:54-109) -> initial position / velocity / spin
+//   init_kernel      trajgen_init.h (on the host too, in the CPU suite): MT19937 state as CPython's random.Random(seed) builds it
+//                    (mt19937.h) -> the nine uniform draws of _init_simulation (mujocosimulation.py:54-109) -> r0, v0, w0
 //   simulate_kernel  one lane per seed: RK4 of gravity + drag + Magnus + added mass + soft contacts (table, net, ground),
 //                    1 ms MuJoCo steps split into `substeps`, the reference's sampling loop with its out-of-bounds and
 //                    out-of-image stops (:112-151)
 //   select_kernel    one lane per seed: _count_hits (helper.py:282-321) and every rejection / cut rule (:152-219)
 // The physics restates MuJoCo's published fluid and soft-contact model for this one-sphere scene (see
 // oracle/trajgen_ref.py); MuJoCo itself is absent, so that part of the parity is unpinned.  Sampling and selection are
-// pinned by the reference's own code (tests/golden/trajgen.npz).
+// pinned by the reference's own code (tests/golden/trajgen.npz).  Table, net and ball constants and V3: scene.h.
 // Layout: samples[(k*9 + c) * n + lane] (k = sample, c = x y z vx vy vz wx wy wz): every store is coalesced over seeds.
 #include "common.h"
-#include <math.h>
-#include <string.h>
-#include <vector>
+#include "trajgen_init.h"
 
 using namespace ttup;
+using namespace ttup::scene;
 
 namespace {
 
 constexpr int MAX_SAMPLES = 512;          // >= the 500 or 501 labels of the sampling loop
-constexpr double PI = 3.141592653589793238462643383279502884;
-constexpr double TABLE_HEIGHT = 0.76, TABLE_WIDTH = 1.525, TABLE_LENGTH = 2.74;
-constexpr double NET_POST_OFFSET = 0.1525, NET_ABOVE = 0.1525;
-constexpr double NET_TOTAL_HEIGHT = TABLE_HEIGHT + NET_ABOVE, NET_TOTAL_WIDTH = TABLE_WIDTH + 2 * NET_POST_OFFSET;
-constexpr double R_BALL = 0.02, M_BALL = 0.0027, RHO = 1.225, MU_AIR = 0.000018, GRAV = 9.81;
-constexpr double C_BLUNT = 0.235, C_MAGNUS = 1.0;
+constexpr double NET_TOTAL_HEIGHT = TABLE_HEIGHT + NET_HEIGHT, NET_TOTAL_WIDTH = TABLE_WIDTH + 2 * NET_POST_OFFSET;
 constexpr double IMG_W = 1920.0, IMG_H = 1080.0;
 constexpr int FPS = 500;
 
-struct V3 { double x, y, z; };
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(double s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double norm(V3 a) { return sqrt(dot(a, a)); }
-
-// ------------------------------------------------------------------ CPython random.Random(seed)
-// init_genrand(19650218) is seed-independent: its 624 words come from the host once (mt0).  init_by_array(key) with
-// key = 32-bit little-endian words of abs(seed); the per-lane state lives in global scratch, word-major (coalesced).
-__global__ void init_kernel(const long long* seeds, int n, int mode, int direction, const unsigned* mt0, unsigned* mt, double* state) {
-#pragma clang fp contract(off)      // a + (b - a) * random() must round like CPython's two operations
+// random.Random(seed) and its nine draws (trajgen_init.h); the per-lane MT19937 state lives in global scratch, word-major (coalesced)
+__global__ void init_kernel(const long long* seeds, int n, int mode, int direction, unsigned* mt, double* state) {
     const int lane = blockIdx.x * blockDim.x + threadIdx.x;
     if (lane >= n) return;
-    const long long sd = seeds[lane];
-    const unsigned long long a = sd < 0 ? (unsigned long long)(-sd) : (unsigned long long)sd;
-    const unsigned key[2] = {(unsigned)(a & 0xffffffffu), (unsigned)(a >> 32)};
-    const int keylen = key[1] ? 2 : 1;
-#define MT(i) mt[(size_t)(i) * n + lane]
-    // first pass: 624 steps starting at i = 1
-    unsigned prev = mt0[0];
-    int j = 0;
-    for (int i = 1; i < 624; ++i) {
-        const unsigned v = (mt0[i] ^ ((prev ^ (prev >> 30)) * 1664525u)) + key[j] + (unsigned)j;
-        MT(i) = v; prev = v;
-        if (++j >= keylen) j = 0;
-    }
-    MT(0) = prev;                                   // i wrapped: mt[0] = mt[623]
-    {
-        const unsigned v = (MT(1) ^ ((prev ^ (prev >> 30)) * 1664525u)) + key[j] + (unsigned)j;      // 624th step at i = 1
-        MT(1) = v; prev = v;
-    }
-    // second pass: 623 steps starting at i = 2
-    for (int i = 2; i < 624; ++i) {
-        const unsigned v = (MT(i) ^ ((prev ^ (prev >> 30)) * 1566083941u)) - (unsigned)i;
-        MT(i) = v; prev = v;
-    }
-    {
-        const unsigned v = (MT(1) ^ ((prev ^ (prev >> 30)) * 1566083941u)) - 1u;        // wrapped: mt[0] = mt[623], i = 1
-        MT(1) = v;
-    }
-    // mt[0] = 0x80000000; first 18 outputs of the regenerated state
-    unsigned out[18];
-    unsigned cur = 0x80000000u;
-    for (int kk = 0; kk < 18; ++kk) {
-        const unsigned nxt = MT(kk + 1);
-        const unsigned y = (cur & 0x80000000u) | (nxt & 0x7fffffffu);
-        unsigned v = MT(kk + 397) ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-        v ^= v >> 11; v ^= (v << 7) & 0x9d2c5680u; v ^= (v << 15) & 0xefc60000u; v ^= v >> 18;
-        out[kk] = v;
-        cur = nxt;
-    }
-#undef MT
-    int o = 0;
-    auto uniform = [&](double lo, double hi) {
-        const unsigned x = out[o] >> 5, y = out[o + 1] >> 6;
-        o += 2;
-        return lo + (hi - lo) * (((double)x * 67108864.0 + (double)y) * (1.0 / 9007199254740992.0));
-    };
-    const bool first = mode >= 3;                   // first_good, first_short, first_long
-    const bool l2r = direction == 0;
-    const double sign_x = l2r ? 1.0 : -1.0;
-    double r[3];
-    if (first) {
-        r[0] = uniform(1.0, 2.5) * sign_x; r[1] = uniform(-1.5, 1.5); r[2] = uniform(0.8, 1.6);
-    } else {
-        r[0] = uniform(0.1, 4.0) * sign_x; r[1] = uniform(-2.0, 2.0);
-        r[2] = (fabs(r[0]) < TABLE_LENGTH / 2 && fabs(r[1]) < TABLE_WIDTH / 2) ? uniform(0.8, 1.8) : uniform(0.5, 1.8);
-    }
-    double cx, cy;
-    if (first) { cy = r[1] > 0 ? TABLE_WIDTH / 2 : -TABLE_WIDTH / 2; cx = l2r ? TABLE_LENGTH / 2 : -TABLE_LENGTH / 2; }
-    else { cy = 0.0; cx = l2r ? -TABLE_LENGTH / 2 : TABLE_LENGTH / 2; }
-    const double r2d = 180.0 / PI, d2r = PI / 180.0;
-    const double base_phi = 180.0 + atan2(r[1] - cy, r[0] - cx) * r2d;
-    const double base_theta = 90.0 - atan2(r[2] - TABLE_HEIGHT, fabs(r[0] - cx)) * r2d;
-    double min_theta, max_theta;
-    if (r[2] < TABLE_HEIGHT) { min_theta = fmax(90.0, base_theta - 25.0); max_theta = fmin(170.0, base_theta + 60.0); }
-    else { min_theta = fmax(10.0, base_theta - 25.0); max_theta = fmin(150.0, base_theta + 60.0); }
-    double speed = uniform(3.0, 30.0);
-    double phi = uniform((base_phi - 60.0) * d2r, (base_phi + 60.0) * d2r);
-    double theta = uniform(min_theta * d2r, max_theta * d2r);
-    const double v[3] = {speed * sin(theta) * cos(phi), speed * sin(theta) * sin(phi), speed * cos(theta)};
-    speed = uniform(0.0, 500.0);
-    phi = uniform(0.0, 2.0 * PI);
-    theta = uniform(0.0, PI);
-    const double w[3] = {speed * sin(theta) * cos(phi), speed * sin(theta) * sin(phi), speed * cos(theta)};
-    for (int c = 0; c < 3; ++c) { state[(size_t)c * n + lane] = r[c]; state[(size_t)(3 + c) * n + lane] = v[c]; state[(size_t)(6 + c) * n + lane] = w[c]; }
+    ds::MT m = {mt + lane, (size_t)n, 0};
+    double s[9];
+    trajgen::init_state(seeds[lane], mode, direction, m, s);
+    for (int c = 0; c < 9; ++c) state[(size_t)c * n + lane] = s[c];
 }
 
 // ------------------------------------------------------------------ physics
@@ -180,7 +94,7 @@ __device__ __forceinline__ void accel(V3 r, V3 v, V3 w, V3* a, V3* al) {
         V3 n;
         double dist = box_contact(r, {0.0, 0.0, TABLE_HEIGHT / 2}, {TABLE_LENGTH / 2, TABLE_WIDTH / 2, TABLE_HEIGHT / 2}, &n);
         contact_force(dist, n, pair, v, w, a0, al0, &fc, &tc);
-        dist = box_contact(r, {0.0, 0.0, TABLE_HEIGHT}, {0.02, TABLE_HEIGHT + NET_POST_OFFSET, NET_ABOVE}, &n);
+        dist = box_contact(r, {0.0, 0.0, TABLE_HEIGHT}, {0.02, TABLE_HEIGHT + NET_POST_OFFSET, NET_HEIGHT}, &n);
         contact_force(dist, n, pair, v, w, a0, al0, &fc, &tc);
         contact_force(r.z - R_BALL, {0.0, 0.0, 1.0}, ground, v, w, a0, al0, &fc, &tc);
     }
@@ -247,8 +161,6 @@ __global__ void simulate_kernel(const double* state, int n, int mode, int direct
 
 // ------------------------------------------------------------------ selection
 struct Hits { int count; double t[3]; };          // true count, first three hit times
-
-struct TimesTable { const double* t; };
 
 __global__ void select_kernel(const double* samples, const int* n_saved, int n, int mode, int direction, const double* times,
                               int* n_keep, double* bounces, int* n_bounces) {
@@ -350,7 +262,7 @@ int label_table(double* out) {
 extern "C" int ttup_trajgen_max_samples(void) { return label_table(nullptr); }
 
 extern "C" size_t ttup_trajgen_workspace_bytes(int n_seeds) {
-    return n_seeds <= 0 ? 0 : (size_t)n_seeds * (624 * sizeof(unsigned) + 9 * sizeof(double)) + 624 * sizeof(unsigned) + MAX_SAMPLES * sizeof(double);
+    return n_seeds <= 0 ? 0 : MAX_SAMPLES * sizeof(double) + (size_t)n_seeds * (9 * sizeof(double) + 624 * sizeof(unsigned));          // times, state, mt
 }
 
 extern "C" int ttup_trajgen_simulate(const int64_t* seeds_dev, int n_seeds, int mode, int direction, int substeps, const double* cam_host,
@@ -361,17 +273,10 @@ extern "C" int ttup_trajgen_simulate(const int64_t* seeds_dev, int n_seeds, int 
     TTUP_REQUIRE(workspace_bytes >= ttup_trajgen_workspace_bytes(n_seeds), TTUP_EINVAL, "ttup_trajgen_simulate: workspace too small");
     if (n_seeds == 0) return TTUP_OK;
     hipStream_t st = (hipStream_t)stream;
-    unsigned* mt0_dev = (unsigned*)workspace;
-    double* times_dev = (double*)(mt0_dev + 624);
-    double* state = times_dev + MAX_SAMPLES;
+    double* state = (double*)workspace + MAX_SAMPLES;          // the time labels of ttup_trajgen_select come first
     unsigned* mt = (unsigned*)(state + (size_t)9 * n_seeds);
-    unsigned mt0[624];
-    mt0[0] = 19650218u;
-    for (int i = 1; i < 624; ++i) mt0[i] = 1812433253u * (mt0[i - 1] ^ (mt0[i - 1] >> 30)) + (unsigned)i;
-    TTUP_HIP_CHECK(hipMemcpyAsync(mt0_dev, mt0, sizeof mt0, hipMemcpyHostToDevice, st));
-    TTUP_HIP_CHECK(hipStreamSynchronize(st));          // mt0 lives on this stack frame
     const int threads = 64, blocks = cdiv(n_seeds, threads);
-    hipLaunchKernelGGL(init_kernel, dim3(blocks), dim3(threads), 0, st, (const long long*)seeds_dev, n_seeds, mode, direction, mt0_dev, mt, state);
+    hipLaunchKernelGGL(init_kernel, dim3(blocks), dim3(threads), 0, st, (const long long*)seeds_dev, n_seeds, mode, direction, mt, state);
     TTUP_LAUNCH_CHECK();
     if (init_dev) TTUP_HIP_CHECK(hipMemcpyAsync(init_dev, state, (size_t)9 * n_seeds * sizeof(double), hipMemcpyDeviceToDevice, st));
     Cam cam;
@@ -389,7 +294,7 @@ extern "C" int ttup_trajgen_select(const double* samples_dev, const int* n_saved
     TTUP_REQUIRE(workspace_bytes >= ttup_trajgen_workspace_bytes(n_seeds), TTUP_EINVAL, "ttup_trajgen_select: workspace too small");
     if (n_seeds == 0) return TTUP_OK;
     hipStream_t st = (hipStream_t)stream;
-    double* times_dev = (double*)((unsigned*)workspace + 624);
+    double* times_dev = (double*)workspace;
     double labels[MAX_SAMPLES];
     const int nl = label_table(labels);
     TTUP_HIP_CHECK(hipMemcpyAsync(times_dev, labels, (size_t)nl * sizeof(double), hipMemcpyHostToDevice, st));
