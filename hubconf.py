@@ -17,12 +17,12 @@ IMAGES_ZIP_FILENAME = "example_images.zip"
 
 
 def ball_detection(model_name='segformerpp_b2', **kwargs):
-    """Loads the ball detection model.  Built here: 'wasb' (the in-tree HRNet) and 'vitpose' (ViTPose-small, fp32); 'segformerpp_*' raises NotImplementedError."""
+    """Loads the ball detection model.  Built here: 'wasb' (the in-tree HRNet) and 'vitpose' (ViTPose-small; fp32, or dtype='bf16'); 'segformerpp_*' raises NotImplementedError."""
     return BallDetector(model_name=model_name, **kwargs)
 
 
 def table_detection(model_name='segformerpp_b2', **kwargs):
-    """Loads the table detection model.  Built here: 'hrnet' (the in-tree HRNet) and 'vitpose' (ViTPose-small, fp32); 'segformerpp_*' raises NotImplementedError."""
+    """Loads the table detection model.  Built here: 'hrnet' (the in-tree HRNet) and 'vitpose' (ViTPose-small; fp32, or dtype='bf16'); 'segformerpp_*' raises NotImplementedError."""
     return TableDetector(model_name=model_name, **kwargs)
 
 
@@ -32,11 +32,11 @@ def full_pipeline():
     return TableTennisPipeline()
 
 
-def full_pipeline_two_detectors(ball_aux='vitpose', table_aux='vitpose'):
+def full_pipeline_two_detectors(ball_aux='vitpose', table_aux='vitpose', aux_dtype='f32'):
     """`full_pipeline` with a second detector in the agreement filters, as the reference runs them.  ball_aux / table_aux: 'vitpose'
     (ViTPose-small) or None (the WASB / HRNet primary on both sides: nothing is rejected for disagreement); 'segformerpp_*' raises
-    NotImplementedError, anything else ValueError."""
-    return TableTennisPipeline(ball_aux=ball_aux, table_aux=table_aux)
+    NotImplementedError, anything else ValueError.  aux_dtype: 'f32' (default) or 'bf16', the arithmetic of the ViTPose aux detectors."""
+    return TableTennisPipeline(ball_aux=ball_aux, table_aux=table_aux, aux_dtype=aux_dtype)
 
 
 def download_example_images(local_folder='example_images'):

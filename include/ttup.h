@@ -209,7 +209,10 @@ int ttup_wasb_out_channels(ttup_wasb* net);
 
 /* ---------------------------------------------------------------- a2': ViTPose-small detector (csrc/vitpose.hip)
  * Replaces VitPose.forward (balldetection/models/vitpose.py:92-103, classify_invisible=False; tabledetection/models/vitpose.py)
- * behind `self.model(x)` for model_name 'vitpose'.  fp32 arithmetic throughout (fp32-operand MFMA), no bf16 path.
+ * behind `self.model(x)` for model_name 'vitpose'.  ttup_vitpose_create: fp32 arithmetic throughout (fp32-operand MFMA).
+ * ttup_vitpose_create_dtype with dtype 1: the bf16 path on the bf16 matrix pipe (bf16 matrix weights and stored activations, fp32
+ * residual stream, softmax, accumulation and heatmap, fp64 LayerNorms: DESIGN.md section 24) -- an uncertified detector, meant for the
+ * hub's aux slot; dtype 0 is ttup_vitpose_create.  forward / forward_frames dispatch on the handle.
  * blob: upliftingtabletennis_amd.weights.pack_vitpose_blob:
  *   char magic[8]="TTUPVIT1"; int32 in_ch, out_ch, 384, 12 (depth), 12 (heads), 1536 (mlp), 256 (deconv), n_pos;
  *   float pos_embed[n_pos][384]; patch w[384][in_ch][16][16], b[384];
@@ -221,6 +224,8 @@ int ttup_wasb_out_channels(ttup_wasb* net);
  * micro_batch: samples per internal pass (0 = min(8, max_batch)); out_ch 1 (ball) or up to 16 (13: table keypoints). */
 int  ttup_vitpose_create(const void* blob, size_t blob_bytes, int height, int width, int max_batch, int micro_batch,
                          int in_ch, int out_ch, ttup_vitpose** out);
+int  ttup_vitpose_create_dtype(const void* blob, size_t blob_bytes, int height, int width, int max_batch, int micro_batch,
+                               int in_ch, int out_ch, int dtype, ttup_vitpose** out);
 void ttup_vitpose_destroy(ttup_vitpose* net);
 int  ttup_vitpose_micro_batch(ttup_vitpose* net);
 /* x_dev: float32 (B,in_ch,H,W) NCHW, 16-byte aligned.  heat_dev: float32 (B,out_ch,H/4,W/4) (nullable).
@@ -233,6 +238,15 @@ int  ttup_vitpose_forward(ttup_vitpose* net, const float* x_dev, int batch, floa
  * to it on ttup_preprocess_triples / ttup_preprocess_frames of the same frames; each frame is pre-processed once. */
 int  ttup_vitpose_forward_frames(ttup_vitpose* net, const uint8_t* frames_dev, int n_frames, int src_h, int src_w, float* heat_dev,
                                  int64_t* argmax_dev, float* win_dev, void* stream);
+/* Testing seam: one stage alone on a given device input, batch <= micro_batch.  stage 0: the patch embedding of in_dev = x
+ * (batch,in_ch,H,W); stages 1..12: block `stage` on in_dev = a float32 residual stream (batch*tokens,384); stage 13: the head
+ * (last_norm, deconvolutions, final conv) on a residual stream.  ttup_vitpose_read_tap then copies what that stage left in the
+ * handle's buffers to dst (host or device, exactly `bytes` long): stage 0 "x"; blocks "qkv", "att", "x_attn" (the residual stream
+ * after the attention half), "hid", "x"; head "ln", "d1", "d2" (NHWC), "heat".  x, x_attn and heat are float32; the others are
+ * float32 on an f32 handle and raw bf16 (uint16) on a bf16 handle.  An unknown tap, a tap the last stage did not write, a wrong
+ * size, or a forward since the stage: TTUP_EINVAL. */
+int  ttup_vitpose_run_stage(ttup_vitpose* net, int stage, const float* in_dev, int batch, void* stream);
+int  ttup_vitpose_read_tap(ttup_vitpose* net, const char* tap, void* dst, size_t bytes);
 
 /* ---------------------------------------------------------------- a3/a4: heatmap argmax + refine
  * Replaces extract_position_torch_gaussian (ball: helper_balldetection.py:29-110, called at

@@ -2,7 +2,9 @@
 """The hub with two detectors per agreement filter -- hubconf.full_pipeline_two_detectors() (WASB / HRNet primaries, ViTPose-small
 aux) -- against today's single-detector hubconf.full_pipeline(), in one run, on tools/bench_hub.py's synthetic 1280x720 clips:
 `predict` on the 48-frame clip and the overlapped clip path (detections, both filters, uplift of the first 49) on the 256-frame
-one.  Also reports the share of ball detections the two-detector filter rejects.  Prints one JSON line."""
+one.  Also reports the share of ball detections the two-detector filter rejects.  --aux-dtype f32 | bf16: the arithmetic of the
+ViTPose aux detectors (default f32).  Prints one JSON line."""
+import argparse
 import json
 import os
 import sys
@@ -16,6 +18,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault('TTUP_SYNTHETIC_WEIGHTS', '1')
 import hubconf  # noqa: E402
 from upliftingtabletennis_amd import glue, synth  # noqa: E402
+
+_ap = argparse.ArgumentParser()
+_ap.add_argument('--aux-dtype', choices=('f32', 'bf16'), default='f32')
+aux_dtype = _ap.parse_args().aux_dtype
 
 n = int(os.environ.get('TTUP_HUB_FRAMES', '48'))
 nl = int(os.environ.get('TTUP_HUB_LONG', '256'))
@@ -50,10 +56,10 @@ def rejected_share(hub, clip):
     return 1.0 - len(keep) / len(pos)
 
 
-out = {'metric': 'hub_two_detectors_fps', 'frames': n, 'long_frames': nl}
+out = {'metric': 'hub_two_detectors_fps', 'frames': n, 'long_frames': nl, 'aux_dtype': aux_dtype}
 with warnings.catch_warnings():
     warnings.simplefilter('ignore')
-    for key, make in (('single', hubconf.full_pipeline), ('two', hubconf.full_pipeline_two_detectors)):
+    for key, make in (('single', hubconf.full_pipeline), ('two', lambda: hubconf.full_pipeline_two_detectors(aux_dtype=aux_dtype))):
         hub = make()
         out['%s_fps_%d' % (key, n)] = round(n / timed(lambda: hub.predict(images, 60.0), reps), 1)
         if nl > 0:

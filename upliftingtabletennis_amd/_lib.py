@@ -85,10 +85,13 @@ SIGNATURES = {
     'ttup_odefit_integrate': (_i, [_vp, _vp, _vp, _i, _i, _i, _c.c_double, _vp, _vp, _vp]),
     'ttup_trajgen_select': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'ttup_vitpose_create': (_i, [_vp, _sz, _i, _i, _i, _i, _i, _i, _c.POINTER(_vp)]),
+    'ttup_vitpose_create_dtype': (_i, [_vp, _sz, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_vp)]),
     'ttup_vitpose_destroy': (None, [_vp]),
     'ttup_vitpose_micro_batch': (_i, [_vp]),
     'ttup_vitpose_forward': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'ttup_vitpose_forward_frames': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'ttup_vitpose_run_stage': (_i, [_vp, _i, _vp, _i, _vp]),
+    'ttup_vitpose_read_tap': (_i, [_vp, _c.c_char_p, _vp, _sz]),
     'ttup_dataset_workspace_bytes': (_sz, [_i]),
     'ttup_dataset_seed': (_i, [_vp, _i, _vp, _sz, _vp]),
     'ttup_dataset_draws': (_i, [_vp, _sz, _i, _i, _i, _vp, _vp]),

@@ -44,6 +44,12 @@ using namespace ttup::gemm;
 
 constexpr int DIM = 384, HEADS = 12, HD = 32, MLP = 1536, DEC = 256, DEPTH = 12;
 
+}  // namespace vit
+}  // namespace ttup
+#include "vitpose_bf16.h"
+namespace ttup {
+namespace vit {
+
 // one wave per row of DIM floats -> (mean, 1/sqrt(var + eps)), eps 1e-6 (vit.py:274)
 __global__ __launch_bounds__(256) void ln_stats_kernel(const float* __restrict__ x, int M, float* __restrict__ stats) {
     const int row = ttup_bid_x() * 4 + (ttup_tid_x() >> 6), lane = ttup_tid_x() & 63;
@@ -211,23 +217,32 @@ struct ttup_vitpose {
     float* weights = nullptr;                   // every tensor of the blob (after the header), device copy
     const float *pos, *patch_w, *patch_b, *lnw, *lnb, *dc_w[2], *dc_b[2], *fin_w, *fin_b;
     Block blk[DEPTH];
+    int dtype = 0;                              // 0: fp32 path; 1: bf16 path
+    bf16_t* w16 = nullptr;                      // bf16 handle: the blob rounded to bf16, same offsets as `weights`
+    // qkv, att, hid and d2 hold bf16 in a bf16 handle (half the bytes), fp32 otherwise; x, stats and heat are fp32 in both
     float *x = nullptr, *stats = nullptr, *qkv = nullptr, *att = nullptr, *hid = nullptr, *d2 = nullptr, *heat = nullptr;
+    // ttup_vitpose_run_stage / read_tap: the stage that ran last (-1: none) and its batch, and the residual stream after the
+    // attention half of a block (x itself goes on to the MLP half), allocated on first use
+    int tap_stage = -1, tap_batch = 0;
+    float* x_attn = nullptr;
+    double* stats64 = nullptr;                  // bf16 handle: (M, 2) LN mean, rstd in fp64
     float* frames = nullptr;                    // forward_frames: fp32 (3, H, W) records of one micro-batch's frames
     void* ws = nullptr;
     size_t ws_bytes = 0;
 };
 
 static void vitpose_free(ttup_vitpose* n) {
-    for (void* p : {(void*)n->weights, (void*)n->x, (void*)n->stats, (void*)n->qkv, (void*)n->att, (void*)n->hid, (void*)n->d2,
+    for (void* p : {(void*)n->weights, (void*)n->w16, (void*)n->x_attn, (void*)n->stats64, (void*)n->x, (void*)n->stats, (void*)n->qkv, (void*)n->att, (void*)n->hid, (void*)n->d2,
                     (void*)n->heat, (void*)n->frames, n->ws})
         if (p) (void)hipFree(p);
     delete n;
 }
 
-extern "C" int ttup_vitpose_create(const void* blob, size_t blob_bytes, int height, int width, int max_batch, int micro_batch,
-                                   int in_ch, int out_ch, ttup_vitpose** out) {
+extern "C" int ttup_vitpose_create_dtype(const void* blob, size_t blob_bytes, int height, int width, int max_batch, int micro_batch,
+                                         int in_ch, int out_ch, int dtype, ttup_vitpose** out) {
     TTUP_REQUIRE(out && blob, TTUP_EINVAL, "ttup_vitpose_create: null argument");
     *out = nullptr;
+    TTUP_REQUIRE(dtype == 0 || dtype == 1, TTUP_EINVAL, "ttup_vitpose_create: dtype %d is neither 0 (f32) nor 1 (bf16)", dtype);
     TTUP_REQUIRE(height >= 16 && width >= 16 && height % 16 == 0 && width % 16 == 0, TTUP_EINVAL,
                  "ttup_vitpose_create: height and width must be positive multiples of 16 (got %dx%d)", height, width);
     TTUP_REQUIRE(max_batch >= 1 && micro_batch >= 0 && in_ch >= 1 && out_ch >= 1 && out_ch <= 16, TTUP_EINVAL,
@@ -255,12 +270,23 @@ extern "C" int ttup_vitpose_create(const void* blob, size_t blob_bytes, int heig
 
     ttup_vitpose* n = new ttup_vitpose();
     n->H = height; n->W = width; n->hp = height / 16; n->wp = width / 16; n->ntok = ntok;
-    n->in_ch = in_ch; n->out_ch = out_ch; n->max_batch = max_batch;
+    n->in_ch = in_ch; n->out_ch = out_ch; n->max_batch = max_batch; n->dtype = dtype;
     n->micro = micro_batch ? (micro_batch < max_batch ? micro_batch : max_batch) : (max_batch < 8 ? max_batch : 8);
     auto fail = [&](int rc) { vitpose_free(n); return rc; };
 #define VP_CHECK(expr) do { if ((expr) != hipSuccess) { ttup::set_error("%s failed (%s:%d)", #expr, __FILE__, __LINE__); return fail(TTUP_EHIP); } } while (0)
     VP_CHECK(hipMalloc((void**)&n->weights, total * 4));
     VP_CHECK(hipMemcpy(n->weights, (const char*)blob + 40, total * 4, hipMemcpyHostToDevice));
+    // Every tensor rounded once (RNE); the path reads the matrix weights from here and everything else from `weights`.  Rounding the
+    // whole blob keeps one offset table for both (a tensor's bf16 copy sits at its fp32 offset: launch_gemm) at the price of memory
+    // that is never read -- the bf16 copies of biases, LN parameters, pos_embed and the final conv (under 1 % of the blob) and the fp32
+    // copies of the matrix weights: 1.5 x the fp32 handle's weight memory (about 140 MB instead of 95 MB).  Deliberate.
+    if (dtype == 1) {
+        std::vector<bf16_t> w16(total);
+        const float* src = (const float*)((const char*)blob + 40);
+        for (size_t i = 0; i < total; ++i) w16[i] = f32_to_bf16(src[i]);
+        VP_CHECK(hipMalloc((void**)&n->w16, total * 2));
+        VP_CHECK(hipMemcpy(n->w16, w16.data(), total * 2, hipMemcpyHostToDevice));
+    }
     const float* p = n->weights;
     size_t k = 0;
     auto next = [&]() { const float* r = p; p += sizes[k++]; return r; };
@@ -273,13 +299,14 @@ extern "C" int ttup_vitpose_create(const void* blob, size_t blob_bytes, int heig
     n->lnw = next(); n->lnb = next();
     n->dc_w[0] = next(); n->dc_b[0] = next(); n->dc_w[1] = next(); n->dc_b[1] = next();
     n->fin_w = next(); n->fin_b = next();
-    const size_t M = (size_t)n->micro * ntok;
+    const size_t M = (size_t)n->micro * ntok, esz = dtype == 1 ? 2 : 4;
     VP_CHECK(hipMalloc((void**)&n->x, M * DIM * 4));
     VP_CHECK(hipMalloc((void**)&n->stats, M * 2 * 4));
-    VP_CHECK(hipMalloc((void**)&n->qkv, M * 3 * DIM * 4));
-    VP_CHECK(hipMalloc((void**)&n->att, M * DIM * 4));
-    VP_CHECK(hipMalloc((void**)&n->hid, M * MLP * 4));          // also deconv 1's output (M * 4 * DEC <= M * MLP)
-    VP_CHECK(hipMalloc((void**)&n->d2, M * 16 * DEC * 4));
+    if (dtype == 1) VP_CHECK(hipMalloc((void**)&n->stats64, M * 2 * 8));
+    VP_CHECK(hipMalloc((void**)&n->qkv, M * 3 * DIM * esz));
+    VP_CHECK(hipMalloc((void**)&n->att, M * DIM * esz));
+    VP_CHECK(hipMalloc((void**)&n->hid, M * MLP * esz));        // also deconv 1's output (M * 4 * DEC <= M * MLP)
+    VP_CHECK(hipMalloc((void**)&n->d2, M * 16 * DEC * esz));
     VP_CHECK(hipMalloc((void**)&n->heat, M * 16 * out_ch * 4));
     if (in_ch % 3 == 0)          // one micro-batch of samples spans micro + in_ch / 3 - 1 frames
         VP_CHECK(hipMalloc((void**)&n->frames, (size_t)(n->micro + in_ch / 3 - 1) * 3 * height * width * 4));
@@ -290,87 +317,180 @@ extern "C" int ttup_vitpose_create(const void* blob, size_t blob_bytes, int heig
     return TTUP_OK;
 }
 
+extern "C" int ttup_vitpose_create(const void* blob, size_t blob_bytes, int height, int width, int max_batch, int micro_batch,
+                                   int in_ch, int out_ch, ttup_vitpose** out) {
+    return ttup_vitpose_create_dtype(blob, blob_bytes, height, width, max_batch, micro_batch, in_ch, out_ch, 0, out);
+}
+
 extern "C" void ttup_vitpose_destroy(ttup_vitpose* net) {
     if (net) vitpose_free(net);
 }
 
 extern "C" int ttup_vitpose_micro_batch(ttup_vitpose* net) { return net ? net->micro : -1; }
 
+// One GEMM of the handle's path.  fp32 handle: gemm_kernel on g as it stands.  bf16 handle: gemm_bf16_kernel with the weight read
+// from w16 at g.w's offset, the A_DENSE / A_DECONV input (g.a) read as bf16, and the output (g.out) written as bf16 when out_bf16.
 template <int AM>
-static int launch_gemm(const GemmArgs& a, hipStream_t st) {
-    TTUP_REQUIRE(a.N % BN == 0 && a.K % BK == 0, TTUP_EINVAL, "vitpose gemm: N %d / K %d not multiples of %d / %d", a.N, a.K, BN, BK);
-    hipLaunchKernelGGL(gemm_kernel<AM>, dim3(cdiv(a.M, BM), a.N / BN), dim3(256), 0, st, a);
+static int launch_gemm(const ttup_vitpose* n, const GemmArgs& a, bool out_bf16, hipStream_t st) {
+    if (n->dtype == 0) {
+        TTUP_REQUIRE(a.N % BN == 0 && a.K % BK == 0, TTUP_EINVAL, "vitpose gemm: N %d / K %d not multiples of %d / %d", a.N, a.K, BN, BK);
+        hipLaunchKernelGGL(gemm_kernel<AM>, dim3(cdiv(a.M, BM), a.N / BN), dim3(256), 0, st, a);
+        TTUP_LAUNCH_CHECK();
+        return TTUP_OK;
+    }
+    TTUP_REQUIRE(a.N % TN == 0 && a.K % TK == 0, TTUP_EINVAL, "vitpose bf16 gemm: N %d / K %d not multiples of %d / %d", a.N, a.K, TN, TK);
+    Gemm16Args p = {};
+    p.g = a;
+    p.a16 = (const bf16_t*)a.a;
+    p.w16 = n->w16 + (a.w - n->weights);
+    p.out16 = out_bf16 ? (bf16_t*)a.out : nullptr;
+    p.stats64 = n->stats64;
+    hipLaunchKernelGGL(gemm_bf16_kernel<AM>, dim3(cdiv(a.M, TM), a.N / TN), dim3(256), 0, st, p);
     TTUP_LAUNCH_CHECK();
     return TTUP_OK;
 }
 
-
 #define VP_RC(expr) do { int _rc = (expr); if (_rc != TTUP_OK) return _rc; } while (0)
 
-// one micro-batch of nb samples: x (nb, in_ch, H, W) -> heat (nb, out_ch, H/4, W/4); with from_frames x holds the samples'
-// per-frame records instead (A_PATCH_FRAMES)
-static int vitpose_run(ttup_vitpose* n, const float* x_in, int nb, float* heat, hipStream_t st, bool from_frames = false) {
-    const int M = nb * n->ntok;
-    auto args = [&](const float* a, const float* w, const float* bias, float* out, int N, int K, int flags) {
-        GemmArgs g = {};
-        g.a = a; g.w = w; g.bias = bias; g.out = out; g.M = M; g.N = N; g.K = K; g.flags = flags;
-        return g;
-    };
-    // (a) patch embedding + bias + pos_embed[1:] + pos_embed[:1]  (vit.py:222, :366)
-    GemmArgs g = args(x_in, n->patch_w, n->patch_b, n->x, DIM, n->in_ch * 256, E_POS);
-    g.cin = n->in_ch; g.ih = n->H; g.iw = n->W; g.pos = n->pos; g.ntok = n->ntok;
-    VP_RC(from_frames ? launch_gemm<A_PATCH_FRAMES>(g, st) : launch_gemm<A_PATCH>(g, st));
-    const int ln_grid = cdiv(M, 4);
-    for (int i = 0; i < DEPTH; ++i) {
-        const Block& b = n->blk[i];
-        // x = x + proj(attn(norm1(x)))
-        hipLaunchKernelGGL(ln_stats_kernel, dim3(ln_grid), dim3(256), 0, st, n->x, M, n->stats);
-        TTUP_LAUNCH_CHECK();
-        g = args(n->x, b.qkvw, b.qkvb, n->qkv, 3 * DIM, DIM, 0);
-        g.ln_g = b.n1w; g.ln_b = b.n1b; g.stats = n->stats;
-        VP_RC(launch_gemm<A_LN>(g, st));
-        hipLaunchKernelGGL(attention_kernel, dim3(cdiv(n->ntok, AQ), HEADS, nb), dim3(256), 0, st, n->qkv, n->ntok,
-                           1.0f / sqrtf((float)HD), n->att);
-        TTUP_LAUNCH_CHECK();
-        g = args(n->att, b.projw, b.projb, n->x, DIM, DIM, E_RESID);
-        g.res = n->x;
-        VP_RC(launch_gemm<A_DENSE>(g, st));
-        // x = x + fc2(gelu(fc1(norm2(x))))
-        hipLaunchKernelGGL(ln_stats_kernel, dim3(ln_grid), dim3(256), 0, st, n->x, M, n->stats);
-        TTUP_LAUNCH_CHECK();
-        g = args(n->x, b.fc1w, b.fc1b, n->hid, MLP, DIM, E_GELU);
-        g.ln_g = b.n2w; g.ln_b = b.n2b; g.stats = n->stats;
-        VP_RC(launch_gemm<A_LN>(g, st));
-        g = args(n->hid, b.fc2w, b.fc2b, n->x, DIM, MLP, E_RESID);
-        g.res = n->x;
-        VP_RC(launch_gemm<A_DENSE>(g, st));
-    }
-    // last_norm: materialised once (deconv 1 gathers every token four times per phase)
-    hipLaunchKernelGGL(ln_stats_kernel, dim3(ln_grid), dim3(256), 0, st, n->x, M, n->stats);
+static GemmArgs gemm_args(const float* a, const float* w, const float* bias, float* out, int M, int N, int K, int flags) {
+    GemmArgs g = {};
+    g.a = a; g.w = w; g.bias = bias; g.out = out; g.M = M; g.N = N; g.K = K; g.flags = flags;
+    return g;
+}
+
+static int ln_stats(const ttup_vitpose* n, int M, hipStream_t st) {
+    if (n->dtype == 0) hipLaunchKernelGGL(ln_stats_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, n->x, M, n->stats);
+    else hipLaunchKernelGGL(ln_stats64_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, n->x, M, n->stats64);
     TTUP_LAUNCH_CHECK();
+    return TTUP_OK;
+}
+
+// patch embedding + bias + pos_embed[1:] + pos_embed[:1]  (vit.py:222, :366): x_in (nb, in_ch, H, W), or with from_frames the samples'
+// per-frame records (A_PATCH_FRAMES), -> the residual stream x
+static int run_patch(ttup_vitpose* n, const float* x_in, int nb, hipStream_t st, bool from_frames) {
+    GemmArgs g = gemm_args(x_in, n->patch_w, n->patch_b, n->x, nb * n->ntok, DIM, n->in_ch * 256, E_POS);
+    g.cin = n->in_ch; g.ih = n->H; g.iw = n->W; g.pos = n->pos; g.ntok = n->ntok;
+    return from_frames ? launch_gemm<A_PATCH_FRAMES>(n, g, false, st) : launch_gemm<A_PATCH>(n, g, false, st);
+}
+
+// one transformer block on the residual stream x; x_attn, when given, receives x as it stands between the two halves
+static int run_block(ttup_vitpose* n, int i, int nb, hipStream_t st, float* x_attn = nullptr) {
+    const int M = nb * n->ntok;
+    const Block& b = n->blk[i];
+    // x = x + proj(attn(norm1(x)))
+    VP_RC(ln_stats(n, M, st));
+    GemmArgs g = gemm_args(n->x, b.qkvw, b.qkvb, n->qkv, M, 3 * DIM, DIM, 0);
+    g.ln_g = b.n1w; g.ln_b = b.n1b; g.stats = n->stats;
+    VP_RC(launch_gemm<A_LN>(n, g, true, st));
+    if (n->dtype == 0)
+        hipLaunchKernelGGL(attention_kernel, dim3(cdiv(n->ntok, AQ), HEADS, nb), dim3(256), 0, st, n->qkv, n->ntok, 1.0f / sqrtf((float)HD), n->att);
+    else
+        hipLaunchKernelGGL(attention_bf16_kernel, dim3(cdiv(n->ntok, 64), HEADS, nb), dim3(256), 0, st, (const bf16_t*)n->qkv, n->ntok,
+                           1.0f / sqrtf((float)HD), (bf16_t*)n->att);
+    TTUP_LAUNCH_CHECK();
+    g = gemm_args(n->att, b.projw, b.projb, n->x, M, DIM, DIM, E_RESID);
+    g.res = n->x;
+    VP_RC(launch_gemm<A_DENSE>(n, g, false, st));
+    if (x_attn) TTUP_HIP_CHECK(hipMemcpyAsync(x_attn, n->x, (size_t)M * DIM * 4, hipMemcpyDeviceToDevice, st));
+    // x = x + fc2(gelu(fc1(norm2(x))))
+    VP_RC(ln_stats(n, M, st));
+    g = gemm_args(n->x, b.fc1w, b.fc1b, n->hid, M, MLP, DIM, E_GELU);
+    g.ln_g = b.n2w; g.ln_b = b.n2b; g.stats = n->stats;
+    VP_RC(launch_gemm<A_LN>(n, g, true, st));
+    g = gemm_args(n->hid, b.fc2w, b.fc2b, n->x, M, DIM, MLP, E_RESID);
+    g.res = n->x;
+    return launch_gemm<A_DENSE>(n, g, false, st);
+}
+
+// the head on the residual stream x: last_norm, the two deconvolutions, the final 1x1 conv -> heat (nb, out_ch, H/4, W/4)
+static int run_head(ttup_vitpose* n, int nb, float* heat, hipStream_t st) {
+    const int M = nb * n->ntok;
+    // last_norm: materialised once (deconv 1 gathers every token four times per phase)
+    VP_RC(ln_stats(n, M, st));
     {
-        GemmArgs d = args(n->x, nullptr, nullptr, n->att, DIM, DIM, 0);
+        GemmArgs d = gemm_args(n->x, nullptr, nullptr, n->att, M, DIM, DIM, 0);
         d.ln_g = n->lnw; d.ln_b = n->lnb; d.stats = n->stats;
-        hipLaunchKernelGGL(ln_apply_kernel, dim3(cdiv(M * (DIM / 4), 256)), dim3(256), 0, st, d);
+        if (n->dtype == 0) hipLaunchKernelGGL(ln_apply_kernel, dim3(cdiv(M * (DIM / 4), 256)), dim3(256), 0, st, d);
+        else hipLaunchKernelGGL(ln_apply_bf16_kernel, dim3(cdiv(M * (DIM / 8), 256)), dim3(256), 0, st, d, (const double*)n->stats64, (bf16_t*)n->att);
         TTUP_LAUNCH_CHECK();
     }
-    // (d) deconvolutions: four 2x2 phase GEMMs each, BN folded, ReLU; NHWC (nb, hp, wp, 384) -> (nb, 2hp, 2wp, 256) -> (nb, 4hp, 4wp, 256)
+    // deconvolutions: four 2x2 phase GEMMs each, BN folded, ReLU; NHWC (nb, hp, wp, 384) -> (nb, 2hp, 2wp, 256) -> (nb, 4hp, 4wp, 256)
     const float* din = n->att;
     float* douts[2] = {n->hid, n->d2};
     int h = n->hp, w = n->wp, cin = DIM;
     for (int l = 0; l < 2; ++l) {
         for (int ph = 0; ph < 4; ++ph) {
-            GemmArgs d = args(din, n->dc_w[l] + (size_t)ph * DEC * 4 * cin, n->dc_b[l], douts[l], DEC, 4 * cin, E_RELU);
-            d.M = nb * h * w; d.cin = cin; d.ih = h; d.iw = w; d.py = ph >> 1; d.px = ph & 1;
-            VP_RC(launch_gemm<A_DECONV>(d, st));
+            GemmArgs d = gemm_args(din, n->dc_w[l] + (size_t)ph * DEC * 4 * cin, n->dc_b[l], douts[l], nb * h * w, DEC, 4 * cin, E_RELU);
+            d.cin = cin; d.ih = h; d.iw = w; d.py = ph >> 1; d.px = ph & 1;
+            VP_RC(launch_gemm<A_DECONV>(n, d, true, st));
         }
         din = douts[l]; h *= 2; w *= 2; cin = DEC;
     }
     const long long npix = (long long)nb * h * w;
-    hipLaunchKernelGGL(conv1x1_kernel, dim3((unsigned)((npix + 63) / 64)), dim3(256), 0, st, n->d2, npix, h * w, n->fin_w, n->fin_b,
-                       n->out_ch, heat);
+    if (n->dtype == 0)
+        hipLaunchKernelGGL(conv1x1_kernel, dim3((unsigned)((npix + 63) / 64)), dim3(256), 0, st, n->d2, npix, h * w, n->fin_w, n->fin_b, n->out_ch, heat);
+    else
+        hipLaunchKernelGGL(conv1x1_bf16_kernel, dim3((unsigned)((npix + 63) / 64)), dim3(256), 0, st, (const bf16_t*)n->d2, npix, h * w, n->fin_w,
+                           n->fin_b, n->out_ch, heat);
     TTUP_LAUNCH_CHECK();
     return TTUP_OK;
+}
+
+// one micro-batch of nb samples: x (nb, in_ch, H, W) -> heat (nb, out_ch, H/4, W/4); with from_frames x holds the samples'
+// per-frame records instead (A_PATCH_FRAMES)
+static int vitpose_run(ttup_vitpose* n, const float* x_in, int nb, float* heat, hipStream_t st, bool from_frames = false) {
+    n->tap_stage = -1;
+    VP_RC(run_patch(n, x_in, nb, st, from_frames));
+    for (int i = 0; i < DEPTH; ++i) VP_RC(run_block(n, i, nb, st));
+    return run_head(n, nb, heat, st);
+}
+
+// The testing seam: one stage alone on a given input, and what it left in the handle's buffers.
+extern "C" int ttup_vitpose_run_stage(ttup_vitpose* net, int stage, const float* in_dev, int batch, void* stream) {
+    TTUP_REQUIRE(net && in_dev, TTUP_EINVAL, "ttup_vitpose_run_stage: null handle or input");
+    TTUP_REQUIRE(stage >= 0 && stage <= DEPTH + 1, TTUP_EINVAL, "ttup_vitpose_run_stage: stage %d outside 0..%d", stage, DEPTH + 1);
+    TTUP_REQUIRE(batch >= 1 && batch <= net->micro, TTUP_EINVAL, "ttup_vitpose_run_stage: batch %d outside 1..%d (the micro-batch)", batch, net->micro);
+    TTUP_REQUIRE(((uintptr_t)in_dev & 15) == 0, TTUP_EINVAL, "ttup_vitpose_run_stage: input must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t xbytes = (size_t)batch * net->ntok * DIM * 4;
+    net->tap_stage = -1;
+    if (stage == 0) {
+        VP_RC(run_patch(net, in_dev, batch, st, false));
+    } else {
+        TTUP_HIP_CHECK(hipMemcpyAsync(net->x, in_dev, xbytes, hipMemcpyDeviceToDevice, st));
+        if (stage <= DEPTH) {
+            if (!net->x_attn) TTUP_HIP_CHECK(hipMalloc((void**)&net->x_attn, (size_t)net->micro * net->ntok * DIM * 4));
+            VP_RC(run_block(net, stage - 1, batch, st, net->x_attn));
+        } else {
+            VP_RC(run_head(net, batch, net->heat, st));
+        }
+    }
+    net->tap_stage = stage; net->tap_batch = batch;
+    return TTUP_OK;
+}
+
+extern "C" int ttup_vitpose_read_tap(ttup_vitpose* net, const char* tap, void* dst, size_t bytes) {
+    TTUP_REQUIRE(net && tap && dst, TTUP_EINVAL, "ttup_vitpose_read_tap: null argument");
+    TTUP_REQUIRE(net->tap_stage >= 0, TTUP_EINVAL, "ttup_vitpose_read_tap: no stage has run since the last forward");
+    const int s = net->tap_stage;
+    const bool blk = s >= 1 && s <= DEPTH, head = s == DEPTH + 1;
+    const size_t M = (size_t)net->tap_batch * net->ntok, esz = net->dtype == 1 ? 2 : 4;
+    // name, written by this stage, buffer, elements, element size
+    const struct { const char* name; bool ok; const void* buf; size_t count, size; } taps[] = {
+        {"x_attn", blk, net->x_attn, M * DIM, 4}, {"x", s == 0 || blk, net->x, M * DIM, 4},
+        {"qkv", blk, net->qkv, M * 3 * DIM, esz}, {"att", blk, net->att, M * DIM, esz}, {"hid", blk, net->hid, M * MLP, esz},
+        {"ln", head, net->att, M * DIM, esz}, {"d1", head, net->hid, M * 4 * DEC, esz}, {"d2", head, net->d2, M * 16 * DEC, esz},
+        {"heat", head, net->heat, M * 16 * net->out_ch, 4}};
+    for (const auto& t : taps) {
+        if (strcmp(tap, t.name) != 0) continue;
+        TTUP_REQUIRE(t.ok, TTUP_EINVAL, "ttup_vitpose_read_tap: stage %d does not write tap '%s'", s, tap);
+        TTUP_REQUIRE(bytes == t.count * t.size, TTUP_EINVAL, "ttup_vitpose_read_tap: tap '%s' has %zu bytes, the buffer %zu", tap, t.count * t.size, bytes);
+        TTUP_HIP_CHECK(hipDeviceSynchronize());          // whatever stream the stage ran on, and whether it still exists
+        TTUP_HIP_CHECK(hipMemcpy(dst, t.buf, bytes, hipMemcpyDefault));
+        return TTUP_OK;
+    }
+    ttup::set_error("ttup_vitpose_read_tap: unknown tap '%s'", tap);
+    return TTUP_EINVAL;
 }
 
 extern "C" int ttup_vitpose_forward(ttup_vitpose* net, const float* x_dev, int batch, float* heat_dev, int64_t* argmax_dev,

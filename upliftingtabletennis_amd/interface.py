@@ -101,19 +101,20 @@ def _load_uplift_checkpoint():
 class _HubDetector:
     """What the four detectors share: the constructor tail, the frame upload, the peak refine and `cert`, the certified argmax of a
     bf16 handle -- a wasb.EpsAudit, where the protocol lives: eps measured on the first input, one sample per 256 audited after it;
-    None when certification is off or the handle is fp32 (ViTPose) -- with the detector calls that go through it.  `calibrate`,
+    None when certification is off, the handle is fp32 or the detector is a ViTPose (either dtype) -- with the detector calls that go through it.  `calibrate`,
     `enqueue`, `audit`, `settle` and `refine_peaks` are what the pipeline's overlapped clip path drives a detector by; each does the
     right thing with and without `cert`."""
     NO_CERTIFY_ENV = ('TTUP_NO_CERTIFY',)
     HEAT_DIV = 1            # the heatmaps are model_resolution / HEAT_DIV
     CLIP_AUX = False        # whether the clip path can run this detector as an aux detector, beside the primaries and with nothing to settle
+    CERTIFIES = True        # whether a bf16 handle of this detector gets the certified argmax
 
     def _init_hub(self, model, res, max_batch):
         self.device = torch.device('cuda')
         self.resolution = (WIDTH, HEIGHT)
         self.KEYPOINT_VISIBLE = KEYPOINT_VISIBLE
         self.model, self.model_resolution, self.max_batch = model, res, max_batch
-        off = model.dtype != 'bf16' or any(os.environ.get(k) == '1' for k in self.NO_CERTIFY_ENV)
+        off = not self.CERTIFIES or model.dtype != 'bf16' or any(os.environ.get(k) == '1' for k in self.NO_CERTIFY_ENV)
         self.cert = None if off else wasb.EpsAudit(model, every=0 if os.environ.get('TTUP_NO_AUDIT') == '1' else 256, seed=0)
 
     @property
@@ -282,11 +283,14 @@ class TableDetector(_HubDetector):
 
 
 class _ViTPoseHooks:
-    """What a ViTPose detector changes in its base: it runs the uncertified fp32 path (csrc/vitpose.hip) -- there is no bf16 ViTPose to
-    certify, so the peaks come from fp32 heatmaps like the reference's, `cert` is None and nothing is calibrated -- its heatmaps are a
-    quarter of the model resolution, and its clip call (`ViTPoseNet.forward_frames`) takes a frame range of any length."""
+    """What a ViTPose detector changes in its base: it is uncertified -- a ViT's receptive field is global, so the certified argmax's
+    fp32 crops do not apply: `cert` is None and nothing is calibrated, for the fp32 path (csrc/vitpose.hip, `dtype='f32'`, the
+    default: peaks from fp32 heatmaps like the reference's) and for the bf16 path (`dtype='bf16'`, DESIGN.md section 24: meant for
+    the aux slot, whose only job is to agree with the primary within the agreement filters' pixel radii) alike -- its heatmaps are
+    a quarter of the model resolution, and its clip call (`ViTPoseNet.forward_frames`) takes a frame range of any length."""
     HEAT_DIV = 4
     CLIP_AUX = True
+    CERTIFIES = False
 
     def _certified_forward(self, x):
         return self.model.forward(x, want_heatmap=True, want_peaks=True)
@@ -299,7 +303,7 @@ class ViTPoseBallDetector(_ViTPoseHooks, BallDetector):
     def __init__(self, model_name='vitpose', max_batch=32, dtype='f32', lanes=0):
         _lib.require_gpu()
         sd, res, in_frames = _load_ball_checkpoint(model_name)
-        self._init_hub(vitpose.ViTPoseNet(sd, in_ch=3 * in_frames, out_ch=1, resolution=res, max_batch=max_batch), res, max_batch)
+        self._init_hub(vitpose.ViTPoseNet(sd, in_ch=3 * in_frames, out_ch=1, resolution=res, max_batch=max_batch, dtype=dtype), res, max_batch)
 
 
 class ViTPoseTableDetector(_ViTPoseHooks, TableDetector):
@@ -309,7 +313,7 @@ class ViTPoseTableDetector(_ViTPoseHooks, TableDetector):
     def __init__(self, model_name='vitpose', max_batch=8, dtype='f32', lanes=0):
         _lib.require_gpu()
         sd, res = _load_table_checkpoint(model_name)
-        self._init_hub(vitpose.ViTPoseNet(sd, in_ch=3, out_ch=13, resolution=res, max_batch=max_batch), res, max_batch)
+        self._init_hub(vitpose.ViTPoseNet(sd, in_ch=3, out_ch=13, resolution=res, max_batch=max_batch, dtype=dtype), res, max_batch)
 
 
 class UpliftingModel:
@@ -536,10 +540,13 @@ class _ClipRun:
 
 
 class TableTennisPipeline:
-    def __init__(self, max_batch=32, ball_aux=None, table_aux=None):
+    def __init__(self, max_batch=32, ball_aux=None, table_aux=None, aux_dtype='f32'):
         """ball_aux / table_aux: the second detector of each agreement filter (interface.py:254-289 runs two per frame).  None: the
         primary stands in for both sides (the filters then keep every detection the primary makes); 'vitpose': ViTPose-small, fed
-        from the same single upload of the clip.  The primaries stay WASB / HRNet, and the filters keep the primaries' positions."""
+        from the same single upload of the clip.  The primaries stay WASB / HRNet, and the filters keep the primaries' positions.
+        aux_dtype: 'f32' or 'bf16', the arithmetic of the ViTPose aux detectors (vitpose.ViTPoseNet)."""
+        if aux_dtype not in vitpose.DTYPES:
+            raise ValueError("aux_dtype must be 'f32' or 'bf16', got %r" % (aux_dtype,))
         ball_cls = _aux_class(ball_aux, ViTPoseBallDetector, 'ball_aux')
         table_cls = _aux_class(table_aux, ViTPoseTableDetector, 'table_aux')
         _lib.require_gpu()
@@ -555,8 +562,8 @@ class TableTennisPipeline:
         self.ball_detector = BallDetector(model_name='wasb', max_batch=max(max_batch, self.CHUNK_LONG), lanes=lanes)
         self.table_detector = TableDetector(model_name='hrnet', max_batch=max(16, self.CHUNK_LONG), lanes=lanes)
         # the reference's primary SegFormer++ detectors are not available offline: without an aux detector the primary fills both slots
-        self.ball_detector_aux = ball_cls('vitpose', max_batch=max(max_batch, self.CHUNK_LONG)) if ball_cls else self.ball_detector
-        self.table_detector_aux = table_cls('vitpose', max_batch=max(16, self.CHUNK_LONG)) if table_cls else self.table_detector
+        self.ball_detector_aux = ball_cls('vitpose', max_batch=max(max_batch, self.CHUNK_LONG), dtype=aux_dtype) if ball_cls else self.ball_detector
+        self.table_detector_aux = table_cls('vitpose', max_batch=max(16, self.CHUNK_LONG), dtype=aux_dtype) if table_cls else self.table_detector
         # the overlapped clip path runs both detectors side by side: the table detector goes first on the GPU, so that its
         # host-side consumer (the DBSCAN keypoint filter) overlaps with the rest of the ball detector
         self.table_detector.model.set_priority(True)
