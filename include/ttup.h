@@ -393,6 +393,37 @@ int    ttup_uplift_opt_get_step(ttup_uplift_opt* opt, long long* step_host);
  * Replaces transform_rotationaxes (uplifting/helper.py:394-420): rot (B,3), pos (B,T,3) -> out (B,3). */
 int ttup_transform_rotationaxes(const float* rot_dev, const float* pos_dev, int batch, int len, float* out_dev, void* stream);
 
+/* ---------------------------------------------------------------- a7e: evaluation metrics (csrc/uplift_eval.hip)
+ * The per-batch arithmetic of the reference's val (uplifting/train.py:166-195) and val_real (:250-283) over a whole prediction
+ * set of n samples with t time steps: fp32 inputs, every per-sample operation and every sum in fp64, a fixed summation tree, no
+ * floating-point atomics -- two calls return the same bits.  No handle; nothing synchronises with the host.  workspace:
+ * ttup_uplift_eval_workspace_bytes(n) bytes (one query serves both calls), 8-byte aligned, private to the call while it runs.
+ * Null pointers, n <= 0, t < 2 (the local frame is built from time steps 0 and 1) and a short workspace: TTUP_EINVAL before
+ * any device call.  transform_global != 0: the predicted spin is in the world frame and is taken into the ball-local frame first.
+ * A time step with mask == 0 is selected out (a non-finite value there is inert); the cosine is clamped to [-1, 1] before acos.
+ *
+ * ttup_uplift_val_metrics: pred_rot (n,3), pred_pos (n,t,3), r_world (n,t,3), rotation (n,3), mask (n,t).  The target spin goes
+ *   through transform_rotationaxes(rotation, r_world), the predicted one too when transform_global.
+ *   sums_dev[8]: over the samples, ||d||, |dx|, |dy|, |dz|, | ||pred|| - ||gt|| |, the angle in degrees, the masked mean position
+ *     error sum_t ||pos - r_world|| mask / sum_t mask, and ||d||^2 (d = local predicted - local target spin).
+ *   counts_dev[13]: TP[3], TN[3], FP[3], FN[3] per spin component, then n.  They are helper.binary_metrics called as the
+ *     reference calls it (train.py:181), prediction first: TP both > 0, TN both < 0, FP prediction < 0 and target > 0,
+ *     FN prediction > 0 and target < 0 -- FP and FN swapped relative to their names.
+ * ttup_uplift_val_real_metrics: r_img (n,t,2) normalised image coordinates, Mint (n,3,3), Mext (n,4,4) row major, spin_class (n)
+ *   int32 (1 topspin, 2 backspin, anything else: not annotated).  With transform_global the predicted spin goes through
+ *   transform_rotationaxes(pred_rot, pred_pos) -- the PREDICTED positions (train.py:253).
+ *   sums_dev[1]: over the samples, the masked mean distance between cam2img(world2cam(pred_pos, Mext), Mint) and
+ *     r_img * (2560, 1440) (uplifting/helper.py:26) in pixels.
+ *   counts_dev[5]: TP, TN, FP, FN of the sign of local spin component 1 against spin_class (train.py:265-276), then n.
+ *   scores_dev[n]: local spin component 1 of every sample; labels_dev[n]: 1 topspin, 0 backspin, -1 not annotated. */
+size_t ttup_uplift_eval_workspace_bytes(int n);
+int    ttup_uplift_val_metrics(const float* pred_rot_dev, const float* pred_pos_dev, const float* r_world_dev, const float* rotation_dev, const float* mask_dev,
+                               int n, int t, int transform_global, void* workspace_dev, size_t workspace_bytes, double* sums_dev, long long* counts_dev,
+                               void* stream);
+int    ttup_uplift_val_real_metrics(const float* pred_rot_dev, const float* pred_pos_dev, const float* r_img_dev, const float* mask_dev, const float* mint_dev,
+                                    const float* mext_dev, const int* spin_class_dev, int n, int t, int transform_global, void* workspace_dev,
+                                    size_t workspace_bytes, double* sums_dev, long long* counts_dev, double* scores_dev, int* labels_dev, void* stream);
+
 /* ---------------------------------------------------------------- f2: synthetic-trajectory generator (BASELINE config 5)
  * Replaces the per-seed work of find_valid_trajectories_worker (syntheticdataset/mujocosimulation.py:112-219):
  *   ttup_trajgen_simulate  = _init_simulation (:54-109, CPython random.Random(seed) reproduced bit for bit) + the

@@ -77,6 +77,9 @@ SIGNATURES = {
     'ttup_uplift_opt_set_step': (_i, [_vp, _c.c_longlong]),
     'ttup_uplift_opt_get_step': (_i, [_vp, _c.POINTER(_c.c_longlong)]),
     'ttup_transform_rotationaxes': (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    'ttup_uplift_eval_workspace_bytes': (_sz, [_i]),
+    'ttup_uplift_val_metrics': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    'ttup_uplift_val_real_metrics': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     'ttup_trajgen_max_samples': (_i, []),
     'ttup_trajgen_workspace_bytes': (_sz, [_i]),
     'ttup_trajgen_simulate': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
