@@ -2,6 +2,7 @@
 // training loss and its gradients), and the 1-D launch both units use.
 #pragma once
 #include "common.h"
+#include "uplift_grad_plan.h"
 #include <map>
 #include <utility>
 #include <vector>
@@ -72,8 +73,8 @@ struct ttup_uplift {
     long long* stage_stamps = nullptr;          // TTUP_STAGE_STAMPS: the stage kernel's cycle stamps, allocated on first use
     float2 *rope = nullptr, *table_rope = nullptr;      // (cos, sin) tables: [chunk*max_len][hd/2] per forward, [n_table][hd/2] fixed
     std::vector<void*> allocs;
-    // 'connectstage' / 'dynamic' only: every record of the blob after inv_freq as plain fp32, in blob order -- which is the order of
-    // arch.uplift_variant_schema without the inv_freq buffers and the embed.* tensors (csrc/uplift_grad.hip: dX needs W itself)
+    // 'connectstage' / 'dynamic' only: every record of the blob after inv_freq as plain fp32, in blob order -- the used tensors of
+    // grad_layout (csrc/uplift_grad_plan.h) back to back, i.e. the gradient buffer without its hole (csrc/uplift_grad.hip: dX needs W itself)
     float* plain = nullptr; long long plain_floats = 0;
     bool trained = false;          // ttup_uplift_opt_step has changed `plain` (csrc/uplift_opt.hip): the packed weights below no longer match it
     // scratch (sized for `chunk` trajectories of max_len tokens)
@@ -94,3 +95,13 @@ struct ttup_uplift {
         for (void* p : allocs) if (p) (void)hipFree(p);
     }
 };
+
+namespace ttup {
+namespace upl {
+// the handle trains: connectstage/dynamic with its plain weights -- the one variant the gradient pass and the optimizer serve
+inline bool trains(const ttup_uplift* net) { return net->name == NAME_CONNECT && net->mode == MODE_DYNAMIC && net->plain && net->plain_floats > 0; }
+inline GradDims grad_dims(const ttup_uplift* net) {
+    return {net->D, net->hd, net->n_table, (int)net->pos_layers.size(), (int)net->layers.size(), (int)net->second.size()};
+}
+}  // namespace upl
+}  // namespace ttup

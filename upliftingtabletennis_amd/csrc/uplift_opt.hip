@@ -229,15 +229,13 @@ extern "C" int ttup_opt_flat_step(float* param_dev, const float* grad_dev, float
 
 extern "C" int ttup_uplift_opt_create(ttup_uplift* net, double lr, double beta1, double beta2, double eps, double ema_decay, double max_norm, ttup_uplift_opt** out) {
     TTUP_REQUIRE(net && out, TTUP_EINVAL, "ttup_uplift_opt_create: null pointer");
-    TTUP_REQUIRE(net->name == NAME_CONNECT && net->mode == MODE_DYNAMIC && net->plain && net->plain_floats > 0, TTUP_EINVAL,
-                 "ttup_uplift_opt_create: the optimizer serves connectstage/dynamic handles only (the variant with gradients)");
+    TTUP_REQUIRE(trains(net), TTUP_EINVAL, "ttup_uplift_opt_create: the optimizer serves connectstage/dynamic handles only (the variant with gradients)");
     const HyperD hd = {lr, beta1, beta2, eps, ema_decay, max_norm};
     if (int rc = check_hyper("ttup_uplift_opt_create", hd)) return rc;
-    const long long D = net->D;
+    const GradLayout lay = grad_layout(grad_dims(net));
     std::unique_ptr<ttup_uplift_opt> opt(new ttup_uplift_opt);
     opt->net = net; opt->hyper = hd; opt->n = net->plain_floats;
-    opt->hole_begin = D;                      // cls_token, then the hole: embed.fc1.weight (D x 3), .bias, fc2.weight (D x D), .bias
-    opt->hole_len = D * 3 + D + D * D + D;
+    opt->hole_begin = lay.hole_begin; opt->hole_len = lay.hole_len;          // embed.*, right after cls_token
     TTUP_REQUIRE(opt->hole_begin <= opt->n, TTUP_EINVAL, "ttup_uplift_opt_create: the handle's plain weights do not fit the layout");
     const size_t bytes = (size_t)opt->n * sizeof(float);
     TTUP_HIP_CHECK(hipMalloc((void**)&opt->m, bytes));
