@@ -2,11 +2,11 @@
 tests/helpers/vitpose_edge_cases.py unchanged, the tile sizes of the bf16 kernels they have to straddle, the oracle's taps of every
 case in fp64 and fp32 arithmetic, and the measures and floors the GPU tests compare with.
 
-Tile sizes of the new kernels over the token axis (csrc/gemm_bf16.h, csrc/vitpose_bf16.h):
+Tile sizes of the new kernels over the token axis (csrc/gemm_bf16.h, csrc/vitpose_kernels.h):
   gemm_bf16_kernel        TM = 128 rows of M = batch * tokens per workgroup, 64 per wave, 16 per MFMA tile (TN = 128 and TK = 32 cut
                           N and K, which no case varies: every N is a multiple of 128, every K of 32)
   attention_bf16_kernel   64 queries per workgroup (16 per wave), key tiles of 64, MFMA k-steps of 32 keys, score tiles of 16 keys
-  conv1x1_bf16_kernel     64 pixels per workgroup (a token is 16 pixels)
+  conv1x1_kernel<bf16>    64 pixels per workgroup (a token is 16 pixels)
 The 17 edge cases hold 1, 3, 15, 63, 64, 65, 127, 128 and 129 tokens with M = 3, 6, 30, 126, 128, 195, 127, 256 and 258: T - 1, T and
 T + 1 for the tiles of 64 and 128, but of the 16-wide MFMA / score tile only 15 and of the 32-key k-step nothing.  `EXTRA` adds 16, 17,
 31, 32 and 33 tokens as one-row strips at batch 1, so that M in the GEMM is the token count too: a score tile exactly full and with

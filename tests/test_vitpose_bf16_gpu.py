@@ -1,4 +1,4 @@
-"""The bf16 ViTPose path (csrc/gemm_bf16.h, csrc/vitpose_bf16.h; `ViTPoseNet(dtype='bf16')`) against its rounding oracle
+"""The bf16 ViTPose path (csrc/gemm_bf16.h, csrc/vitpose_kernels.h; `ViTPoseNet(dtype='bf16')`) against its rounding oracle
 (tests/helpers/vitpose_bf16_torch.py) over the sweep of tests/helpers/vitpose_bf16_cases.py.
 
 No oracle reproduces a bf16 forward end to end -- twelve blocks amplify single rounding flips -- so the kernels are checked

@@ -5,7 +5,8 @@
 
 The revision's csrc/ and include/ are checked out to a temporary directory, both sides are compiled to gfx950 assembly with exactly
 build.py's FLAGS (plus --cuda-device-only -S), and every kernel's text is compared after dropping comments, .loc / .file / .ident
-lines, the per-build __hip_cuid_* symbol and the function's position in the unit that block labels carry.  Per kernel it prints
+lines, the per-build __hip_cuid_* symbol, the function's position in the unit that block labels carry and the section of its own that a
+template instance gets.  Per kernel it prints
 `identical` or the number of differing lines (a kernel found on one side only is paired with one of the other side that has the
 same code under another name: `identical (was NAME)`) -- and, for a kernel that differs, whether the sequence of matrix, LDS and vector-memory instructions is still the same (the other differences a refactor
 may leave are commuted integer address arithmetic, kernel-argument offsets and renamed symbols) -- followed by the resource
@@ -53,6 +54,8 @@ def kernels(lines):
                 break
             s = re.sub(r'__hip_cuid_[0-9a-f]+', '__hip_cuid', ln.split(';')[0]).strip()
             s = re.sub(r'\.LBB\d+_', '.LBB_', s)          # block labels carry the function's position in the unit
+            if re.match(r'\.section\s+\.text\.', s):          # a template instance lies in a comdat section of its own, a plain kernel in .text
+                s = '.text'
             if s and not s.startswith(('.loc', '.file', '.ident')):
                 out.append(re.sub(r'\s+', ' ', s))
         body[n] = out

@@ -1,7 +1,7 @@
 // The bf16 GEMM of the ViTPose detector's bf16 path (csrc/vitpose.hip) on v_mfma_f32_16x16x32_bf16: bf16 operands, fp32
 // accumulation.  C[m][n] = epilogue(sum_k A[m][k] W[n][k]) with the A modes and epilogues of gemm_f32.h (whose GemmArgs it takes):
 //   A_PATCH / A_PATCH_FRAMES          read fp32 (gemm::load_a4) and round to bf16 (RNE) on the way into LDS: the GEMM prologue;
-//   A_LN                              the same through LayerNorm evaluated in fp64 (row mean / rstd as doubles from ln_stats64_kernel),
+//   A_LN                              the same through LayerNorm evaluated in fp64 (row mean / rstd as doubles from ln_stats_kernel<double>),
 //                                     rounded to fp32 and then to bf16: the operand is stored nowhere, so it has to be THE bf16
 //                                     neighbour of the exact value -- an fp32 LayerNorm lands on the other side of a rounding tie
 //                                     once in a few thousand operands, which moves a whole output row by ulp(operand) |W|
@@ -9,7 +9,7 @@
 //   A_DENSE / A_DECONV                read stored bf16 activations (a16);
 //   W                                 bf16, rounded once at handle creation (w16);
 //   output                            fp32 (g.out) or rounded to bf16 (out16), after bias and the epilogue.
-// Tile: TM x TN = 128 x 128 per workgroup, TK = 32 per step, 4 waves of 64 x 64 (4 x 4 MFMA tiles).  The product is computed
+// Tile (gemm_modes.h): TM x TN = 128 x 128 per workgroup, TK = 32 per step, 4 waves of 64 x 64 (4 x 4 MFMA tiles).  The product is computed
 // transposed (W rows in the MFMA's A slot, activation rows in its B slot), so a lane ends with four consecutive n of one row m: one
 // 8- or 16-byte store, one 16-byte bias / residual / pos_embed load.  An output element's sum runs over k in steps of 32 in the
 // MFMA's own order, whatever M is: batch composition is bit-neutral.
@@ -31,8 +31,6 @@ typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
-
-constexpr int TM = 128, TN = 128, TK = 32;
 
 struct Gemm16Args {
     GemmArgs g;              // shapes, fp32 operands and epilogue terms as in gemm_f32.h; g.w is not read
@@ -73,13 +71,8 @@ __device__ __forceinline__ u32x4 load_a8(const Gemm16Args& p, int m, int k) {
         if (m >= g.M) return z;
         return *(const u32x4*)(p.a16 + (size_t)m * g.K + k);
     } else if (AM == A_DECONV) {
-        if (m >= g.M) return z;
-        const int per = g.ih * g.iw;
-        const int b = m / per, t = m - b * per, y = t / g.iw, x = t - y * g.iw;
-        const int tap = k / g.cin, c = k - tap * g.cin;
-        const int iy = y + g.py + (tap >> 1) - 1, ix = x + g.px + (tap & 1) - 1;
-        if (iy < 0 || iy >= g.ih || ix < 0 || ix >= g.iw) return z;
-        return *(const u32x4*)(p.a16 + (((size_t)b * g.ih + iy) * g.iw + ix) * g.cin + c);
+        size_t e;
+        return m < g.M && deconv_in(g, m, k, &e) ? *(const u32x4*)(p.a16 + e) : z;
     } else if (AM == A_LN) {
         if (m >= g.M) return z;
         return pack8(load_ln4(g, p.stats64, m, k), load_ln4(g, p.stats64, m, k + 4));
@@ -145,13 +138,7 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(Gemm16Args p) {
     for (int i = 0; i < 4; ++i) {
         const int m = m0 + wm + 16 * i + lr;
         if (m >= g.M) continue;
-        size_t orow;
-        if (AM == A_DECONV) {
-            const int per = g.ih * g.iw, bb = m / per, t = m - bb * per, y = t / g.iw, x = t - y * g.iw;
-            orow = (((size_t)bb * 2 * g.ih + 2 * y + g.py) * (2 * g.iw) + 2 * x + g.px) * g.N;
-        } else {
-            orow = (size_t)m * g.N;
-        }
+        const size_t orow = (AM == A_DECONV ? deconv_out_pixel(m, g.ih, g.iw, g.py, g.px) : (size_t)m) * g.N;
         const int tok = (g.flags & E_POS) ? m % g.ntok : 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {

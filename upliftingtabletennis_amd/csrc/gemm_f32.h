@@ -2,16 +2,15 @@
 // (csrc/vitpose.hip, which describes the tile and its A modes) and the uplift transformer's training pass (csrc/uplift_grad.hip).
 #pragma once
 #include "common.h"
+#include "gemm_modes.h"
 
 namespace ttup {
 namespace gemm {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int BM = 64, BN = 64, BK = 32, LDS_STRIDE = BK + 4;
+constexpr int LDS_STRIDE = BK + 4;          // BM, BN, BK, the A modes and the epilogue flags: gemm_modes.h
 
-enum { A_DENSE = 0, A_LN = 1, A_PATCH = 2, A_DECONV = 3, A_PATCH_FRAMES = 4 };
-enum { E_GELU = 1, E_RESID = 2, E_POS = 4, E_RELU = 8, E_GATE = 16 };
 // GUARD form (the uplift transformer's training pass, uplift_grad.hip): any M, N, K; either operand read by rows (k contiguous) or by
 // columns (the row index contiguous: a transposed operand), leading dimensions of their own; the k range cut into slices of `kslice`
 // (grid z), slice z writing its own partial product at out + z * M * ldo -- summed afterwards in slice order, so a reduction over
@@ -41,6 +40,28 @@ struct GemmArgs {
 };
 
 __device__ __forceinline__ float gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f)); }
+
+// Row m of a deconvolution phase's GEMM is one pixel of the ih x iw input grid: sample b, row y, column x
+struct Pixel { int b, y, x; };
+__device__ __forceinline__ Pixel deconv_pixel(int m, int ih, int iw) {
+    const int per = ih * iw, b = m / per, t = m - b * per, y = t / iw;
+    return {b, y, t - y * iw};
+}
+// ... and phase (py, px) puts it at pixel (2y + py, 2x + px) of the 2ih x 2iw output: that pixel's index in the NHWC output
+__device__ __forceinline__ size_t deconv_out_pixel(int m, int ih, int iw, int py, int px) {
+    const Pixel q = deconv_pixel(m, ih, iw);
+    return ((size_t)q.b * 2 * ih + 2 * q.y + py) * (2 * iw) + 2 * q.x + px;
+}
+// ... reading, at reduction index k = tap * cin + c, input pixel (y + py + tap / 2 - 1, x + px + tap % 2 - 1): that element's index in
+// the NHWC input; false outside the grid
+__device__ __forceinline__ bool deconv_in(const GemmArgs& p, int m, int k, size_t* e) {
+    const Pixel q = deconv_pixel(m, p.ih, p.iw);
+    const int tap = k / p.cin, c = k - tap * p.cin;
+    const int iy = q.y + p.py + (tap >> 1) - 1, ix = q.x + p.px + (tap & 1) - 1;
+    if (iy < 0 || iy >= p.ih || ix < 0 || ix >= p.iw) return false;
+    *e = (((size_t)q.b * p.ih + iy) * p.iw + ix) * p.cin + c;
+    return true;
+}
 
 // Four consecutive k of row m of A (k multiple of 4).
 template <int AM>
@@ -72,12 +93,8 @@ __device__ __forceinline__ f32x4 load_a4(const GemmArgs& p, int m, int k) {
         if (x + 2 >= 0 && x + 2 < p.iw) { const float2 u = *(const float2*)(r + x + 2); z.z = u.x; z.w = u.y; }
         return z;
     } else {
-        const int per = p.ih * p.iw;
-        const int b = m / per, t = m - b * per, y = t / p.iw, x = t - y * p.iw;
-        const int tap = k / p.cin, c = k - tap * p.cin;
-        const int iy = y + p.py + (tap >> 1) - 1, ix = x + p.px + (tap & 1) - 1;
-        if (iy < 0 || iy >= p.ih || ix < 0 || ix >= p.iw) return z;
-        return *(const f32x4*)(p.a + (((size_t)b * p.ih + iy) * p.iw + ix) * p.cin + c);
+        size_t e;
+        return deconv_in(p, m, k, &e) ? *(const f32x4*)(p.a + e) : z;
     }
 }
 
@@ -208,14 +225,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
                 if (p.flags & E_GELU) v = gelu(v);
                 if (p.flags & E_RESID) v = p.res[(size_t)m * p.N + n] + v;
                 if (p.flags & E_RELU) v = fmaxf(v, 0.f);
-                size_t o;
-                if (AM == A_DECONV) {
-                    const int per = p.ih * p.iw, b = m / per, t = m - b * per, y = t / p.iw, x = t - y * p.iw;
-                    o = (((size_t)b * 2 * p.ih + 2 * y + p.py) * (2 * p.iw) + 2 * x + p.px) * p.N + n;
-                } else {
-                    o = (size_t)m * p.N + n;
-                }
-                p.out[o] = v;
+                const size_t orow = AM == A_DECONV ? deconv_out_pixel(m, p.ih, p.iw, p.py, p.px) : (size_t)m;
+                p.out[orow * p.N + n] = v;
             }
         }
     }

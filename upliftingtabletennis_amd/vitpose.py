@@ -16,7 +16,8 @@ from . import _lib, weights
 RESOLUTIONS = {'vitpose': weights.VITPOSE_RESOLUTION}      # (width, height): balldetection/config.py:82, tabledetection/config.py:76
 DTYPES = {'f32': 0, 'bf16': 1}                             # ttup_vitpose_create_dtype
 STAGES = 14                                                # run_stage: 0 patch embedding, 1..12 the blocks, 13 the head
-# read_tap: tap -> (columns per token, stored as bf16 on a bf16 handle); 'heat' is (batch, out_ch, H/4, W/4) float32
+# read_tap: tap -> (columns per token, stored as bf16 on a bf16 handle); 'heat' is (batch, out_ch, H/4, W/4) float32.  The library's
+# own table is csrc/vitpose_plan.h's TAPS; tests/test_vitpose_plan_host.py holds the two together.
 TAPS = {'x': (384, False), 'x_attn': (384, False), 'qkv': (1152, True), 'att': (384, True), 'hid': (1536, True), 'ln': (384, True),
         'd1': (4 * 256, True), 'd2': (16 * 256, True), 'heat': (None, False)}
 
