@@ -424,6 +424,40 @@ int    ttup_uplift_val_real_metrics(const float* pred_rot_dev, const float* pred
                                     const float* mext_dev, const int* spin_class_dev, int n, int t, int transform_global, void* workspace_dev,
                                     size_t workspace_bytes, double* sums_dev, long long* counts_dev, double* scores_dev, int* labels_dev, void* stream);
 
+/* ---------------------------------------------------------------- a3e: detector evaluation (csrc/detect_eval.hip)
+ * What the reference's ball and table val() (balldetection/train.py:144-245, tabledetection/train.py:131-201) and its inference
+ * scripts compute from heatmaps and positions: fp32 heatmaps and positions, fp64 centres, every operation and sum in fp64, a
+ * fixed summation tree, no floating-point atomics -- two calls return the same bits.  No handle; nothing synchronises with the
+ * host.  Workspaces are 8-byte aligned and private to the call while it runs.  Null pointers, n <= 0, sigma <= 0, an empty
+ * tolerance list (or more than TTUP_DETECT_MAX_TOLERANCES) and a short workspace: TTUP_EINVAL before any device call.
+ *
+ * ttup_detect_heatmap_loss: pred (n,c,h,w); centres (n,c,2) [x, y] in output pixels; has_target (n,c) int32.
+ *   sums_dev[n*c]: over the out_h x out_w output pixels, weight * (up(pred) - target)^2 with up = torch's bilinear interpolate
+ *   (align_corners=False, no antialiasing: source coordinate (dst + 0.5) in/out - 0.5 clamped at 0, upper neighbour clamped at the
+ *   last row / column; h, w may exceed the output), target = float32(exp(-((x-cx)^2 + (y-cy)^2) / (2 sigma^2))) or zeros where
+ *   has_target is 0, weight = 100 where weighted and target > 0.1f, else 1 (weighted_mse_loss; weighted = 0: nn.MSELoss).
+ *   Two source rows must fit the 60 KB of LDS a workgroup keeps them in: w <= 7680, else TTUP_EINVAL.
+ * ttup_detect_ball_metrics: pred_pos (n,3) [x, y, visibility]; gt, gt_min, gt_max (n,2); vis (n) int32.  Over the samples with
+ *   vis == 1 (train.py:207-220):
+ *   sums_dev[2]: over those with a detection (x, y > -100), the distance to gt, and the distance to the streak as val() measures
+ *     it (distance_to_streak called with (pred, gt, gt_min, gt_max): the segments gt -> gt_min and gt_min -> gt_max).
+ *   counts_dev[4 + n_tolerances]: visible samples; of those, pred visibility == 1 (PCK's denominator); of those, detected; per
+ *     tolerance, pred visibility == 1 and within it of the nearer of the segments gt_min -> gt, gt -> gt_max
+ *     (_batched_distance_point_to_segment: t = 0 where L^2 <= 1e-12, t clamped to [0, 1]); last, n.
+ * ttup_detect_table_metrics: pred_pos, gt (n,keypoints,3) [x, y, visibility].  valid: pred visibility == 1; visible: gt's == 1.
+ *   sums_dev[2]: the distance over valid & visible; unused.
+ *   counts_dev[4 + n_tolerances]: valid; valid & visible; unused; per tolerance, valid & visible within it; last, n * keypoints. */
+#define TTUP_DETECT_MAX_TOLERANCES 8
+size_t ttup_detect_loss_workspace_bytes(int n_maps, int out_h, int out_w);
+size_t ttup_detect_metrics_workspace_bytes(int n_items);
+int    ttup_detect_heatmap_loss(const float* pred_dev, const double* centres_dev, const int* has_target_dev, int n, int c, int h, int w, double sigma, int out_h,
+                                int out_w, int weighted, void* workspace_dev, size_t workspace_bytes, double* sums_dev, void* stream);
+int    ttup_detect_ball_metrics(const float* pred_pos_dev, const float* gt_dev, const float* gt_min_dev, const float* gt_max_dev, const int* vis_dev, int n,
+                                const double* tolerances, int n_tolerances, void* workspace_dev, size_t workspace_bytes, double* sums_dev,
+                                long long* counts_dev, void* stream);
+int    ttup_detect_table_metrics(const float* pred_pos_dev, const float* gt_dev, int n, int keypoints, const double* tolerances, int n_tolerances,
+                                 void* workspace_dev, size_t workspace_bytes, double* sums_dev, long long* counts_dev, void* stream);
+
 /* ---------------------------------------------------------------- f2: synthetic-trajectory generator (BASELINE config 5)
  * Replaces the per-seed work of find_valid_trajectories_worker (syntheticdataset/mujocosimulation.py:112-219):
  *   ttup_trajgen_simulate  = _init_simulation (:54-109, CPython random.Random(seed) reproduced bit for bit) + the

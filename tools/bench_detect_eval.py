@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Time of evaluating the detectors on the device (BallDetector.val / TableDetector.val, csrc/detect_eval.hip), one JSON line: per
+detector the forward alone (`_certified_forward` on a pre-processed batch), the heatmap-loss launch on its heatmaps at 1080x1920,
+the metrics launch, and the whole `val` call from host frames (upload and pre-processing included).  Launch times are device
+events around `--inner` back-to-back calls on preallocated inputs; every timed call is preceded by a warm-up call of the same
+shape; best and mean of --repeat.  The loss rate is output pixels per second (the kernel's work is per output pixel).
+
+Without checkpoints (TTUP_WEIGHTS) the detectors run on seeded weights: the times do not depend on the weights.
+
+    python tools/bench_detect_eval.py [--triples 64] [--frames 16] [--repeat 3] [--inner 5]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+import warnings
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+os.environ.setdefault('TTUP_SYNTHETIC_WEIGHTS', '1')
+from upliftingtabletennis_amd import _lib, detect_eval, synth, wasb  # noqa: E402
+from upliftingtabletennis_amd.interface import HEIGHT, WIDTH, BallDetector, TableDetector  # noqa: E402
+
+
+def host_timed(fn, repeat):
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(repeat):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return min(ts), sum(ts) / len(ts)
+
+
+def event_timed(launch, repeat, inner):
+    """seconds per launch: device events around `inner` back-to-back launches"""
+    launch()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(repeat):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(inner):
+            launch()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b) * 1e-3 / inner)
+    return min(ts), sum(ts) / len(ts)
+
+
+def measure(det, x, centres, has, weighted, metrics, val, a):
+    """forward / loss / metrics / val times of one detector -> dict"""
+    res = {}
+    best, mean = host_timed(lambda: det._certified_forward(x), a.repeat)
+    res['forward_ms_best'], res['forward_ms_mean'] = best * 1e3, mean * 1e3
+    heat = det._certified_forward(x)[0].clone()
+    centres, has = torch.from_numpy(centres).cuda(), torch.from_numpy(has).cuda()
+    best, mean = event_timed(lambda: detect_eval.heatmap_loss_device(heat, centres, has, 6, weighted, (HEIGHT, WIDTH)), a.repeat, a.inner)
+    pixels = heat.shape[0] * heat.shape[1] * HEIGHT * WIDTH
+    res.update({'heat_shape': list(heat.shape), 'loss_ms_best': best * 1e3, 'loss_ms_mean': mean * 1e3, 'loss_gpixel_per_s_best': pixels / best * 1e-9})
+    best, mean = event_timed(metrics, a.repeat, a.inner)
+    res['metrics_us_best'], res['metrics_us_mean'] = best * 1e6, mean * 1e6
+    best, mean = host_timed(val, a.repeat)
+    res['val_ms_best'], res['val_ms_mean'] = best * 1e3, mean * 1e3
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--triples', type=int, default=64)
+    ap.add_argument('--frames', type=int, default=16)
+    ap.add_argument('--repeat', type=int, default=3)
+    ap.add_argument('--inner', type=int, default=5)
+    a = ap.parse_args()
+    _lib.require_gpu()
+    warnings.simplefilter('ignore')
+    nb, nt = a.triples, a.frames
+    frames = [f for f in synth.synth_frames(max(nb + 2, nt), 720, 1280, seed=0)[0]]
+    rng = np.random.default_rng(0)
+    res = {'triples': nb, 'frames': nt, 'build_id': _lib.build_id()}
+
+    triples = [[frames[i], frames[i + 1], frames[i + 2]] for i in range(nb)]
+    gt = np.stack([rng.uniform(100, 1800, nb), rng.uniform(100, 1000, nb)], 1)
+    lo, hi, vis = gt - 5.0, gt + 5.0, np.ones(nb, np.int64)
+    pos = torch.from_numpy(np.concatenate([gt + rng.normal(0, 4, (nb, 2)), np.ones((nb, 1))], 1)).cuda()
+    dev = [torch.from_numpy(v).cuda() for v in (gt, lo, hi, vis)]
+    for name, dtype in (('wasb', 'bf16'), ('wasb', 'f32'), ('vitpose', 'f32'), ('vitpose', 'bf16')):
+        det = BallDetector(name, max_batch=nb, dtype=dtype)
+        w, h = det.model_resolution
+        x = torch.cat([wasb.preprocess_triples(det._upload(t), (w, h)) for t in triples])
+        res['ball_%s_%s' % (name, dtype)] = measure(det, x, gt.reshape(nb, 1, 2), np.ones((nb, 1), np.int32), False,
+                                                    lambda: detect_eval.ball_metrics_device(pos, *dev), lambda: det.val(triples, gt, lo, hi, vis), a)
+        del det, x
+        torch.cuda.empty_cache()
+
+    images = frames[:nt]
+    coords = np.concatenate([np.floor(rng.uniform(50, 1000, (nt, 13, 2))), np.ones((nt, 13, 1))], 2)
+    tpos = torch.from_numpy(coords + rng.normal(0, 3, coords.shape) * np.array([1, 1, 0])).cuda()
+    tgt = torch.from_numpy(coords).cuda()
+    for name, dtype in (('hrnet', 'bf16'), ('hrnet', 'f32'), ('vitpose', 'f32'), ('vitpose', 'bf16')):
+        det = TableDetector(name, max_batch=nt, dtype=dtype)
+        x = wasb.preprocess_frames(det._upload(images), det.model_resolution)
+        res['table_%s_%s' % (name, dtype)] = measure(det, x, np.ascontiguousarray(coords[..., :2]), np.ones((nt, 13), np.int32), True,
+                                                     lambda: detect_eval.table_metrics_device(tpos, tgt), lambda: det.val(images, coords), a)
+        del det, x
+        torch.cuda.empty_cache()
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()

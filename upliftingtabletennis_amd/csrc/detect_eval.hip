@@ -1,0 +1,428 @@
+// The detectors' evaluation on the device (include/ttup.h): the heatmap loss of the reference's ball and table val()
+// (balldetection/train.py:177-179, tabledetection/train.py:154-156) and of both train() loops (:112-113, :106-107), and the
+// position metrics its val() and inference scripts report (PCK at fixed pixel tolerances, average distance, distance to the
+// motion-blur streak, ratio of detected keypoints).
+//
+// Inputs are fp32 (heatmaps, positions) and fp64 (target centres); every operation and every sum is fp64.
+//
+// Heatmap loss.  The reference upsamples the predicted heatmap bilinearly to the evaluation resolution and compares it there with a
+// Gaussian target of that size: two full-resolution tensors per batch.  loss_kernel writes neither.  One workgroup takes a strip of
+// `strip` output rows of one (sample, channel) map: it copies the source rows the strip interpolates between into LDS (fp32, as
+// they are), then thread t walks the output columns t, t + 256, ... and, per column, the strip's rows.  The target is separable,
+// exp(-dx^2 / 2s^2) * exp(-dy^2 / 2s^2): factor_kernel evaluates the out_h + out_w factors of a map once, in fp64, and the
+// product is rounded once to fp32 as the reference's torch.tensor(heatmap, dtype=float32) rounds its exp.
+//
+// LDS: a strip of r output rows lies between at most min(span, 2 r) source rows, span = y1(last row) - y0(first row) + 1.  When
+// span <= 2 r (every upsampling, and downsampling by less than 2) the rows y0(first) .. y1(last) are kept in order and slot = y -
+// y0(first); otherwise (strong downsampling, the rows are far apart) row i of the strip keeps its own pair in slots 2 i, 2 i + 1.
+// loss_plan() walks the strips with the kernel's own fp64 expressions and picks the largest strip height <= DE_STRIP whose slots
+// fit DE_ROW_BYTES, so a workgroup never needs more than 60 KB and 2 .. 30 workgroups share a CU's 160 KB: WASB (704, 1280) ->
+// 8 rows x 5 KB = 40 KB, 4 workgroups (16 waves) per CU; ViTPose (160, 288) -> 4 rows x 1.1 KB.  Within a wave the 64 lanes read
+// 64 neighbouring output columns: when upsampling these are <= 64 consecutive floats of one LDS row (no bank is hit by two
+// different addresses), lanes that share a source column are served by the broadcast.
+//
+// Sums: thread (columns in order, rows in order) -> xor butterfly over the wave -> the block's 4 waves in order (one partial per
+// strip, in the workspace) -> final kernel: one block per map, thread i adds the partials i, i + 256, ... in order, then a
+// 256-leaf tree in LDS.  No floating-point atomics: two calls return the same bits.  The metric kernels use the same tree.
+#include "no_packed_fp32_begin.h"
+#include "common.h"
+
+#include <math.h>
+
+#pragma clang fp contract(off)
+
+using namespace ttup;
+
+namespace {
+
+constexpr int DE_THREADS = 256;
+constexpr int DE_WAVES = DE_THREADS / 64;
+constexpr int DE_STRIP = 8;                              // output rows per workgroup, at most
+constexpr size_t DE_ROW_BYTES = 60 * 1024;               // LDS for the source rows of a strip (dynamic); the static part is < 1 KB
+constexpr int DE_MAX_TOL = TTUP_DETECT_MAX_TOLERANCES;
+constexpr int DE_SUMS = 2;                               // metric kernels: sums per call
+constexpr int DE_COUNTS = 3 + DE_MAX_TOL;                // ... counts per call, at most
+constexpr float VISIBLE = 1.0f;                          // BALL_VISIBLE / KEYPOINT_VISIBLE
+constexpr double NOT_DETECTED = -100.0;                  // helper_balldetection.py:262: a detection is valid when x, y > -100
+
+struct Tolerances {
+    double v[DE_MAX_TOL];
+    int n;
+};
+
+// torch's upsample_bilinear2d, align_corners = False, no antialiasing: source coordinate of the output index dst, clamped at 0;
+// i1 clamped at the last row / column.  scale = in / out.  Host and device evaluate the same three IEEE operations.
+__host__ __device__ inline void src_coord(int dst, double scale, int in, int& i0, int& i1, double& lam) {
+    double s = ((double)dst + 0.5) * scale - 0.5;
+    if (s < 0.0) s = 0.0;
+    i0 = (int)s;
+    if (i0 > in - 1) i0 = in - 1;                        // (unreachable: s < in - 0.5; keeps every index in bounds whatever scale is)
+    i1 = i0 < in - 1 ? i0 + 1 : i0;
+    lam = s - (double)i0;
+}
+
+// the LDS slots a strip of nr rows from r0 needs (the kernel's rule, restated for loss_plan)
+__host__ __device__ inline int strip_slots(int r0, int nr, double scale, int in, int& ylo, bool& contiguous) {
+    int a, b;
+    double lam;
+    src_coord(r0, scale, in, ylo, b, lam);
+    int yhi;
+    src_coord(r0 + nr - 1, scale, in, a, yhi, lam);
+    const int span = yhi - ylo + 1;
+    contiguous = span <= 2 * nr;
+    return contiguous ? span : 2 * nr;
+}
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
+    return v;
+}
+
+// fac (maps, out_h + out_w): the row factors exp(-(y - cy)^2 / 2 sigma^2), then the column factors; zeros for a map without target
+__global__ __launch_bounds__(DE_THREADS) void factor_kernel(const double* __restrict__ centres, const int* __restrict__ has_target, int out_h, int out_w, int blocks_per_map,
+                                                             double two_sigma2, double* __restrict__ fac) {
+    const int map = ttup_bid_x() / blocks_per_map;
+    const int j = (ttup_bid_x() % blocks_per_map) * DE_THREADS + ttup_tid_x();
+    if (j >= out_h + out_w) return;
+    double f = 0.0;
+    if (has_target[map] != 0) {
+        const double c = j < out_h ? centres[(size_t)map * 2 + 1] : centres[(size_t)map * 2];
+        const double d = (double)(j < out_h ? j : j - out_h) - c;
+        f = exp(-(d * d) / two_sigma2);
+    }
+    fac[(size_t)map * (out_h + out_w) + j] = f;
+}
+
+__global__ __launch_bounds__(DE_THREADS) void loss_kernel(const float* __restrict__ pred, const double* __restrict__ fac, int h, int w, int out_h, int out_w,
+                                                           double scale_y, double scale_x, int strip, int nstrips, int weighted, double* __restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) float rows[];          // [slots][w]
+    __shared__ double s_ly[DE_STRIP], s_gy[DE_STRIP], s_red[DE_WAVES];
+    __shared__ int s_a[DE_STRIP], s_b[DE_STRIP];
+    const int tid = ttup_tid_x();
+    const int map = ttup_bid_x() / nstrips, r0 = (ttup_bid_x() % nstrips) * strip;
+    const int nr = out_h - r0 < strip ? out_h - r0 : strip;
+    int ylo;
+    bool contiguous;
+    const int slots = strip_slots(r0, nr, scale_y, h, ylo, contiguous);
+    const double* f = fac + (size_t)map * (out_h + out_w);
+    if (tid < nr) {
+        int i0, i1;
+        double lam;
+        src_coord(r0 + tid, scale_y, h, i0, i1, lam);
+        s_ly[tid] = lam;
+        s_a[tid] = contiguous ? i0 - ylo : 2 * tid;
+        s_b[tid] = contiguous ? i1 - ylo : 2 * tid + 1;
+        s_gy[tid] = f[r0 + tid];
+    }
+    const float* src = pred + (size_t)map * h * w;
+    for (int s = 0; s < slots; ++s) {
+        int y = ylo + s;
+        if (!contiguous) {
+            int i0, i1;
+            double lam;
+            src_coord(r0 + (s >> 1), scale_y, h, i0, i1, lam);
+            y = (s & 1) ? i1 : i0;
+        }
+        const float* g = src + (size_t)y * w;
+        float* l = rows + (size_t)s * w;
+        for (int x = tid; x < w; x += DE_THREADS) l[x] = g[x];
+    }
+    __syncthreads();
+    const double* gxp = f + out_h;
+    double acc = 0.0;
+    for (int c = tid; c < out_w; c += DE_THREADS) {
+        int x0, x1;
+        double lx;
+        src_coord(c, scale_x, w, x0, x1, lx);
+        const double wx0 = 1.0 - lx, gx = gxp[c];
+        for (int i = 0; i < nr; ++i) {
+            const float* ra = rows + (size_t)s_a[i] * w;
+            const float* rb = rows + (size_t)s_b[i] * w;
+            const double ly = s_ly[i];
+            const double top = wx0 * (double)ra[x0] + lx * (double)ra[x1];
+            const double bot = wx0 * (double)rb[x0] + lx * (double)rb[x1];
+            const double v = (1.0 - ly) * top + ly * bot;
+            const float t = (float)(gx * s_gy[i]);
+            const double d = v - (double)t;
+            double q = d * d;
+            if (weighted && t > 0.1f) q = 100.0 * q;
+            acc = acc + q;
+        }
+    }
+    acc = wave_sum(acc);
+    if ((tid & 63) == 0) s_red[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int k = 0; k < DE_WAVES; ++k) s = s + s_red[k];
+        partial[ttup_bid_x()] = s;
+    }
+}
+
+// one block per map: its strips' partials in fixed order
+__global__ __launch_bounds__(DE_THREADS) void loss_final_kernel(const double* __restrict__ partial, int nstrips, double* __restrict__ sums) {
+    __shared__ double sd[DE_THREADS];
+    const int tid = ttup_tid_x();
+    const double* p = partial + (size_t)ttup_bid_x() * nstrips;
+    double acc = 0.0;
+    for (int i = tid; i < nstrips; i += DE_THREADS) acc = acc + p[i];
+    sd[tid] = acc;
+    __syncthreads();
+    for (int off = DE_THREADS / 2; off >= 1; off >>= 1) {
+        if (tid < off) sd[tid] = sd[tid] + sd[tid + off];
+        __syncthreads();
+    }
+    if (tid == 0) sums[ttup_bid_x()] = sd[0];
+}
+
+// _batched_distance_point_to_segment (helper_balldetection.py:335-399): t = 0 on a segment with L^2 <= 1e-12, clamped to [0, 1]
+__device__ __forceinline__ double segment_distance(double px, double py, double ax, double ay, double bx, double by) {
+    const double sx = bx - ax, sy = by - ay;
+    const double l2 = sx * sx + sy * sy;
+    const double dot = (px - ax) * sx + (py - ay) * sy;
+    double t = 0.0;
+    if (l2 > 1e-12) t = dot / l2;
+    t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t);
+    const double ex = px - (ax + t * sx), ey = py - (ay + t * sy);
+    return sqrt(ex * ex + ey * ey);
+}
+
+__device__ __forceinline__ double nan_min(double a, double b) { return (a <= b || a != a) ? a : b; }          // np.minimum: a NaN wins
+
+// a thread's sums and counts -> one partial per block and quantity: wave butterfly, then the block's waves in order
+__device__ __forceinline__ void block_partials(const double (&s)[DE_SUMS], const int (&c)[DE_COUNTS], int ncounts, long long nblocks, double* __restrict__ psum,
+                                               int* __restrict__ pcnt) {
+    __shared__ double sm[DE_SUMS][DE_WAVES];
+    __shared__ int sc[DE_COUNTS][DE_WAVES];
+    const int tid = ttup_tid_x(), wave = tid >> 6;
+    for (int k = 0; k < DE_SUMS; ++k) {
+        const double v = wave_sum(s[k]);
+        if ((tid & 63) == 0) sm[k][wave] = v;
+    }
+    for (int k = 0; k < DE_COUNTS; ++k) {
+        const int v = wave_sum(c[k]);
+        if ((tid & 63) == 0) sc[k][wave] = v;
+    }
+    __syncthreads();
+    const long long blk = ttup_bid_x();
+    if (tid < DE_SUMS) {
+        double v = 0.0;
+        for (int k = 0; k < DE_WAVES; ++k) v = v + sm[tid][k];
+        psum[(long long)tid * nblocks + blk] = v;
+    } else if (tid >= 64 && tid < 64 + ncounts) {
+        const int q = tid - 64;
+        int v = 0;
+        for (int k = 0; k < DE_WAVES; ++k) v += sc[q][k];
+        pcnt[(long long)q * nblocks + blk] = v;
+    }
+}
+
+// sums: 0 distance to gt  1 distance to the streak as val() measures it, both over the visible samples with a detection (x, y > -100)
+// counts: 0 visible (vis == 1)  1 of those, prediction flagged visible (pred[2] == 1: PCK's denominator)  2 of those, detected
+//         3 + k: within tolerance k of the streak and flagged visible
+__global__ __launch_bounds__(DE_THREADS) void ball_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt, const float* __restrict__ gt_min,
+                                                                   const float* __restrict__ gt_max, const int* __restrict__ vis, long long n, Tolerances tol,
+                                                                   long long nblocks, double* __restrict__ psum, int* __restrict__ pcnt) {
+    const long long i = (long long)ttup_bid_x() * DE_THREADS + ttup_tid_x();
+    double s[DE_SUMS] = {0.0, 0.0};
+    int c[DE_COUNTS];
+    for (int k = 0; k < DE_COUNTS; ++k) c[k] = 0;
+    if (i < n && vis[i] == 1) {
+        const double px = pred[i * 3], py = pred[i * 3 + 1];
+        const double gx = gt[i * 2], gy = gt[i * 2 + 1], ax = gt_min[i * 2], ay = gt_min[i * 2 + 1], bx = gt_max[i * 2], by = gt_max[i * 2 + 1];
+        const bool flagged = pred[i * 3 + 2] == VISIBLE, detected = px > NOT_DETECTED && py > NOT_DETECTED;
+        c[0] = 1;
+        c[1] = flagged;
+        c[2] = detected;
+        // calculate_pck_fixed_tolerance (:228-230): the segments gt_min -> gt and gt -> gt_max
+        const double dp = nan_min(segment_distance(px, py, ax, ay, gx, gy), segment_distance(px, py, gx, gy, bx, by));
+        for (int k = 0; k < tol.n; ++k) c[3 + k] = flagged && dp <= tol.v[k];
+        if (detected) {
+            const double dx = px - gx, dy = py - gy;
+            s[0] = sqrt(dx * dx + dy * dy);
+            // train.py:220 calls distance_to_streak(pred, gt, gt_min, gt_max) against the signature (pred, r_min, r_b, r_max): the
+            // segments it measures are gt -> gt_min and gt_min -> gt_max
+            s[1] = nan_min(segment_distance(px, py, gx, gy, ax, ay), segment_distance(px, py, ax, ay, bx, by));
+        }
+    }
+    block_partials(s, c, 3 + tol.n, nblocks, psum, pcnt);
+}
+
+// one thread per keypoint.  sums: 0 distance over valid & visible (1 unused).  counts: 0 valid (pred[2] == 1)  1 valid & visible
+// (gt[2] == 1)  2 unused  3 + k: of those, within tolerance k
+__global__ __launch_bounds__(DE_THREADS) void table_metrics_kernel(const float* __restrict__ pred, const float* __restrict__ gt, long long n, Tolerances tol,
+                                                                    long long nblocks, double* __restrict__ psum, int* __restrict__ pcnt) {
+    const long long i = (long long)ttup_bid_x() * DE_THREADS + ttup_tid_x();
+    double s[DE_SUMS] = {0.0, 0.0};
+    int c[DE_COUNTS];
+    for (int k = 0; k < DE_COUNTS; ++k) c[k] = 0;
+    if (i < n) {
+        const bool valid = pred[i * 3 + 2] == VISIBLE, both = valid && gt[i * 3 + 2] == VISIBLE;
+        c[0] = valid;
+        c[1] = both;
+        if (both) {
+            const double dx = (double)pred[i * 3] - (double)gt[i * 3], dy = (double)pred[i * 3 + 1] - (double)gt[i * 3 + 1];
+            const double d = sqrt(dx * dx + dy * dy);
+            s[0] = d;
+            for (int k = 0; k < tol.n; ++k) c[3 + k] = d <= tol.v[k];
+        }
+    }
+    block_partials(s, c, 3 + tol.n, nblocks, psum, pcnt);
+}
+
+// one block per quantity (DE_SUMS + ncounts blocks): its per-block partials in fixed order; counts[ncounts] = n
+__global__ __launch_bounds__(DE_THREADS) void metrics_final_kernel(const double* __restrict__ psum, const int* __restrict__ pcnt, long long nblocks, int ncounts, long long n,
+                                                                    double* __restrict__ sums, long long* __restrict__ counts) {
+    __shared__ double sd[DE_THREADS];
+    __shared__ long long sl[DE_THREADS];
+    const int tid = ttup_tid_x(), q = ttup_bid_x();
+    if (q < DE_SUMS) {
+        double acc = 0.0;
+        for (long long i = tid; i < nblocks; i += DE_THREADS) acc = acc + psum[(long long)q * nblocks + i];
+        sd[tid] = acc;
+        __syncthreads();
+        for (int off = DE_THREADS / 2; off >= 1; off >>= 1) {
+            if (tid < off) sd[tid] = sd[tid] + sd[tid + off];
+            __syncthreads();
+        }
+        if (tid == 0) sums[q] = sd[0];
+    } else {
+        const int c = q - DE_SUMS;
+        long long acc = 0;
+        for (long long i = tid; i < nblocks; i += DE_THREADS) acc += pcnt[(long long)c * nblocks + i];
+        sl[tid] = acc;
+        __syncthreads();
+        for (int off = DE_THREADS / 2; off >= 1; off >>= 1) {
+            if (tid < off) sl[tid] += sl[tid + off];
+            __syncthreads();
+        }
+        if (tid == 0) counts[c] = sl[0];
+    }
+    if (q == 0 && tid == 0) counts[ncounts] = n;
+}
+
+// the largest strip height whose source rows fit DE_ROW_BYTES -> (strip, slots); strip = 0 when two rows do not fit
+void loss_plan(int h, int w, int out_h, int& strip, int& slots) {
+    const double scale = (double)h / (double)out_h;
+    for (strip = DE_STRIP; strip >= 1; --strip) {
+        slots = 0;
+        for (int r0 = 0; r0 < out_h; r0 += strip) {
+            int ylo;
+            bool contiguous;
+            const int s = strip_slots(r0, out_h - r0 < strip ? out_h - r0 : strip, scale, h, ylo, contiguous);
+            slots = s > slots ? s : slots;
+        }
+        if ((size_t)slots * w * sizeof(float) <= DE_ROW_BYTES) return;
+    }
+}
+
+long long metric_blocks(long long n) { return (n + DE_THREADS - 1) / DE_THREADS; }
+size_t metrics_workspace_bytes(long long n) { return n > 0 ? (size_t)metric_blocks(n) * (DE_SUMS * sizeof(double) + DE_COUNTS * sizeof(int)) : 0; }
+// the factors of every map, then one partial per map and strip (out_h strips at most: strip height 1)
+size_t loss_workspace_bytes(long long maps, int out_h, int out_w) {
+    return maps > 0 && out_h > 0 && out_w > 0 ? (size_t)maps * ((size_t)2 * out_h + out_w) * sizeof(double) : 0;
+}
+
+int check_tolerances(const char* who, const double* tol, int ntol, Tolerances& t) {
+    TTUP_REQUIRE(tol != nullptr, TTUP_EINVAL, "%s: null pointer", who);
+    TTUP_REQUIRE(ntol >= 1 && ntol <= DE_MAX_TOL, TTUP_EINVAL, "%s: need 1 to %d tolerances, got %d", who, DE_MAX_TOL, ntol);
+    for (int k = 0; k < DE_MAX_TOL; ++k) t.v[k] = k < ntol ? tol[k] : 0.0;
+    t.n = ntol;
+    return TTUP_OK;
+}
+
+int check_metrics(const char* who, long long n, const void* ws, size_t ws_bytes) {
+    TTUP_REQUIRE(n > 0, TTUP_EINVAL, "%s: need at least one sample, got n = %lld", who, n);
+    TTUP_REQUIRE(((size_t)ws & 7) == 0, TTUP_EINVAL, "%s: the workspace must be 8-byte aligned", who);
+    TTUP_REQUIRE(ws_bytes >= metrics_workspace_bytes(n), TTUP_EINVAL, "%s: workspace of %zu bytes, need %zu (ttup_detect_metrics_workspace_bytes)", who, ws_bytes,
+                 metrics_workspace_bytes(n));
+    return TTUP_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ttup_detect_loss_workspace_bytes(int n_maps, int out_h, int out_w) { return loss_workspace_bytes(n_maps, out_h, out_w); }
+
+extern "C" size_t ttup_detect_metrics_workspace_bytes(int n_items) { return metrics_workspace_bytes(n_items); }
+
+extern "C" int ttup_detect_heatmap_loss(const float* pred_dev, const double* centres_dev, const int* has_target_dev, int n, int c, int h, int w, double sigma, int out_h,
+                                        int out_w, int weighted, void* workspace_dev, size_t workspace_bytes, double* sums_dev, void* stream) {
+    const char* who = "ttup_detect_heatmap_loss";
+    TTUP_REQUIRE(pred_dev && centres_dev && has_target_dev && workspace_dev && sums_dev, TTUP_EINVAL, "%s: null pointer", who);
+    TTUP_REQUIRE(n > 0 && c > 0, TTUP_EINVAL, "%s: need at least one sample and one channel, got n = %d, c = %d", who, n, c);
+    TTUP_REQUIRE(h > 0 && w > 0 && out_h > 0 && out_w > 0, TTUP_EINVAL, "%s: empty heatmap or output: (%d, %d) -> (%d, %d)", who, h, w, out_h, out_w);
+    TTUP_REQUIRE(sigma > 0.0, TTUP_EINVAL, "%s: sigma must be positive, got %g", who, sigma);          // (a NaN fails the comparison too)
+    const long long maps = (long long)n * c;
+    int strip, slots;
+    loss_plan(h, w, out_h, strip, slots);
+    TTUP_REQUIRE(strip >= 1, TTUP_EINVAL, "%s: two source rows of %d floats do not fit the %zu bytes of LDS a workgroup keeps them in (w <= %zu)", who, w, DE_ROW_BYTES,
+                 DE_ROW_BYTES / (2 * sizeof(float)));
+    const int nstrips = (out_h + strip - 1) / strip;
+    const int fblocks = (out_h + out_w + DE_THREADS - 1) / DE_THREADS;
+    TTUP_REQUIRE(maps * nstrips <= 0x7fffffffLL && maps * fblocks <= 0x7fffffffLL, TTUP_EINVAL, "%s: %lld maps of %d strips exceed the grid", who, maps, nstrips);
+    TTUP_REQUIRE(((size_t)workspace_dev & 7) == 0, TTUP_EINVAL, "%s: the workspace must be 8-byte aligned", who);
+    TTUP_REQUIRE(workspace_bytes >= loss_workspace_bytes(maps, out_h, out_w), TTUP_EINVAL, "%s: workspace of %zu bytes, need %zu (ttup_detect_loss_workspace_bytes)", who,
+                 workspace_bytes, loss_workspace_bytes(maps, out_h, out_w));
+    double* fac = (double*)workspace_dev;
+    double* partial = fac + (size_t)maps * (out_h + out_w);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(factor_kernel, dim3((unsigned)(maps * fblocks)), dim3(DE_THREADS), 0, st, centres_dev, has_target_dev, out_h, out_w, fblocks, 2.0 * sigma * sigma, fac);
+    TTUP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(loss_kernel, dim3((unsigned)(maps * nstrips)), dim3(DE_THREADS), (size_t)slots * w * sizeof(float), st, pred_dev, (const double*)fac, h, w, out_h, out_w,
+                       (double)h / (double)out_h, (double)w / (double)out_w, strip, nstrips, weighted ? 1 : 0, partial);
+    TTUP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(loss_final_kernel, dim3((unsigned)maps), dim3(DE_THREADS), 0, st, (const double*)partial, nstrips, sums_dev);
+    TTUP_LAUNCH_CHECK();
+    return TTUP_OK;
+}
+
+extern "C" int ttup_detect_ball_metrics(const float* pred_pos_dev, const float* gt_dev, const float* gt_min_dev, const float* gt_max_dev, const int* vis_dev, int n,
+                                        const double* tolerances, int n_tolerances, void* workspace_dev, size_t workspace_bytes, double* sums_dev,
+                                        long long* counts_dev, void* stream) {
+    const char* who = "ttup_detect_ball_metrics";
+    TTUP_REQUIRE(pred_pos_dev && gt_dev && gt_min_dev && gt_max_dev && vis_dev && workspace_dev && sums_dev && counts_dev, TTUP_EINVAL, "%s: null pointer", who);
+    Tolerances tol;
+    if (int rc = check_tolerances(who, tolerances, n_tolerances, tol)) return rc;
+    if (int rc = check_metrics(who, n, workspace_dev, workspace_bytes)) return rc;
+    const long long nb = metric_blocks(n);
+    double* psum = (double*)workspace_dev;
+    int* pcnt = (int*)(psum + nb * DE_SUMS);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(ball_metrics_kernel, dim3((unsigned)nb), dim3(DE_THREADS), 0, st, pred_pos_dev, gt_dev, gt_min_dev, gt_max_dev, vis_dev, (long long)n, tol, nb, psum, pcnt);
+    TTUP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(metrics_final_kernel, dim3(DE_SUMS + 3 + tol.n), dim3(DE_THREADS), 0, st, (const double*)psum, (const int*)pcnt, nb, 3 + tol.n, (long long)n, sums_dev,
+                       counts_dev);
+    TTUP_LAUNCH_CHECK();
+    return TTUP_OK;
+}
+
+extern "C" int ttup_detect_table_metrics(const float* pred_pos_dev, const float* gt_dev, int n, int keypoints, const double* tolerances, int n_tolerances,
+                                         void* workspace_dev, size_t workspace_bytes, double* sums_dev, long long* counts_dev, void* stream) {
+    const char* who = "ttup_detect_table_metrics";
+    TTUP_REQUIRE(pred_pos_dev && gt_dev && workspace_dev && sums_dev && counts_dev, TTUP_EINVAL, "%s: null pointer", who);
+    Tolerances tol;
+    if (int rc = check_tolerances(who, tolerances, n_tolerances, tol)) return rc;
+    TTUP_REQUIRE(n > 0 && keypoints > 0, TTUP_EINVAL, "%s: need at least one sample and one keypoint, got n = %d, keypoints = %d", who, n, keypoints);
+    const long long items = (long long)n * keypoints;
+    TTUP_REQUIRE(items <= 0x7fffffffLL, TTUP_EINVAL, "%s: %lld keypoints exceed 2^31 - 1", who, items);
+    if (int rc = check_metrics(who, items, workspace_dev, workspace_bytes)) return rc;
+    const long long nb = metric_blocks(items);
+    double* psum = (double*)workspace_dev;
+    int* pcnt = (int*)(psum + nb * DE_SUMS);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(table_metrics_kernel, dim3((unsigned)nb), dim3(DE_THREADS), 0, st, pred_pos_dev, gt_dev, items, tol, nb, psum, pcnt);
+    TTUP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(metrics_final_kernel, dim3(DE_SUMS + 3 + tol.n), dim3(DE_THREADS), 0, st, (const double*)psum, (const int*)pcnt, nb, 3 + tol.n, items, sums_dev,
+                       counts_dev);
+    TTUP_LAUNCH_CHECK();
+    return TTUP_OK;
+}
+
+#include "no_packed_fp32_end.h"

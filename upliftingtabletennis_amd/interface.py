@@ -20,7 +20,8 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, calib, glue, inference, refine, uplift, vitpose, wasb, weights
+from . import _lib, calib, detect_eval, glue, inference, refine, uplift, vitpose, wasb, weights
+from .detect_eval import ball_val_metrics, heatmap_loss, table_val_metrics  # noqa: F401  (the evaluation functions, beside the detectors they measure)
 
 HEIGHT, WIDTH = 1080, 1920
 KEYPOINT_VISIBLE = 1
@@ -141,6 +142,11 @@ class _HubDetector:
         h, w = self.heat_hw
         return refine.refine_windows_device(idx.reshape(-1), win.reshape(-1, 9), h, w, self.resolution[0], self.resolution[1], _lib.REFINE_TABLE)
 
+    def refine_peaks_as(self, idx, win, variant):
+        """`refine_peaks` with the fit of `variant` (_lib.REFINE_BALL: what the ball val() refines with, helper_balldetection.py:29-110)."""
+        h, w = self.heat_hw
+        return refine.refine_windows_device(idx.reshape(-1), win.reshape(-1, 9), h, w, self.resolution[0], self.resolution[1], variant)
+
     def calibrate(self, frames_u8=None, x=None):
         """First eps, on the first input this detector sees (a uint8 clip or a float input); a no-op after it and when uncertified."""
         if self.cert is not None and not self.model.certified:
@@ -214,6 +220,39 @@ class BallDetector(_HubDetector):
             return np.zeros((0, 3)), np.zeros((0, 1) + self.heat_hw, np.float32)
         return np.concatenate(pred_pos, axis=0), np.concatenate(preds, axis=0)
 
+    def val(self, images, ball_coords, min_coords, max_coords, vis, sigma=6, refine='ball', tolerances=(2, 5, 10), batch_size=None):
+        """The reference's ball val() (balldetection/train.py:144-245) on this detector.  images: list (length B) of [prev, curr, next]
+        BGR uint8 HWC arrays, as `predict` takes them; ball_coords / min_coords / max_coords (B,2) annotations in 1920x1080 px (the
+        ball and the two ends of its motion-blur streak); vis (B,) with BALL_VISIBLE = 1.
+        -> {'loss', 'pck@2', 'pck@5', 'pck@10', 'avg_dist', 'dist_streak', the counts of detect_eval.ball_val_metrics, 'loss_sums' (B,1)}.
+
+        The forward runs in chunks of `max_batch`; the peaks are refined on the device (refine='ball' as val() does, 'table' as
+        inference_balldetection.py:94), positions and per-sample loss sums stay there, one metrics launch finishes, and the one
+        read-back of the result is the only synchronisation.  The loss is val()'s unweighted nn.MSELoss at 1080x1920 against a
+        Gaussian of `sigma` px around ball_coords (zeros where vis is BALL_INVISIBLE, as the TTHQ loader builds them); batch_size:
+        the loader's batch size, whose per-batch means val() averages (None: one batch)."""
+        variant = detect_eval.refine_variant(refine)
+        n = len(images)
+        centres = np.asarray(ball_coords, np.float64).reshape(n, 1, 2)
+        vis = np.asarray(vis).reshape(n)
+        has = (vis != detect_eval.BALL_INVISIBLE).astype(np.int32).reshape(n, 1)
+        w, h = self.model_resolution
+        pos, sums = [], []
+        for b0 in range(0, n, self.max_batch):
+            b1 = min(n, b0 + self.max_batch)
+            xs = [wasb.preprocess_triples(self._upload(imgs), (w, h)) for imgs in images[b0:b1]]
+            heat, idx, win = self._certified_forward(torch.cat(xs))
+            pos.append(self.refine_peaks_as(idx, win, variant))
+            sums.append(detect_eval.heatmap_loss_device(heat, centres[b0:b1], has[b0:b1], sigma, False, (HEIGHT, WIDTH)))
+        if not pos:
+            raise ValueError('need at least one sample')
+        loss_sums = torch.cat(sums)
+        msums, counts = detect_eval.ball_metrics_device(torch.cat(pos), ball_coords, min_coords, max_coords, vis, tolerances)
+        msums, counts, loss_sums = detect_eval.read_back(msums, counts, loss_sums)
+        out = detect_eval.finish_ball(msums, counts, [float(t) for t in tolerances])
+        out.update(loss=detect_eval.loss_from_sums(loss_sums, (HEIGHT, WIDTH), batch_size), loss_sums=loss_sums)
+        return out
+
     def predict_clip(self, images):
         """Fast path for consecutive frames (what TableTennisPipeline.predict feeds the detector, interface.py:276-279):
         images = list of N BGR uint8 HWC frames -> pred_pos (N-2, 3), the same values `predict` returns for the triples
@@ -263,6 +302,32 @@ class TableDetector(_HubDetector):
         if not pred_pos:
             return np.zeros((0, 13, 3)), np.zeros((0, 1, 13) + self.heat_hw, np.float32)
         return np.concatenate(pred_pos, axis=0), np.concatenate(preds, axis=0)
+
+    def val(self, images, table_coords, sigma=6, tolerances=(2, 5, 10), batch_size=None):
+        """The reference's table val() (tabledetection/train.py:131-201) on this detector.  images: list (length B) of BGR uint8 HWC
+        frames; table_coords (B,13,3) [x, y, visibility] annotations in 1920x1080 px (the loader's integer pixel positions).
+        -> {'loss', 'pck@2', 'pck@5', 'pck@10', 'avg_dist', 'ratio_detected', the counts of detect_eval.table_val_metrics,
+        'loss_sums' (B,13)}.  Runs like `BallDetector.val`; the loss is val()'s weighted_mse_loss, against zeros for a keypoint
+        whose visibility is not KEYPOINT_VISIBLE."""
+        n = len(images)
+        coords = np.asarray(table_coords, np.float64).reshape(n, 13, 3)
+        centres = np.ascontiguousarray(coords[:, :, :2])
+        has = (coords[:, :, 2] == KEYPOINT_VISIBLE).astype(np.int32)
+        pos, sums = [], []
+        for b0 in range(0, n, self.max_batch):
+            b1 = min(n, b0 + self.max_batch)
+            fr = self._upload(images[b0:b1])
+            heat, idx, win = self._certified_forward(wasb.preprocess_frames(fr, self.model_resolution))
+            pos.append(self.refine_peaks(idx, win).reshape(-1, 13, 3))
+            sums.append(detect_eval.heatmap_loss_device(heat, centres[b0:b1], has[b0:b1], sigma, True, (HEIGHT, WIDTH)))
+        if not pos:
+            raise ValueError('need at least one sample')
+        loss_sums = torch.cat(sums)
+        msums, counts = detect_eval.table_metrics_device(torch.cat(pos), coords, tolerances)
+        msums, counts, loss_sums = detect_eval.read_back(msums, counts, loss_sums)
+        out = detect_eval.finish_table(msums, counts, [float(t) for t in tolerances])
+        out.update(loss=detect_eval.loss_from_sums(loss_sums, (HEIGHT, WIDTH), batch_size), loss_sums=loss_sums)
+        return out
 
     def predict_keypoints(self, images):
         """`predict` without the heatmaps: (B,13,3) keypoints only.  Pre-processing, CNN, per-channel argmax and windows run
