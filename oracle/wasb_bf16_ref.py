@@ -46,6 +46,12 @@ and its input channels reversed (any fp32 summation order is a legitimate sample
 flips alone produce; the float64 evaluation is the reference.  variant='f32' is the same with K as stored: a second draw, used
 to see how far two legitimate orders differ from each other.
 
+fp32 storage (`Weights(rounding='f32')`, tests/test_wasb_f32_taps_gpu.py): the fp32 net's numbers in float64.  The folded weights
+and biases are rounded to float32 once, as csrc/wasb_blob.h stores them, the two-source conv adds its two biases in float
+(pack_conv), the head keeps its float weights -- and no activation is ever rounded.  The fp32 graph is the layer-by-layer one
+(csrc/wasb_graph.h builds fused ops for bf16 only), so the model is 'layerwise' and stage4_0 is a tap; without activation rounding
+the two models compute the same values.  The 'f32r' / 'f32' variants are then two fp32 evaluations of the same segment.
+
 Nothing here comes from the reference project: it is this project's graph (csrc/wasb_graph.h) with rounding added.
 """
 import torch
@@ -86,11 +92,14 @@ def _identity(x):
 
 class Weights:
     """The convs of a reference-format state dict with eval-mode BatchNorm folded in (an already folded dict -- conv weights and
-    biases, no BatchNorm keys -- is taken as it is).  rounding=True: stored as the device stores them (see the module docstring);
-    rounding=False: float64 throughout, for the comparison with oracle/wasb_ref.py."""
+    biases, no BatchNorm keys -- is taken as it is).  rounding=True: stored as the device's bf16 net stores them (see the module
+    docstring); rounding=False: float64 throughout, for the comparison with oracle/wasb_ref.py; rounding='f32': stored as the
+    device's fp32 net stores them -- folded in double, rounded to float32 once -- with activations never rounded."""
 
     def __init__(self, state_dict, prefix='model', rounding=True):
+        assert rounding in (True, False, 'f32'), rounding
         self.sd, self.p, self.rounding = state_dict, prefix, rounding
+        self.round_activations = rounding is True
         self._cache = {}
 
     def _t(self, key):
@@ -108,7 +117,9 @@ class Weights:
                 s = self._t(n + '.weight') / torch.sqrt(self._t(n + '.running_var') + BN_EPS)
                 w = w * s.view(-1, 1, 1, 1)
                 b = (b - self._t(n + '.running_mean')) * s + self._t(n + '.bias')
-            if self.rounding:
+            if self.rounding == 'f32':
+                w, b = w.float().double(), b.float().double()
+            elif self.rounding:
                 w, b = bf16_round(w.float()), b.float().double()
             self._cache[key] = (w, b)
         return self._cache[key]
@@ -117,6 +128,8 @@ class Weights:
         w, b = self._t(self.p + '.final_layers.0.weight'), self._t(self.p + '.final_layers.0.bias')
         if w.shape[0] == 3:          # the ball detector keeps the middle one of its three maps
             w, b = w[1:2], b[1:2]
+        if self.rounding == 'f32':
+            w, b = w.float().double(), b.float().double()
         return w, b
 
 
@@ -124,7 +137,7 @@ class _Eval:
     def __init__(self, weights, model, variant):
         assert model in MODELS and variant in ('f64', 'f32r', 'f32'), (model, variant)
         self.w, self.fused, self.f32, self.flip = weights, model == 'fused', variant != 'f64', variant == 'f32r'
-        self.rnd = bf16_round if weights.rounding else _identity
+        self.rnd = bf16_round if weights.round_activations else _identity
 
     def up(self, v):          # the working precision
         return v.float() if self.f32 else v.double()
