@@ -437,6 +437,16 @@ int    ttup_uplift_val_real_metrics(const float* pred_rot_dev, const float* pred
  *   last row / column; h, w may exceed the output), target = float32(exp(-((x-cx)^2 + (y-cy)^2) / (2 sigma^2))) or zeros where
  *   has_target is 0, weight = 100 where weighted and target > 0.1f, else 1 (weighted_mse_loss; weighted = 0: nn.MSELoss).
  *   Two source rows must fit the 60 KB of LDS a workgroup keeps them in: w <= 7680, else TTUP_EINVAL.
+ * ttup_detect_heatmap_loss_grad: the same inputs and the same up, target and weight; writes the gradient of
+ *   scale * sum over maps and output pixels of weight * (up(pred) - target)^2 with respect to pred,
+ *     grad_dev[m, i, j] = float32(scale * sum_y sum_x 2 weight(y,x) (up(pred)[m,y,x] - target[m,y,x]) a_y(i) b_x(j)),
+ *   a_y(i) the weight with which output row y reads source row i (1 - lambda on y0, lambda on y1, their sum where the clamp makes
+ *   y0 == y1), b_x(j) the same for columns; fp64, rounded once on the store; a source row or column no output pixel reads gets +0.0.
+ *   scale = 1 / (n c out_h out_w): the reference's loss.backward() into the network's output, before F.interpolate.  A gather: each
+ *   source pixel is summed by one thread in a fixed order (two calls return the same bits), and nothing of the output resolution is
+ *   written to device memory.  sums_dev (n*c, may be null: no sums wanted) receives what ttup_detect_heatmap_loss writes for the
+ *   same inputs, bit for bit.  TTUP_EINVAL also for a non-finite scale; the width limit is the loss pass's (w <= 7680),
+ *   whether sums are asked for or not.  ttup_detect_loss_grad_workspace_bytes: the workspace of both passes (0 for an empty shape).
  * ttup_detect_ball_metrics: pred_pos (n,3) [x, y, visibility]; gt, gt_min, gt_max (n,2); vis (n) int32.  Over the samples with
  *   vis == 1 (train.py:207-220):
  *   sums_dev[2]: over those with a detection (x, y > -100), the distance to gt, and the distance to the streak as val() measures
@@ -452,6 +462,10 @@ size_t ttup_detect_loss_workspace_bytes(int n_maps, int out_h, int out_w);
 size_t ttup_detect_metrics_workspace_bytes(int n_items);
 int    ttup_detect_heatmap_loss(const float* pred_dev, const double* centres_dev, const int* has_target_dev, int n, int c, int h, int w, double sigma, int out_h,
                                 int out_w, int weighted, void* workspace_dev, size_t workspace_bytes, double* sums_dev, void* stream);
+size_t ttup_detect_loss_grad_workspace_bytes(int n_maps, int h, int w, int out_h, int out_w);
+int    ttup_detect_heatmap_loss_grad(const float* pred_dev, const double* centres_dev, const int* has_target_dev, int n, int c, int h, int w, double sigma, int out_h,
+                                     int out_w, int weighted, double scale, void* workspace_dev, size_t workspace_bytes, double* sums_dev, float* grad_dev,
+                                     void* stream);
 int    ttup_detect_ball_metrics(const float* pred_pos_dev, const float* gt_dev, const float* gt_min_dev, const float* gt_max_dev, const int* vis_dev, int n,
                                 const double* tolerances, int n_tolerances, void* workspace_dev, size_t workspace_bytes, double* sums_dev,
                                 long long* counts_dev, void* stream);

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Time of evaluating the detectors on the device (BallDetector.val / TableDetector.val, csrc/detect_eval.hip), one JSON line: per
 detector the forward alone (`_certified_forward` on a pre-processed batch), the heatmap-loss launch on its heatmaps at 1080x1920,
-the metrics launch, and the whole `val` call from host frames (upload and pre-processing included).  Launch times are device
+the metrics launch, and the whole `val` call from host frames (upload and pre-processing included); with --grad also the gradient of
+that loss into the heatmaps: the gradient launch alone (factors + grad_kernel, no sums asked for), as a multiple
+of the loss launch of the same run, and the whole `heatmap_loss_grad_device` call (sums and gradient).  Launch times are device
 events around `--inner` back-to-back calls on preallocated inputs; every timed call is preceded by a warm-up call of the same
 shape; best and mean of --repeat.  The loss rate is output pixels per second (the kernel's work is per output pixel).
 
 Without checkpoints (TTUP_WEIGHTS) the detectors run on seeded weights: the times do not depend on the weights.
 
-    python tools/bench_detect_eval.py [--triples 64] [--frames 16] [--repeat 3] [--inner 5]
+    python tools/bench_detect_eval.py [--triples 64] [--frames 16] [--repeat 3] [--inner 5] [--grad]
 """
 import argparse
 import json
@@ -53,6 +55,23 @@ def event_timed(launch, repeat, inner):
     return min(ts), sum(ts) / len(ts)
 
 
+def grad_launch(heat, centres, has, weighted):
+    """-> a callable that enqueues the gradient alone (ttup_detect_heatmap_loss_grad without sums) on preallocated buffers"""
+    lib = _lib.load()
+    heat = heat.to(torch.float32).contiguous()
+    n, c, h, w = heat.shape
+    centres, has = centres.to(torch.float64).contiguous(), has.to(torch.int32).contiguous()
+    nbytes = int(lib.ttup_detect_loss_grad_workspace_bytes(n * c, h, w, HEIGHT, WIDTH))
+    ws = torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=heat.device)
+    grad = torch.empty_like(heat)
+    scale = 1.0 / (n * c * HEIGHT * WIDTH)
+
+    def launch():
+        _lib.check(lib.ttup_detect_heatmap_loss_grad(_lib.ptr(heat), _lib.ptr(centres), _lib.ptr(has), n, c, h, w, 6.0, HEIGHT, WIDTH, 1 if weighted else 0, scale,
+                                                     _lib.ptr(ws), nbytes, None, _lib.ptr(grad), _lib.stream_ptr()))
+    return launch
+
+
 def measure(det, x, centres, has, weighted, metrics, val, a):
     """forward / loss / metrics / val times of one detector -> dict"""
     res = {}
@@ -63,6 +82,13 @@ def measure(det, x, centres, has, weighted, metrics, val, a):
     best, mean = event_timed(lambda: detect_eval.heatmap_loss_device(heat, centres, has, 6, weighted, (HEIGHT, WIDTH)), a.repeat, a.inner)
     pixels = heat.shape[0] * heat.shape[1] * HEIGHT * WIDTH
     res.update({'heat_shape': list(heat.shape), 'loss_ms_best': best * 1e3, 'loss_ms_mean': mean * 1e3, 'loss_gpixel_per_s_best': pixels / best * 1e-9})
+    if a.grad:
+        best_loss = best
+        launch = grad_launch(heat, centres, has, weighted)
+        best, mean = event_timed(launch, a.repeat, a.inner)
+        res.update({'grad_ms_best': best * 1e3, 'grad_ms_mean': mean * 1e3, 'grad_over_loss_best': best / best_loss, 'grad_gpixel_per_s_best': pixels / best * 1e-9})
+        best, mean = event_timed(lambda: detect_eval.heatmap_loss_grad_device(heat, centres, has, 6, weighted, (HEIGHT, WIDTH)), a.repeat, a.inner)
+        res['loss_grad_ms_best'], res['loss_grad_ms_mean'] = best * 1e3, mean * 1e3
     best, mean = event_timed(metrics, a.repeat, a.inner)
     res['metrics_us_best'], res['metrics_us_mean'] = best * 1e6, mean * 1e6
     best, mean = host_timed(val, a.repeat)
@@ -76,6 +102,7 @@ def main():
     ap.add_argument('--frames', type=int, default=16)
     ap.add_argument('--repeat', type=int, default=3)
     ap.add_argument('--inner', type=int, default=5)
+    ap.add_argument('--grad', action='store_true', help='also time the gradient of the heatmap loss')
     a = ap.parse_args()
     _lib.require_gpu()
     warnings.simplefilter('ignore')

@@ -83,6 +83,8 @@ SIGNATURES = {
     'ttup_detect_loss_workspace_bytes': (_sz, [_i, _i, _i]),
     'ttup_detect_metrics_workspace_bytes': (_sz, [_i]),
     'ttup_detect_heatmap_loss': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _c.c_double, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    'ttup_detect_loss_grad_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'ttup_detect_heatmap_loss_grad': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _c.c_double, _i, _i, _i, _c.c_double, _vp, _sz, _vp, _vp, _vp]),
     'ttup_detect_ball_metrics': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _c.POINTER(_c.c_double), _i, _vp, _sz, _vp, _vp, _vp]),
     'ttup_detect_table_metrics': (_i, [_vp, _vp, _i, _i, _c.POINTER(_c.c_double), _i, _vp, _sz, _vp, _vp, _vp]),
     'ttup_trajgen_max_samples': (_i, []),

@@ -24,8 +24,12 @@
 // Sums: thread (columns in order, rows in order) -> xor butterfly over the wave -> the block's 4 waves in order (one partial per
 // strip, in the workspace) -> final kernel: one block per map, thread i adds the partials i, i + 256, ... in order, then a
 // 256-leaf tree in LDS.  No floating-point atomics: two calls return the same bits.  The metric kernels use the same tree.
+//
+// The gradient of that loss into the predicted heatmaps (ttup_detect_heatmap_loss_grad) is grad_kernel, described where it stands;
+// what it decides without a device is csrc/detect_grad_plan.h.
 #include "no_packed_fp32_begin.h"
 #include "common.h"
+#include "detect_grad_plan.h"
 
 #include <math.h>
 
@@ -180,6 +184,83 @@ __global__ __launch_bounds__(DE_THREADS) void loss_final_kernel(const double* __
         __syncthreads();
     }
     if (tid == 0) sums[ttup_bid_x()] = sd[0];
+}
+
+// ---- the gradient of the heatmap loss into pred: grad = scale * sum_y sum_x 2 w (up - t) a_y(i) b_x(j)
+//
+// Gather.  One workgroup takes `strip` source rows r0 .. and one group of source columns of one map (detect_grad_plan.h), copies
+// them with one neighbour row above and below and one neighbour column left and right into LDS, and walks the output rows that read
+// those rows, in order: the rows whose upper source row y0 is r0 - 1 .. r0 + nr - 1.  A lane serves one source column j: per
+// output row it interpolates the column pair (j, j + 1) vertically once, walks the output columns x whose left source column is j
+// -- [dg_first(j), dg_first(j + 1)): x0 is j by the plan, never recomputed -- forms r = 2 w (up - t) and adds b_x(j) r to cA,
+// b_x(j + 1) r to cB.  cA belongs to column j, cB to column j + 1; both go, times a_y(y0) and a_y(y0 + 1), to the accumulators of the
+// rows y0 and y0 + 1.  Only those two rows are open at a time: when y0 moves on, row y0 is complete; column j's value is its own A
+// plus the B of the lane before (one shuffle), scaled, rounded once and stored; the accumulators shift.  Lane 0 of a wave serves
+// the last column of the wave before, for its B alone, so a wave never needs another wave's registers: after the LDS copy there
+// is no barrier, nothing of the output resolution is written anywhere, no two lanes add to the same value and the order of every
+// sum is fixed.  A row or column nothing reads keeps accumulators of 0 and is stored as +0.0 whatever scale's sign.
+__global__ __launch_bounds__(DG_MAX_WAVES * 64) void grad_kernel(const float* __restrict__ pred, const double* __restrict__ fac, int h, int w, int out_h, int out_w,
+                                                                  double scale_y, double scale_x, int strip, int nstrips, int waves, int groups, int weighted, double scale,
+                                                                  float* __restrict__ grad) {
+    extern __shared__ __attribute__((aligned(16))) float g_rows[];          // [strip + 2][cw]
+    const int tid = ttup_tid_x(), wave = tid >> 6, lane = tid & 63;
+    const int group = ttup_bid_x() % groups, sid = ttup_bid_x() / groups;
+    const int map = sid / nstrips, r0 = (sid % nstrips) * strip;
+    const int nr = h - r0 < strip ? h - r0 : strip;
+    int rb, re, cb, ce;
+    dg_strip_rows(r0, strip, h, rb, re);
+    dg_group_columns(group, waves, w, cb, ce);
+    const int cw = ce - cb;
+    const float* src = pred + (size_t)map * h * w;
+    for (int r = rb; r < re; ++r) {
+        const float* g = src + (size_t)r * w + cb;
+        float* l = g_rows + (size_t)(r - rb) * cw;
+        for (int x = tid; x < cw; x += waves * 64) l[x] = g[x];
+    }
+    // this lane's column and the output columns whose left source column it is: [f1, f2), empty for no column
+    const int j = dg_column(group, waves, wave, lane), j1 = j < w - 1 ? j + 1 : j;
+    const bool served = j >= 0 && j < w;
+    const int f1 = served ? dg_first(j, scale_x, w, out_w) : 0, f2 = served ? dg_first(j + 1, scale_x, w, out_w) : 0;
+    const double* fy = fac + (size_t)map * (out_h + out_w);
+    const double* fx = fy + out_h;
+    float* gmap = grad + (size_t)map * h * w;
+    const int ybeg = dg_first(r0 - 1, scale_y, h, out_h), yend = dg_first(r0 + nr, scale_y, h, out_h);
+    double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;          // a0 / b0 belong to the source row cur, a1 / b1 to cur + 1
+    int cur = r0 - 1;
+    __syncthreads();
+    for (int y = ybeg; y <= yend; ++y) {
+        int y0 = r0 + nr, y1 = y0;          // (y == yend: past the strip, the rows still open are flushed)
+        double ly = 0.0, wy0 = 0.0, wy1 = 0.0;
+        if (y < yend) dg_weights(y, scale_y, h, y0, y1, ly, wy0, wy1);
+        for (; cur < y0; ++cur) {
+            const double tot = a0 + __shfl_up(b0, 1, 64);
+            if (cur >= r0 && lane >= 1 && served) gmap[(size_t)cur * w + j] = tot == 0.0 ? 0.0f : (float)(scale * tot);
+            a0 = a1;
+            b0 = b1;
+            a1 = b1 = 0.0;
+        }
+        if (y < yend && f2 > f1) {
+            const float* ra = g_rows + (size_t)(y0 - rb) * cw;
+            const float* rc = g_rows + (size_t)(y1 - rb) * cw;
+            const double gy = fy[y], uy = 1.0 - ly;
+            const double vl = uy * (double)ra[j - cb] + ly * (double)rc[j - cb];
+            const double vr = uy * (double)ra[j1 - cb] + ly * (double)rc[j1 - cb];
+            double ca = 0.0, cr = 0.0;
+            for (int x = f1; x < f2; ++x) {
+                const double lx = dg_lambda(x, scale_x, j), ux = 1.0 - lx;          // dg_src_coord's lambda: its i0 is j by the ranges
+                const double v = ux * vl + lx * vr;
+                const float t = (float)(fx[x] * gy);
+                double r = 2.0 * (v - (double)t);
+                if (weighted && t > 0.1f) r = 100.0 * r;
+                ca = ca + (j1 == j ? ux + lx : ux) * r;          // dg_weights' pair
+                cr = cr + (j1 == j ? 0.0 : lx) * r;
+            }
+            a0 = a0 + wy0 * ca;
+            a1 = a1 + wy1 * ca;
+            b0 = b0 + wy0 * cr;
+            b1 = b1 + wy1 * cr;
+        }
+    }
 }
 
 // _batched_distance_point_to_segment (helper_balldetection.py:335-399): t = 0 on a segment with L^2 <= 1e-12, clamped to [0, 1]
@@ -379,6 +460,51 @@ extern "C" int ttup_detect_heatmap_loss(const float* pred_dev, const double* cen
                        (double)h / (double)out_h, (double)w / (double)out_w, strip, nstrips, weighted ? 1 : 0, partial);
     TTUP_LAUNCH_CHECK();
     hipLaunchKernelGGL(loss_final_kernel, dim3((unsigned)maps), dim3(DE_THREADS), 0, st, (const double*)partial, nstrips, sums_dev);
+    TTUP_LAUNCH_CHECK();
+    return TTUP_OK;
+}
+
+extern "C" size_t ttup_detect_loss_grad_workspace_bytes(int n_maps, int h, int w, int out_h, int out_w) {
+    return h > 0 && w > 0 ? loss_workspace_bytes(n_maps, out_h, out_w) : 0;
+}
+
+extern "C" int ttup_detect_heatmap_loss_grad(const float* pred_dev, const double* centres_dev, const int* has_target_dev, int n, int c, int h, int w, double sigma, int out_h,
+                                             int out_w, int weighted, double scale, void* workspace_dev, size_t workspace_bytes, double* sums_dev, float* grad_dev,
+                                             void* stream) {
+    const char* who = "ttup_detect_heatmap_loss_grad";
+    TTUP_REQUIRE(pred_dev && centres_dev && has_target_dev && workspace_dev && grad_dev, TTUP_EINVAL, "%s: null pointer", who);
+    TTUP_REQUIRE(n > 0 && c > 0, TTUP_EINVAL, "%s: need at least one sample and one channel, got n = %d, c = %d", who, n, c);
+    TTUP_REQUIRE(h > 0 && w > 0 && out_h > 0 && out_w > 0, TTUP_EINVAL, "%s: empty heatmap or output: (%d, %d) -> (%d, %d)", who, h, w, out_h, out_w);
+    TTUP_REQUIRE(sigma > 0.0, TTUP_EINVAL, "%s: sigma must be positive, got %g", who, sigma);
+    TTUP_REQUIRE(isfinite(scale), TTUP_EINVAL, "%s: scale must be finite, got %g", who, scale);
+    const long long maps = (long long)n * c;
+    const GradPlan plan = dg_plan(h, w, out_h, out_w);
+    int strip, slots;
+    loss_plan(h, w, out_h, strip, slots);          // the loss pass's limit holds for the pair, whether the sums are asked for or not
+    TTUP_REQUIRE(strip >= 1, TTUP_EINVAL, "%s: two source rows of %d floats do not fit the %zu bytes of LDS the loss pass keeps them in (w <= %zu)", who, w, DE_ROW_BYTES,
+                 DE_ROW_BYTES / (2 * sizeof(float)));
+    TTUP_REQUIRE(plan.strip >= 1 && plan.waves <= DG_MAX_WAVES && plan.lds <= DG_LDS_BYTES, TTUP_EINVAL, "%s: no plan for (%d, %d) -> (%d, %d)", who, h, w, out_h, out_w);
+    const int nstrips = (out_h + strip - 1) / strip;
+    const int fblocks = (out_h + out_w + DE_THREADS - 1) / DE_THREADS;
+    TTUP_REQUIRE(maps * nstrips <= 0x7fffffffLL && maps * fblocks <= 0x7fffffffLL && maps * plan.nstrips * plan.groups <= 0x7fffffffLL, TTUP_EINVAL, "%s: %lld maps exceed the grid", who, maps);
+    TTUP_REQUIRE(((size_t)workspace_dev & 7) == 0, TTUP_EINVAL, "%s: the workspace must be 8-byte aligned", who);
+    TTUP_REQUIRE(workspace_bytes >= loss_workspace_bytes(maps, out_h, out_w), TTUP_EINVAL, "%s: workspace of %zu bytes, need %zu (ttup_detect_loss_grad_workspace_bytes)", who,
+                 workspace_bytes, loss_workspace_bytes(maps, out_h, out_w));
+    double* fac = (double*)workspace_dev;
+    double* partial = fac + (size_t)maps * (out_h + out_w);
+    const double scale_y = (double)h / (double)out_h, scale_x = (double)w / (double)out_w;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(factor_kernel, dim3((unsigned)(maps * fblocks)), dim3(DE_THREADS), 0, st, centres_dev, has_target_dev, out_h, out_w, fblocks, 2.0 * sigma * sigma, fac);
+    TTUP_LAUNCH_CHECK();
+    if (sums_dev) {          // the loss pass's own launches on the same factors: the sums ttup_detect_heatmap_loss writes
+        hipLaunchKernelGGL(loss_kernel, dim3((unsigned)(maps * nstrips)), dim3(DE_THREADS), (size_t)slots * w * sizeof(float), st, pred_dev, (const double*)fac, h, w, out_h,
+                           out_w, scale_y, scale_x, strip, nstrips, weighted ? 1 : 0, partial);
+        TTUP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(loss_final_kernel, dim3((unsigned)maps), dim3(DE_THREADS), 0, st, (const double*)partial, nstrips, sums_dev);
+        TTUP_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(grad_kernel, dim3((unsigned)(maps * plan.nstrips * plan.groups)), dim3(plan.waves * 64), plan.lds, st, pred_dev, (const double*)fac, h, w, out_h, out_w,
+                       scale_y, scale_x, plan.strip, plan.nstrips, plan.waves, plan.groups, weighted ? 1 : 0, scale, grad_dev);
     TTUP_LAUNCH_CHECK();
     return TTUP_OK;
 }

@@ -6,7 +6,11 @@ pixel tolerances, the average distance, the distance to the motion-blur streak a
 fp32 heatmaps and positions, fp64 arithmetic and sums, a fixed summation tree: two calls return the same bits.  The `*_device`
 functions enqueue on the current stream and return device tensors; the public functions read them back once and finish the ratios
 on the host, with the reference's sentinels: PCK -1 and distances 10000 when no detection is valid, NaN where it divides 0 by 0.
-`BallDetector.val` / `TableDetector.val` (interface.py) run a detector through them.  DESIGN.md section 27."""
+`BallDetector.val` / `TableDetector.val` (interface.py) run a detector through them.  DESIGN.md section 27.
+
+`heatmap_loss_grad` adds the gradient of that loss into the predicted heatmaps -- what the reference's loss.backward() leaves in the
+network's output (balldetection/train.py:112-119, tabledetection/train.py:106-108) -- from the same call as the sums; the detectors'
+`heatmap_loss_grad` methods run a detector through it.  DESIGN.md section 28."""
 import ctypes
 
 import numpy as np
@@ -105,6 +109,45 @@ def heatmap_loss(pred, centres, has_target, sigma=6, weighted=False, size=(HEIGH
     -> {'sums': float64 (N, C), the per-(sample, channel) sums over the output pixels, 'loss': `loss_from_sums` of them}."""
     sums = heatmap_loss_device(pred, centres, has_target, sigma, weighted, size).cpu().numpy()
     return {'sums': sums, 'loss': loss_from_sums(sums, size, batch_size)}
+
+
+def heatmap_loss_grad_device(pred, centres, has_target, sigma=6, weighted=True, size=(HEIGHT, WIDTH), scale=None):
+    """-> (sums (N, C) float64, grad (N, C, h, w) float32), device tensors: `heatmap_loss_device`'s sums, bit for bit, and the gradient
+    of scale * sums.sum() with respect to pred (csrc/detect_eval.hip grad_kernel).  scale=None: 1 / (N C size[0]
+    size[1]), the element mean -- the reference's loss.backward() into the network's output.  Enqueued on the current stream;
+    nothing synchronises."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    dev = _device_of(pred)
+    pred = _to(pred, dev, torch.float32)
+    if pred.dim() != 4:
+        raise ValueError('pred must have shape (N, C, h, w), got %s' % (tuple(pred.shape),))
+    n, c, h, w = pred.shape
+    centres = _to(centres, dev, torch.float64)
+    has_target = _to(has_target, dev, torch.int32)
+    if tuple(centres.shape) != (n, c, 2) or tuple(has_target.shape) != (n, c):
+        raise ValueError('centres must have shape (N, C, 2) and has_target (N, C) for pred %s, got %s and %s'
+                         % (tuple(pred.shape), tuple(centres.shape), tuple(has_target.shape)))
+    out_h, out_w = int(size[0]), int(size[1])
+    if scale is None:
+        scale = 1.0 / (n * c * out_h * out_w)
+    sums = torch.empty((n, c), dtype=torch.float64, device=dev)
+    grad = torch.empty((n, c, h, w), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nbytes = int(lib.ttup_detect_loss_grad_workspace_bytes(n * c, h, w, out_h, out_w))
+        ws = _workspace(nbytes, dev)
+        _lib.check(lib.ttup_detect_heatmap_loss_grad(_lib.ptr(pred), _lib.ptr(centres), _lib.ptr(has_target), n, c, h, w, float(sigma), out_h, out_w,
+                                                     1 if weighted else 0, float(scale), _lib.ptr(ws), nbytes, _lib.ptr(sums), _lib.ptr(grad), _lib.stream_ptr()))
+    return sums, grad
+
+
+def heatmap_loss_grad(pred, centres, has_target, sigma=6, weighted=True, size=(HEIGHT, WIDTH), scale=None):
+    """The detectors' training loss (`weighted_mse_loss` after F.interpolate; weighted=False: nn.MSELoss) and its gradient into pred,
+    without a full-resolution tensor.  Arguments as `heatmap_loss`.  -> (loss: the batch's element mean, what
+    `heatmap_loss(..., batch_size=None)['loss']` returns; grad (N, C, h, w) float32 device tensor: the gradient of scale * the summed
+    squared error, scale=None: of that mean)."""
+    sums, grad = heatmap_loss_grad_device(pred, centres, has_target, sigma, weighted, size, scale)
+    return loss_from_sums(sums.cpu().numpy(), size), grad
 
 
 def ball_metrics_device(pred_pos, gt_pos, gt_min, gt_max, vis, tolerances=(2, 5, 10)):

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib, calib, detect_eval, glue, inference, refine, uplift, vitpose, wasb, weights
-from .detect_eval import ball_val_metrics, heatmap_loss, table_val_metrics  # noqa: F401  (the evaluation functions, beside the detectors they measure)
+from .detect_eval import ball_val_metrics, heatmap_loss, heatmap_loss_grad, heatmap_loss_grad_device, table_val_metrics  # noqa: F401  (the evaluation functions, beside the detectors they measure)
 
 HEIGHT, WIDTH = 1080, 1920
 KEYPOINT_VISIBLE = 1
@@ -253,6 +253,29 @@ class BallDetector(_HubDetector):
         out.update(loss=detect_eval.loss_from_sums(loss_sums, (HEIGHT, WIDTH), batch_size), loss_sums=loss_sums)
         return out
 
+    def heatmap_loss_grad(self, images, ball_coords, vis, sigma=6, size=(HEIGHT, WIDTH), weighted=True):
+        """The reference's ball training loss (balldetection/train.py:112-113: weighted_mse_loss after F.interpolate to `size`;
+        weighted=False: nn.MSELoss) on this detector, and its gradient into the detector's heatmaps -- the seed of a backward pass.
+        images, ball_coords, vis as `val` takes them.  -> (loss: the element mean over the whole batch, grad (B,1,H,W) float32
+        device tensor, shaped like the heatmaps: d loss / d heatmap).  The forward runs in the chunks `val` runs; no heatmap goes
+        to the host."""
+        n = len(images)
+        centres = np.asarray(ball_coords, np.float64).reshape(n, 1, 2)
+        has = (np.asarray(vis).reshape(n) != detect_eval.BALL_INVISIBLE).astype(np.int32).reshape(n, 1)
+        w, h = self.model_resolution
+        scale = 1.0 / (max(n, 1) * int(size[0]) * int(size[1]))
+        sums, grads = [], []
+        for b0 in range(0, n, self.max_batch):
+            b1 = min(n, b0 + self.max_batch)
+            xs = [wasb.preprocess_triples(self._upload(imgs), (w, h)) for imgs in images[b0:b1]]
+            heat = self._certified_forward(torch.cat(xs))[0]
+            s, g = detect_eval.heatmap_loss_grad_device(heat, centres[b0:b1], has[b0:b1], sigma, weighted, size, scale)
+            sums.append(s)
+            grads.append(g)
+        if not sums:
+            raise ValueError('need at least one sample')
+        return detect_eval.loss_from_sums(torch.cat(sums).cpu().numpy(), size), torch.cat(grads)
+
     def predict_clip(self, images):
         """Fast path for consecutive frames (what TableTennisPipeline.predict feeds the detector, interface.py:276-279):
         images = list of N BGR uint8 HWC frames -> pred_pos (N-2, 3), the same values `predict` returns for the triples
@@ -328,6 +351,27 @@ class TableDetector(_HubDetector):
         out = detect_eval.finish_table(msums, counts, [float(t) for t in tolerances])
         out.update(loss=detect_eval.loss_from_sums(loss_sums, (HEIGHT, WIDTH), batch_size), loss_sums=loss_sums)
         return out
+
+    def heatmap_loss_grad(self, images, table_coords, sigma=6, size=(HEIGHT, WIDTH), weighted=True):
+        """The reference's table training loss (tabledetection/train.py:106-107) on this detector and its gradient into the
+        detector's heatmaps; images and table_coords as `val` takes them.  -> (loss, grad (B,13,H,W) float32 device tensor).  Runs
+        like `BallDetector.heatmap_loss_grad`; the target of a keypoint whose visibility is not KEYPOINT_VISIBLE is zeros."""
+        n = len(images)
+        coords = np.asarray(table_coords, np.float64).reshape(n, 13, 3)
+        centres = np.ascontiguousarray(coords[:, :, :2])
+        has = (coords[:, :, 2] == KEYPOINT_VISIBLE).astype(np.int32)
+        scale = 1.0 / (max(n, 1) * 13 * int(size[0]) * int(size[1]))
+        sums, grads = [], []
+        for b0 in range(0, n, self.max_batch):
+            b1 = min(n, b0 + self.max_batch)
+            fr = self._upload(images[b0:b1])
+            heat = self._certified_forward(wasb.preprocess_frames(fr, self.model_resolution))[0]
+            s, g = detect_eval.heatmap_loss_grad_device(heat, centres[b0:b1], has[b0:b1], sigma, weighted, size, scale)
+            sums.append(s)
+            grads.append(g)
+        if not sums:
+            raise ValueError('need at least one sample')
+        return detect_eval.loss_from_sums(torch.cat(sums).cpu().numpy(), size), torch.cat(grads)
 
     def predict_keypoints(self, images):
         """`predict` without the heatmaps: (B,13,3) keypoints only.  Pre-processing, CNN, per-channel argmax and windows run

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib, weights
-from .detect_eval import ball_val_metrics, heatmap_loss, table_val_metrics  # noqa: F401  (how good the detectors' heatmaps and positions are)
+from .detect_eval import ball_val_metrics, heatmap_loss, heatmap_loss_grad, heatmap_loss_grad_device, table_val_metrics  # noqa: F401  (how good the detectors' heatmaps and positions are)
 
 RESOLUTIONS = {'wasb': (1280, 704)}     # balldetection/config.py:84-85 (width, height)
 
