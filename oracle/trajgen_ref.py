@@ -8,7 +8,9 @@ What is pinned and what is not
   * `init_state`            bit-for-bit against the reference's `_init_simulation` (run here with a stand-in `mujoco`
                             module that only provides the MjModel/MjData containers) -- tests/golden/trajgen.npz
   * `count_hits`, `select`  against the reference's `_count_hits` / `find_valid_trajectories_worker` control flow, driven
-                            by THIS file's integrator through the same stand-in -- tests/golden/trajgen.npz
+                            by THIS file's integrator through the same stand-in -- tests/golden/trajgen.npz; `count_hits`
+                            also on crafted tracks at every mask threshold and interval shape (tests/helpers/
+                            trajgen_edge_cases.py) -- tests/golden/trajgen_edges.npz
   * `simulate` (the physics)  **parity unpinned**: the arithmetic lives in MuJoCo 3.3.2 (`mujoco.mj_step`,
                             requirements_full.txt:5), which is not importable here and which no reference test exercises.
                             Restated from MuJoCo's published model for this scene:
@@ -252,32 +254,70 @@ def is_oob(p, mode, direction):
     return bool(correct_side and (abs(p[0]) > ox or abs(p[1]) > oy))
 
 
-def simulate(seeds, mode, direction, substeps=SUBSTEPS):
+STOP_REASONS = ['oob_x', 'oob_y', 'oob_z', 'image', 'full']
+
+
+def stop_margins(p, img, mode, direction):
+    """How far one sample is from changing the sampling loop's decision: (reason or None, metres, pixels).
+    The position rule is `side and (|x| > ox or |y| > oy or z < oz)`: with s the depth into the side that is tested (inf
+    where the mode tests none) and e the largest excess over a bound, it fires iff min(s, e) > 0, and |min(s, e)| is the
+    distance to the threshold that decides.  The image rule keeps 0 <= u < W, 0 <= v < H: |min(u, W - u, v, H - v)|.
+    The position rule is evaluated first, so a sample it stops has no pixel margin (inf)."""
+    ox, oy, oz = OOB[mode]
+    excess = [abs(p[0]) - ox, abs(p[1]) - oy, oz - p[2] if mode in ('final_win', 'intermediate', 'first_short') else -np.inf]
+    sided = mode not in ('final_lose', 'first_short')
+    s = (-p[0] if direction == 'left_to_right' else p[0]) if sided else np.inf
+    g = min(s, max(excess))
+    q = min(img[0], WIDTH - img[0], img[1], HEIGHT - img[1])
+    if is_oob(p, mode, direction):
+        return STOP_REASONS[[e > 0 for e in excess].index(True)], abs(g), np.inf
+    if not (0 <= img[0] < WIDTH and 0 <= img[1] < HEIGHT):
+        return 'image', abs(g), abs(q)
+    return None, abs(g), abs(q)
+
+
+def simulate(seeds, mode, direction, substeps=SUBSTEPS, camera=None, want_stop=False):
     """Sampling loop for a batch of seeds.  Returns pos, vel, rot (N, S, 3) and n_saved (N,): sample 0 is the state after
     the first 1 ms step (labelled t=0), sample k the state at 2k ms; a trajectory stops at the first out-of-bounds or
-    out-of-image sample (mujocosimulation.py:112-151)."""
+    out-of-image sample (mujocosimulation.py:112-151).  `camera`: (Mext, Mint) instead of `camera_matrices()`.
+    With `want_stop` two more values: per seed the stop reason (STOP_REASONS; 'full' = all labels saved) and margins
+    (N, 3, 2) from `stop_margins` -- [deciding sample (the last one for 'full'), the sample before it, the smallest over
+    all samples before those] x [metres, pixels], inf where there is no such sample or rule."""
     times = save_times()
     n = len(seeds)
     st = [init_state(s, mode, direction) for s in seeds]
     r = np.stack([s[0] for s in st]); v = np.stack([s[1] for s in st]); w = np.stack([s[2] for s in st])
-    ex, mint = camera_matrices()
+    ex, mint = camera_matrices() if camera is None else camera
     S = len(times)
     pos = np.zeros((n, S, 3)); vel = np.zeros((n, S, 3)); rot = np.zeros((n, S, 3))
     n_saved = np.zeros(n, dtype=np.int64)
     alive = np.ones(n, dtype=bool)
+    reasons = ['full'] * n
+    margins = np.full((n, 3, 2), np.inf)
     r, v, w = step_ms(r, v, w, 1, substeps)
     for k in range(S):
         if k > 0:
             r, v, w = step_ms(r, v, w, 1 if k == 1 else 2, substeps)
         img = project(r, ex, mint)
         for i in np.nonzero(alive)[0]:
-            if is_oob(r[i], mode, direction) or not (0 <= img[i, 0] < WIDTH and 0 <= img[i, 1] < HEIGHT):
+            stop = is_oob(r[i], mode, direction) or not (0 <= img[i, 0] < WIDTH and 0 <= img[i, 1] < HEIGHT)
+            if want_stop:
+                why, m, px = stop_margins(r[i], img[i], mode, direction)
+                assert (why is not None) == bool(stop)
+                margins[i, 2] = np.minimum(margins[i, 2], margins[i, 1])
+                margins[i, 1] = margins[i, 0]
+                margins[i, 0] = (m, px)
+                if stop:
+                    reasons[i] = why
+            if stop:
                 alive[i] = False
                 continue
             pos[i, k], vel[i, k], rot[i, k] = r[i], v[i], w[i]
             n_saved[i] = k + 1
         if not alive.any():
             break
+    if want_stop:
+        return pos, vel, rot, n_saved, reasons, margins
     return pos, vel, rot, n_saved
 
 
@@ -309,59 +349,66 @@ def count_hits(positions, direction):
     return out[0], out[1], out[2]
 
 
-def select(positions, times, mode, direction):
-    """Everything after the sampling loop for one trajectory: returns None (rejected) or (n_keep, bounces)."""
+def select(positions, times, mode, direction, why=None):
+    """Everything after the sampling loop for one trajectory: returns None (rejected) or (n_keep, bounces).
+    `why`: a list that receives two labels, the rule that decided ('too_short', 'too_high', 'cut_too_short', 'net',
+    'last_side', 'counts', 'accepted') and the cut branch taken ('none', 'ground', 'opponent_extra', 'own_extra',
+    'opponent_first'; 'none' where the trajectory is rejected before the cut rules)."""
+    def done(label, branch, result):
+        if why is not None:
+            why.extend([label, branch])
+        return result
     positions = np.asarray(positions)
     times = np.asarray(times)[:len(positions)]
     if len(positions) < MIN_TRAJ_LEN_FRAMES:
-        return None
+        return done('too_short', 'none', None)
     ho, hw, hg = count_hits(positions, direction)
     if np.max(positions[:, 2]) > (1.4 if 'first' in mode else 1.8):
-        return None
+        return done('too_high', 'none', None)
     tmin = MIN_TRAJ_CUT_TIME_RATIO * MAX_SIMULATION_TIME
-    cut = -1
+    cut, branch = -1, 'none'
 
     def idx(t):
         return int(np.sum(times < t)) - 1
     if mode in ('final_lose', 'intermediate', 'first_long'):
         if len(hg) > 0 and hg[0] >= tmin:
-            cut = idx(hg[0]); hg = []
+            cut = idx(hg[0]); hg = []; branch = 'ground'
     elif mode == 'final_win':
         if len(ho) > 2 and ho[2] >= tmin:
-            cut = idx(ho[2]); ho = ho[:2]
+            cut = idx(ho[2]); ho = ho[:2]; branch = 'opponent_extra'
         elif len(hg) > 0 and hg[0] >= tmin:
-            cut = idx(hg[0])
+            cut = idx(hg[0]); branch = 'ground'
         if cut != -1:
             hg = []
     elif mode == 'first_good':
         if len(ho) > 1 and ho[1] >= tmin:
-            cut = idx(ho[1]); ho = ho[:1]
+            cut = idx(ho[1]); ho = ho[:1]; branch = 'opponent_extra'
         elif len(hg) > 0 and hg[0] >= tmin:
-            cut = idx(hg[0])
+            cut = idx(hg[0]); branch = 'ground'
         if cut != -1:
             hg = []
     elif mode == 'first_short':
         if len(hw) > 2 and hw[2] >= tmin:
-            cut = idx(hw[2]); hw, ho, hg = hw[:2], [], []
+            cut = idx(hw[2]); hw, ho, hg = hw[:2], [], []; branch = 'own_extra'
         elif len(ho) > 0 and ho[0] >= tmin:
-            cut = idx(ho[0]); ho, hg = [], []
+            cut = idx(ho[0]); ho, hg = [], []; branch = 'opponent_first'
         elif len(hg) > 0 and hg[0] >= tmin:
-            cut = idx(hg[0]); hg = []
+            cut = idx(hg[0]); hg = []; branch = 'ground'
     if cut != -1:
         positions = positions[:cut]
     if len(positions) < MIN_TRAJ_LEN_FRAMES:
-        return None
+        return done('cut_too_short', branch, None)
     close = np.abs(positions[:, 0]) < NET_CLEARANCE_X_MARGIN
     if np.any(close):
         if np.max(positions[close, 2]) < NET_TOTAL_HEIGHT and np.min(np.abs(positions[close, 1])) < NET_TOTAL_WIDTH / 2:
-            return None
+            return done('net', branch, None)
     last_x = positions[-1][0]
     opposite = last_x < 0 if direction == 'left_to_right' else last_x > 0
     if mode in ('final_lose', 'first_long') and not opposite:
-        return None
+        return done('last_side', branch, None)
     if (len(ho), len(hw), len(hg)) != VALID_COUNTS[mode]:
-        return None
-    return len(positions), np.array(sorted(ho + hw))
+        return done('counts', branch, None)
+    return done('accepted', branch, (len(positions), np.array(sorted(ho + hw))))
 
 
 def seed_order(current_seed, batch_size, num_processes):

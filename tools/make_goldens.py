@@ -597,6 +597,41 @@ def gen_trajgen():
 
 
 
+def gen_trajgen_edges():
+    """f2 at its edges (tests/helpers/trajgen_edge_cases.py): the reference's `_count_hits` on every named crafted track -- the
+    three hit lists only, the tracks are rebuilt from the helper -- and, for the fixed seed lists of the stop-rule tests, what
+    the ORACLE's sampling loop gives (sample counts, stop reasons, margins; not reference-derived, recorded to spare the GPU
+    suite a minute of numpy integration)."""
+    from oracle import trajgen_ref as T
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    from helpers import trajgen_edge_cases as C
+    install_mujoco_standin({})
+    import syntheticdataset.helper as mh
+    out = {}
+    cases = C.all_named_cases()
+    out['names'] = np.array([c['name'] for c in cases])
+    for j, key in enumerate(('opponent', 'own', 'ground')):
+        lists = [mh._count_hits(list(C.track(c)), c['direction'])[j] for c in cases]
+        out['hits/%s/n' % key] = np.array([len(h) for h in lists], dtype=np.int64)
+        out['hits/%s/t' % key] = np.array([t for h in lists for t in h], dtype=np.float64)
+    for mode in T.MODES:
+        for direction in T.DIRECTIONS:
+            seeds = C.stop_seeds(mode, direction)
+            _, _, _, ns, why, margins = T.simulate(seeds, mode, direction, want_stop=True)
+            key = 'stop/%s/%s' % (mode, direction)
+            out[key + '/seeds'] = np.array(seeds, dtype=np.int64)
+            out[key + '/n_saved'] = ns
+            out[key + '/reason'] = np.array([T.STOP_REASONS.index(w) for w in why], dtype=np.int64)
+            out[key + '/margins'] = margins
+            print('trajgen edges %s/%s: %s' % (mode, direction, {w: why.count(w) for w in T.STOP_REASONS}))
+    mode, direction = C.CAMERA_COMBO                  # the same seeds seen by a camera whose principal point is moved
+    _, _, _, ns, why, margins = T.simulate(C.stop_seeds(mode, direction), mode, direction, camera=C.shifted_camera(), want_stop=True)
+    out['stop_camera/n_saved'], out['stop_camera/margins'] = ns, margins
+    out['stop_camera/reason'] = np.array([T.STOP_REASONS.index(w) for w in why], dtype=np.int64)
+    np.savez_compressed(os.path.join(OUT, 'trajgen_edges.npz'), **out)
+    print('trajgen_edges.npz: %d named cases, %.0f KB' % (len(cases), os.path.getsize(os.path.join(OUT, 'trajgen_edges.npz')) / 1024))
+
+
 def ref_table_hrnet(sd_np, resolution):
     from tabledetection.models.hrnet import MyHRNet
     orig = torch.load
@@ -777,6 +812,6 @@ if __name__ == '__main__':
     os.makedirs(OUT, exist_ok=True)
     install_stubs()
     torch.manual_seed(0)
-    which = sys.argv[1:] or ['wasb', 'refine', 'uplift', 'glue', 'full', 'table', 'trajgen', 'calib', 'e2e', 'hard', 'hard_table']
+    which = sys.argv[1:] or ['wasb', 'refine', 'uplift', 'glue', 'full', 'table', 'trajgen', 'trajgen_edges', 'calib', 'e2e', 'hard', 'hard_table']
     for w_ in which:
-        {'wasb': gen_wasb, 'refine': gen_refine, 'uplift': gen_uplift, 'glue': gen_glue, 'full': gen_fullsize, 'table': gen_table, 'trajgen': gen_trajgen, 'calib': gen_calib, 'calib64': gen_calib64, 'e2e': gen_e2e, 'hard': gen_hard, 'hard_table': gen_hard_table}[w_]()
+        {'wasb': gen_wasb, 'refine': gen_refine, 'uplift': gen_uplift, 'glue': gen_glue, 'full': gen_fullsize, 'table': gen_table, 'trajgen': gen_trajgen, 'trajgen_edges': gen_trajgen_edges, 'calib': gen_calib, 'calib64': gen_calib64, 'e2e': gen_e2e, 'hard': gen_hard, 'hard_table': gen_hard_table}[w_]()
