@@ -247,6 +247,49 @@ int  ttup_vitpose_forward_frames(ttup_vitpose* net, const uint8_t* frames_dev, i
  * size, or a forward since the stage: TTUP_EINVAL. */
 int  ttup_vitpose_run_stage(ttup_vitpose* net, int stage, const float* in_dev, int batch, void* stream);
 int  ttup_vitpose_read_tap(ttup_vitpose* net, const char* tap, void* dst, size_t bytes);
+/* The backbone alone: x_dev (batch,in_ch,H,W) float32 -> out_dev (batch*tokens,384) float32, last_norm's output (what the head's
+ * deconvolutions read; bit-equal to the "ln" tap of stage 13 on the residual stream the blocks leave), in micro-batches, any batch >= 0.
+ * An f32 handle only: a bf16 handle is TTUP_EINVAL. */
+int  ttup_vitpose_features(ttup_vitpose* net, const float* x_dev, int batch, float* out_dev, void* stream);
+
+/* ---------------------------------------------------------------- ViTPose head: training-mode forward and backward
+ * The keypoint head (two ConvTranspose2d(k4,s2,p1,no bias) + BatchNorm2d(eps 1e-5, momentum 0.1) + ReLU, a 1x1 conv) with BN kept
+ * apart from the weights, and its backward.  Parameters stay where the caller keeps them, in the reference's layouts (all device
+ * pointers, float32; num_batches_tracked int64): the handle packs what its kernels read on every forward.  The handle owns one
+ * workspace (ttup_vitpose_head_workspace_bytes) sized for max_rows tokens (batch * hp * wp) and out_ch in 1..16, and keeps the
+ * activations of the last forward for the backward.
+ * forward: feat_dev (batch*hp*wp, 384) token-major (sample, row, column), 16-byte aligned -> heat_dev (batch,out_ch,4hp,4wp).
+ *   train != 0: BN takes the batch's mean and biased variance over (batch, H, W) and updates running_mean / running_var (the
+ *   unbiased variance) / num_batches_tracked in place; train == 0: BN reads the running statistics and updates nothing.
+ * backward: dheat_dev (batch,out_ch,4hp,4wp), the batch and grid of the last forward -> every gradient of ttup_vitpose_head_grads
+ *   (overwritten, the reference's shapes; feat (batch*hp*wp, 384), 16-byte aligned), through BN in the mode the forward ran in.
+ *   It may run more than once per forward.  Same inputs, same bits: no sum is atomic.
+ * read_tap (testing seam): "z1", "a1" (batch,2hp,2wp,256) and "z2", "a2" (batch,4hp,4wp,256) NHWC, "mean1", "var1", "mean2", "var2"
+ *   (256: the statistics the BN used) of the last forward, to dst (host or device, exactly `bytes` long).
+ * TTUP_EINVAL before any device call: null pointers, out_ch outside 1..16, max_rows outside 1..2^22, a non-positive batch or grid,
+ * more rows than max_rows, a backward without a forward or with another batch or grid than the forward's, an unknown tap or a
+ * wrong size. */
+typedef struct ttup_vitpose_head ttup_vitpose_head;
+typedef struct ttup_vitpose_head_params {
+    const float *deconv1_weight, *bn1_weight, *bn1_bias;          /* (384,256,4,4), (256), (256) */
+    float *bn1_running_mean, *bn1_running_var;                    /* (256) each */
+    int64_t* bn1_num_batches_tracked;                             /* (1) */
+    const float *deconv2_weight, *bn2_weight, *bn2_bias;          /* (256,256,4,4), (256), (256) */
+    float *bn2_running_mean, *bn2_running_var;
+    int64_t* bn2_num_batches_tracked;
+    const float *final_weight, *final_bias;                       /* (out_ch,256,1,1), (out_ch) */
+} ttup_vitpose_head_params;
+typedef struct ttup_vitpose_head_grads {
+    float *deconv1_weight, *bn1_weight, *bn1_bias, *deconv2_weight, *bn2_weight, *bn2_bias, *final_weight, *final_bias, *feat;
+} ttup_vitpose_head_grads;
+size_t ttup_vitpose_head_workspace_bytes(int out_ch, long long max_rows);          /* 0: refused arguments */
+int  ttup_vitpose_head_create(int out_ch, long long max_rows, ttup_vitpose_head** out);
+void ttup_vitpose_head_destroy(ttup_vitpose_head* head);
+int  ttup_vitpose_head_forward(ttup_vitpose_head* head, const float* feat_dev, int batch, int hp, int wp, const ttup_vitpose_head_params* params,
+                               int train, float* heat_dev, void* stream);
+int  ttup_vitpose_head_backward(ttup_vitpose_head* head, const float* dheat_dev, int batch, int hp, int wp, const ttup_vitpose_head_grads* grads,
+                                void* stream);
+int  ttup_vitpose_head_read_tap(ttup_vitpose_head* head, const char* tap, void* dst, size_t bytes);
 
 /* ---------------------------------------------------------------- a3/a4: heatmap argmax + refine
  * Replaces extract_position_torch_gaussian (ball: helper_balldetection.py:29-110, called at

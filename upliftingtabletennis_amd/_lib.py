@@ -102,6 +102,13 @@ SIGNATURES = {
     'ttup_vitpose_forward_frames': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'ttup_vitpose_run_stage': (_i, [_vp, _i, _vp, _i, _vp]),
     'ttup_vitpose_read_tap': (_i, [_vp, _c.c_char_p, _vp, _sz]),
+    'ttup_vitpose_features': (_i, [_vp, _vp, _i, _vp, _vp]),
+    'ttup_vitpose_head_workspace_bytes': (_sz, [_i, _c.c_longlong]),
+    'ttup_vitpose_head_create': (_i, [_i, _c.c_longlong, _c.POINTER(_vp)]),
+    'ttup_vitpose_head_destroy': (None, [_vp]),
+    'ttup_vitpose_head_forward': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'ttup_vitpose_head_backward': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    'ttup_vitpose_head_read_tap': (_i, [_vp, _c.c_char_p, _vp, _sz]),
     'ttup_dataset_workspace_bytes': (_sz, [_i]),
     'ttup_dataset_seed': (_i, [_vp, _i, _vp, _sz, _vp]),
     'ttup_dataset_draws': (_i, [_vp, _sz, _i, _i, _i, _vp, _vp]),

@@ -1,5 +1,6 @@
 // The fp32 GEMM on the matrix pipe (v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accumulation) shared by the ViTPose detector
-// (csrc/vitpose.hip, which describes the tile and its A modes) and the uplift transformer's training pass (csrc/uplift_grad.hip).
+// (csrc/vitpose.hip, which describes the tile and its A modes), the uplift transformer's training pass (csrc/uplift_grad.hip) and the
+// ViTPose head's (csrc/vitpose_head_grad.hip: the A_DGRAD / O_DGRAD gather of a transposed convolution's backward, gemm_modes.h).
 #pragma once
 #include "common.h"
 #include "gemm_modes.h"
@@ -15,10 +16,11 @@ constexpr int LDS_STRIDE = BK + 4;          // BM, BN, BK, the A modes and the e
 // columns (the row index contiguous: a transposed operand), leading dimensions of their own; the k range cut into slices of `kslice`
 // (grid z), slice z writing its own partial product at out + z * M * ldo -- summed afterwards in slice order, so a reduction over
 // tens of thousands of rows has a fixed tree and needs no atomics.
-enum { O_ROWS = 0, O_COLS = 1 };
+enum { O_ROWS = 0, O_COLS = 1, O_DGRAD = 2 };          // O_DGRAD (w only): the gather of gemm_modes.h's dgrad_index, read by columns
 
 struct GemmArgs {
-    const float* a;          // A_DENSE / A_LN: (M, K) row-major; A_PATCH: NCHW input; A_DECONV: NHWC input; A_PATCH_FRAMES: (n, 3, H, W)
+    const float* a;          // A_DENSE / A_LN: (M, K) row-major; A_PATCH: NCHW input; A_DECONV: NHWC input; A_PATCH_FRAMES: (n, 3, H, W);
+                             // A_DGRAD: the NHWC (2ih, 2iw, cin) gradient the rows gather from
     const float* w;          // (N, K)
     const float* bias;       // (N)
     const float* ln_g;       // A_LN: (K) gain, bias
@@ -28,7 +30,8 @@ struct GemmArgs {
     const float* pos;        // E_POS: (N_tok + 1, N)
     float* out;
     int M, N, K;
-    int cin, ih, iw;         // A_PATCH: input channels and size; A_DECONV: input channels and (phase) grid h x w
+    int cin, ih, iw;         // A_PATCH: input channels and size; A_DECONV: input channels and (phase) grid h x w; A_DGRAD / O_DGRAD:
+                             // channels of the gathered gradient and the grid h x w of the rows
     int ntok;                // tokens per sample (E_POS)
     int py, px;              // A_DECONV: output phase
     int flags;
@@ -92,9 +95,12 @@ __device__ __forceinline__ f32x4 load_a4(const GemmArgs& p, int m, int k) {
         if (x >= 0 && x < p.iw) { const float2 u = *(const float2*)(r + x); z.x = u.x; z.y = u.y; }
         if (x + 2 >= 0 && x + 2 < p.iw) { const float2 u = *(const float2*)(r + x + 2); z.z = u.x; z.w = u.y; }
         return z;
-    } else {
+    } else if (AM == A_DECONV) {
         size_t e;
         return deconv_in(p, m, k, &e) ? *(const f32x4*)(p.a + e) : z;
+    } else {
+        const long long e = dgrad_index(m, k, p.ih, p.iw, p.cin);          // a quad stays inside one tap's run of cin (cin multiple of 4)
+        return e >= 0 ? *(const f32x4*)(p.a + e) : z;
     }
 }
 
@@ -123,6 +129,15 @@ __device__ __forceinline__ f32x4 load_c4(const float* __restrict__ a, int ld, in
     return z;
 }
 
+// GUARD form, w = the O_DGRAD gather read by columns: columns n .. n+3 (one tap, four consecutive channels: N and cin multiples of 4)
+// of row k
+__device__ __forceinline__ f32x4 load_d4(const GemmArgs& p, int n, int k, int kend) {
+    f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    if (k >= kend || n >= p.N) return z;
+    const long long e = dgrad_index(k, n, p.ih, p.iw, p.cin);
+    return e >= 0 ? *(const f32x4*)(p.w + e) : z;
+}
+
 template <int AM, bool GUARD = false, int WM = O_ROWS>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     __shared__ float sa[BM * LDS_STRIDE];
@@ -147,7 +162,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
         for (int h = 0; h < 2; ++h) {
             if (GUARD) {
                 ra[h] = AM == O_ROWS ? load_g4(p.a, p.lda, m0 + lrow + 32 * h, p.M, k0 + lq, kend) : load_c4(p.a, p.lda, m0 + crow, p.M, k0 + ck + 16 * h, kend);
-                rw[h] = WM == O_ROWS ? load_g4(p.w, p.ldw, n0 + lrow + 32 * h, p.N, k0 + lq, kend) : load_c4(p.w, p.ldw, n0 + crow, p.N, k0 + ck + 16 * h, kend);
+                rw[h] = WM == O_ROWS ? load_g4(p.w, p.ldw, n0 + lrow + 32 * h, p.N, k0 + lq, kend)
+                      : WM == O_COLS ? load_c4(p.w, p.ldw, n0 + crow, p.N, k0 + ck + 16 * h, kend) : load_d4(p, n0 + crow, k0 + ck + 16 * h, kend);
             } else {
                 ra[h] = load_a4<AM>(p, m0 + lrow + 32 * h, k0 + lq);
                 rw[h] = *(const f32x4*)(p.w + (size_t)(n0 + lrow + 32 * h) * p.K + k0 + lq);
@@ -162,7 +178,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) sa[(crow + e) * LDS_STRIDE + ck + 16 * h] = ra[h][e];
             } else *(f32x4*)(sa + (lrow + 32 * h) * LDS_STRIDE + lq) = ra[h];
-            if (GUARD && WM == O_COLS) {
+            if (GUARD && WM != O_ROWS) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) sw[(crow + e) * LDS_STRIDE + ck + 16 * h] = rw[h][e];
             } else *(f32x4*)(sw + (lrow + 32 * h) * LDS_STRIDE + lq) = rw[h];

@@ -304,6 +304,27 @@ extern "C" int ttup_vitpose_forward(ttup_vitpose* net, const float* x_dev, int b
     return TTUP_OK;
 }
 
+// The backbone alone: the patch embedding, the blocks and last_norm per micro-batch -> out (batch * tokens, DIM), what run_head's
+// deconvolutions read (the same launches, so the same bits as the "ln" tap)
+extern "C" int ttup_vitpose_features(ttup_vitpose* net, const float* x_dev, int batch, float* out_dev, void* stream) {
+    TTUP_REQUIRE(net && x_dev && out_dev, TTUP_EINVAL, "ttup_vitpose_features: null argument");
+    TTUP_REQUIRE(net->dtype == 0, TTUP_EINVAL, "ttup_vitpose_features: a bf16 handle keeps last_norm's output in bf16; use an f32 handle");
+    TTUP_REQUIRE(batch >= 0, TTUP_EINVAL, "ttup_vitpose_features: negative batch %d", batch);
+    TTUP_REQUIRE(((uintptr_t)x_dev & 15) == 0, TTUP_EINVAL, "ttup_vitpose_features: input must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t in_per = (size_t)net->in_ch * net->H * net->W, out_per = (size_t)net->ntok * DIM;
+    for (int b0 = 0; b0 < batch; b0 += net->micro) {
+        const int nb = batch - b0 < net->micro ? batch - b0 : net->micro;
+        net->tap_stage = -1;
+        VP_RC(run_patch(net, x_dev + b0 * in_per, nb, st, false));
+        for (int i = 0; i < DEPTH; ++i) VP_RC(run_block(net, i, nb, st));
+        VP_RC(launch_ln_stats(net, nb * net->ntok, st));
+        VP_RC(launch_ln_apply(net, gemm_args(net, G_LAST_NORM, nb, 0, 0, ln_args(net, net->blob.lnw, net->blob.lnb)), st));
+        TTUP_HIP_CHECK(hipMemcpyAsync(out_dev + b0 * out_per, net->buf(GEMMS[G_LAST_NORM].out), nb * out_per * 4, hipMemcpyDeviceToDevice, st));
+    }
+    return TTUP_OK;
+}
+
 // n_frames BGR uint8 HWC frames (device, any size) -> the outputs of ttup_vitpose_forward on ttup_preprocess_triples (in_ch 9) or
 // ttup_preprocess_frames (in_ch 3) of them, bit for bit: each micro-batch's frames are pre-processed once into fp32 records (the
 // same launch_preprocess) and the patch embedding gathers its triples from them.

@@ -20,7 +20,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, calib, detect_eval, glue, inference, refine, uplift, vitpose, wasb, weights
+from . import _lib, calib, detect_eval, glue, inference, refine, uplift, vitpose, vitpose_head, wasb, weights
 from .detect_eval import ball_val_metrics, heatmap_loss, heatmap_loss_grad, heatmap_loss_grad_device, table_val_metrics  # noqa: F401  (the evaluation functions, beside the detectors they measure)
 
 HEIGHT, WIDTH = 1080, 1920
@@ -117,6 +117,10 @@ class _HubDetector:
         self.model, self.model_resolution, self.max_batch = model, res, max_batch
         off = not self.CERTIFIES or model.dtype != 'bf16' or any(os.environ.get(k) == '1' for k in self.NO_CERTIFY_ENV)
         self.cert = None if off else wasb.EpsAudit(model, every=0 if os.environ.get('TTUP_NO_AUDIT') == '1' else 256, seed=0)
+
+    def _head_pass_check(self):
+        """`head_loss_and_grad` exists for the ViTPose detectors alone (their head is the one whose backward is built)"""
+        raise NotImplementedError('head_loss_and_grad: only the ViTPose detectors have a head backward (DESIGN.md section 29)')
 
     @property
     def AUDIT_EVERY(self):
@@ -276,6 +280,21 @@ class BallDetector(_HubDetector):
             raise ValueError('need at least one sample')
         return detect_eval.loss_from_sums(torch.cat(sums).cpu().numpy(), size), torch.cat(grads)
 
+    def head_loss_and_grad(self, images, ball_coords, vis, sigma=6, size=(HEIGHT, WIDTH), weighted=True, train=True):
+        """`heatmap_loss_grad` carried on through the keypoint head: the backbone's features, the head's
+        training-mode forward with the whole batch in one BatchNorm (train=False: the running statistics), the loss's gradient
+        into the heatmaps and the head's backward.  -> (loss, {reference key: gradient} of the head's eight parameters, dfeat
+        (B * tokens, 384): the gradient into last_norm's output).  Works on a copy of the detector's head parameters: the
+        detector itself is unchanged.  ViTPose / f32 only."""
+        self._head_pass_check()
+        n = len(images)
+        centres = np.asarray(ball_coords, np.float64).reshape(n, 1, 2)
+        has = (np.asarray(vis).reshape(n) != detect_eval.BALL_INVISIBLE).astype(np.int32).reshape(n, 1)
+        if not n:
+            raise ValueError('need at least one sample')
+        x = torch.cat([wasb.preprocess_triples(self._upload(imgs), self.model_resolution) for imgs in images])
+        return self._head_pass(x, centres, has, sigma, size, weighted, 1.0 / (n * int(size[0]) * int(size[1])), train)
+
     def predict_clip(self, images):
         """Fast path for consecutive frames (what TableTennisPipeline.predict feeds the detector, interface.py:276-279):
         images = list of N BGR uint8 HWC frames -> pred_pos (N-2, 3), the same values `predict` returns for the triples
@@ -373,6 +392,19 @@ class TableDetector(_HubDetector):
             raise ValueError('need at least one sample')
         return detect_eval.loss_from_sums(torch.cat(sums).cpu().numpy(), size), torch.cat(grads)
 
+    def head_loss_and_grad(self, images, table_coords, sigma=6, size=(HEIGHT, WIDTH), weighted=True, train=True):
+        """`heatmap_loss_grad` carried on through the keypoint head, like `BallDetector.head_loss_and_grad`.  -> (loss, grads,
+        dfeat).  ViTPose / f32 only."""
+        self._head_pass_check()
+        n = len(images)
+        coords = np.asarray(table_coords, np.float64).reshape(n, 13, 3)
+        centres = np.ascontiguousarray(coords[:, :, :2])
+        has = (coords[:, :, 2] == KEYPOINT_VISIBLE).astype(np.int32)
+        if not n:
+            raise ValueError('need at least one sample')
+        x = wasb.preprocess_frames(self._upload(images), self.model_resolution)
+        return self._head_pass(x, centres, has, sigma, size, weighted, 1.0 / (n * 13 * int(size[0]) * int(size[1])), train)
+
     def predict_keypoints(self, images):
         """`predict` without the heatmaps: (B,13,3) keypoints only.  Pre-processing, CNN, per-channel argmax and windows run
         fused on the device; nothing but the 39 numbers per frame comes back to the host."""
@@ -404,6 +436,25 @@ class _ViTPoseHooks:
     def _certified_forward(self, x):
         return self.model.forward(x, want_heatmap=True, want_peaks=True)
 
+    def _keep_head(self, state_dict):
+        """The head's parameters in the reference's layout, for `head_loss_and_grad` (the handle itself holds them BN-folded)"""
+        self._head_state = {k: np.array(weights._np(v)) for k, v in state_dict.items() if '.keypoint_head.' in k}
+
+    def _head_pass_check(self):
+        if self.model.dtype != 'f32':
+            raise ValueError("head_loss_and_grad needs dtype='f32': a %s handle keeps last_norm's output in %s" % (self.model.dtype, self.model.dtype))
+
+    def _head_pass(self, x, centres, has, sigma, size, weighted, scale, train):
+        """features -> the head's training forward (one BN over the whole batch) -> the loss's gradient -> the head's backward, on a
+        head of its own per call: a copy of the parameters and a workspace sized for this batch, freed with it"""
+        net = self.model
+        feat = net.features(x)
+        head = vitpose_head.ViTPoseHead(self._head_state, net.OUT_CH, max_rows=feat.shape[0], device=net.device)
+        heat = head.forward(feat, (net.H // 16, net.W // 16), train=train)
+        sums, grad = detect_eval.heatmap_loss_grad_device(heat, centres, has, sigma, weighted, size, scale)
+        grads, dfeat = head.backward(grad)
+        return detect_eval.loss_from_sums(sums.cpu().numpy(), size), grads, dfeat
+
 
 class ViTPoseBallDetector(_ViTPoseHooks, BallDetector):
     """BallDetector('vitpose'): the reference's ViTPose-small ball detector (balldetection/models/vitpose.py, in_frames 3,
@@ -413,6 +464,7 @@ class ViTPoseBallDetector(_ViTPoseHooks, BallDetector):
         _lib.require_gpu()
         sd, res, in_frames = _load_ball_checkpoint(model_name)
         self._init_hub(vitpose.ViTPoseNet(sd, in_ch=3 * in_frames, out_ch=1, resolution=res, max_batch=max_batch, dtype=dtype), res, max_batch)
+        self._keep_head(sd)
 
 
 class ViTPoseTableDetector(_ViTPoseHooks, TableDetector):
@@ -423,6 +475,7 @@ class ViTPoseTableDetector(_ViTPoseHooks, TableDetector):
         _lib.require_gpu()
         sd, res = _load_table_checkpoint(model_name)
         self._init_hub(vitpose.ViTPoseNet(sd, in_ch=3, out_ch=13, resolution=res, max_batch=max_batch, dtype=dtype), res, max_batch)
+        self._keep_head(sd)
 
 
 class UpliftingModel:

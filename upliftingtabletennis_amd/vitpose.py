@@ -107,6 +107,20 @@ class ViTPoseNet:
             _lib.check(rc)
         return heat, idx, win
 
+    def features(self, x):
+        """x (B, in_ch, H, W) float -> (B * tokens, 384) float32: the backbone alone, last_norm's output -- what the keypoint head's
+        deconvolutions read (`vitpose_head.ViTPoseHead.forward`), bit-equal to the 'ln' tap.  Runs in micro-batches; an f32 handle only."""
+        if self.dtype != 'f32':
+            raise ValueError("features needs an f32 handle: a %s handle keeps last_norm's output in %s" % (self.dtype, self.dtype))
+        if x.dim() != 4 or x.shape[1] != self.IN_CH or x.shape[2] != self.H or x.shape[3] != self.W:
+            raise ValueError('expected input (B,%d,%d,%d), got %s' % (self.IN_CH, self.H, self.W, tuple(x.shape)))
+        x = x.to(self.device, torch.float32).contiguous()
+        out = torch.empty((x.shape[0] * (self.H // 16) * (self.W // 16), 384), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            rc = self._lib.ttup_vitpose_features(self._handle, _lib.ptr(x), x.shape[0], _lib.ptr(out), _lib.stream_ptr())
+        _lib.check(rc)
+        return out
+
     def run_stage(self, stage, x):
         """The testing seam: one stage alone.  Stage 0: the patch embedding of x (B, in_ch, H, W); 1..12: that block on the float32
         residual stream x (B * tokens, 384); 13: the head on a residual stream.  B is at most the micro-batch; `read_tap` then
