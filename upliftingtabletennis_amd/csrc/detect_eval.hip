@@ -12,24 +12,27 @@
 // exp(-dx^2 / 2s^2) * exp(-dy^2 / 2s^2): factor_kernel evaluates the out_h + out_w factors of a map once, in fp64, and the
 // product is rounded once to fp32 as the reference's torch.tensor(heatmap, dtype=float32) rounds its exp.
 //
-// LDS: a strip of r output rows lies between at most min(span, 2 r) source rows, span = y1(last row) - y0(first row) + 1.  When
-// span <= 2 r (every upsampling, and downsampling by less than 2) the rows y0(first) .. y1(last) are kept in order and slot = y -
-// y0(first); otherwise (strong downsampling, the rows are far apart) row i of the strip keeps its own pair in slots 2 i, 2 i + 1.
-// loss_plan() walks the strips with the kernel's own fp64 expressions and picks the largest strip height <= DE_STRIP whose slots
-// fit DE_ROW_BYTES, so a workgroup never needs more than 60 KB and 2 .. 30 workgroups share a CU's 160 KB: WASB (704, 1280) ->
+// LDS: which source rows a strip keeps, and in which slot, is decided without a device in csrc/detect_loss_plan.h (the coordinate
+// itself is csrc/detect_grad_plan.h's dg_src_coord): the kernel's fill loop and its reads call those functions, and loss_plan()
+// walks the strips with them and picks the largest strip height <= DE_STRIP whose slots fit DE_ROW_BYTES
+// (tests/test_detect_loss_plan_host.py holds the three together on the CPU), so a workgroup never needs more than 60 KB and
+// 2 .. 30 workgroups share a CU's 160 KB: WASB (704, 1280) ->
 // 8 rows x 5 KB = 40 KB, 4 workgroups (16 waves) per CU; ViTPose (160, 288) -> 4 rows x 1.1 KB.  Within a wave the 64 lanes read
 // 64 neighbouring output columns: when upsampling these are <= 64 consecutive floats of one LDS row (no bank is hit by two
 // different addresses), lanes that share a source column are served by the broadcast.
 //
 // Sums: thread (columns in order, rows in order) -> xor butterfly over the wave -> the block's 4 waves in order (one partial per
 // strip, in the workspace) -> final kernel: one block per map, thread i adds the partials i, i + 256, ... in order, then a
-// 256-leaf tree in LDS.  No floating-point atomics: two calls return the same bits.  The metric kernels use the same tree.
+// 256-leaf tree in LDS.  No floating-point atomics: two calls return the same bits.  The metric kernels use the same tree; it is
+// written once, in csrc/eval_reduce.h.
 //
 // The gradient of that loss into the predicted heatmaps (ttup_detect_heatmap_loss_grad) is grad_kernel, described where it stands;
 // what it decides without a device is csrc/detect_grad_plan.h.
 #include "no_packed_fp32_begin.h"
 #include "common.h"
 #include "detect_grad_plan.h"
+#include "detect_loss_plan.h"
+#include "eval_reduce.h"
 
 #include <math.h>
 
@@ -39,10 +42,8 @@ using namespace ttup;
 
 namespace {
 
-constexpr int DE_THREADS = 256;
+constexpr int DE_THREADS = ER_THREADS;
 constexpr int DE_WAVES = DE_THREADS / 64;
-constexpr int DE_STRIP = 8;                              // output rows per workgroup, at most
-constexpr size_t DE_ROW_BYTES = 60 * 1024;               // LDS for the source rows of a strip (dynamic); the static part is < 1 KB
 constexpr int DE_MAX_TOL = TTUP_DETECT_MAX_TOLERANCES;
 constexpr int DE_SUMS = 2;                               // metric kernels: sums per call
 constexpr int DE_COUNTS = 3 + DE_MAX_TOL;                // ... counts per call, at most
@@ -53,41 +54,6 @@ struct Tolerances {
     double v[DE_MAX_TOL];
     int n;
 };
-
-// torch's upsample_bilinear2d, align_corners = False, no antialiasing: source coordinate of the output index dst, clamped at 0;
-// i1 clamped at the last row / column.  scale = in / out.  Host and device evaluate the same three IEEE operations.
-__host__ __device__ inline void src_coord(int dst, double scale, int in, int& i0, int& i1, double& lam) {
-    double s = ((double)dst + 0.5) * scale - 0.5;
-    if (s < 0.0) s = 0.0;
-    i0 = (int)s;
-    if (i0 > in - 1) i0 = in - 1;                        // (unreachable: s < in - 0.5; keeps every index in bounds whatever scale is)
-    i1 = i0 < in - 1 ? i0 + 1 : i0;
-    lam = s - (double)i0;
-}
-
-// the LDS slots a strip of nr rows from r0 needs (the kernel's rule, restated for loss_plan)
-__host__ __device__ inline int strip_slots(int r0, int nr, double scale, int in, int& ylo, bool& contiguous) {
-    int a, b;
-    double lam;
-    src_coord(r0, scale, in, ylo, b, lam);
-    int yhi;
-    src_coord(r0 + nr - 1, scale, in, a, yhi, lam);
-    const int span = yhi - ylo + 1;
-    contiguous = span <= 2 * nr;
-    return contiguous ? span : 2 * nr;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    return v;
-}
 
 // fac (maps, out_h + out_w): the row factors exp(-(y - cy)^2 / 2 sigma^2), then the column factors; zeros for a map without target
 __global__ __launch_bounds__(DE_THREADS) void factor_kernel(const double* __restrict__ centres, const int* __restrict__ has_target, int out_h, int out_w, int blocks_per_map,
@@ -112,29 +78,20 @@ __global__ __launch_bounds__(DE_THREADS) void loss_kernel(const float* __restric
     const int tid = ttup_tid_x();
     const int map = ttup_bid_x() / nstrips, r0 = (ttup_bid_x() % nstrips) * strip;
     const int nr = out_h - r0 < strip ? out_h - r0 : strip;
-    int ylo;
-    bool contiguous;
-    const int slots = strip_slots(r0, nr, scale_y, h, ylo, contiguous);
+    const LossStrip ls = dl_strip(r0, nr, scale_y, h);
     const double* f = fac + (size_t)map * (out_h + out_w);
     if (tid < nr) {
         int i0, i1;
         double lam;
-        src_coord(r0 + tid, scale_y, h, i0, i1, lam);
+        dg_src_coord(r0 + tid, scale_y, h, i0, i1, lam);
         s_ly[tid] = lam;
-        s_a[tid] = contiguous ? i0 - ylo : 2 * tid;
-        s_b[tid] = contiguous ? i1 - ylo : 2 * tid + 1;
+        s_a[tid] = dl_slot(ls, tid, 0, i0);
+        s_b[tid] = dl_slot(ls, tid, 1, i1);
         s_gy[tid] = f[r0 + tid];
     }
     const float* src = pred + (size_t)map * h * w;
-    for (int s = 0; s < slots; ++s) {
-        int y = ylo + s;
-        if (!contiguous) {
-            int i0, i1;
-            double lam;
-            src_coord(r0 + (s >> 1), scale_y, h, i0, i1, lam);
-            y = (s & 1) ? i1 : i0;
-        }
-        const float* g = src + (size_t)y * w;
+    for (int s = 0; s < ls.slots; ++s) {
+        const float* g = src + (size_t)dl_slot_row(ls, r0, s, scale_y, h) * w;
         float* l = rows + (size_t)s * w;
         for (int x = tid; x < w; x += DE_THREADS) l[x] = g[x];
     }
@@ -144,7 +101,7 @@ __global__ __launch_bounds__(DE_THREADS) void loss_kernel(const float* __restric
     for (int c = tid; c < out_w; c += DE_THREADS) {
         int x0, x1;
         double lx;
-        src_coord(c, scale_x, w, x0, x1, lx);
+        dg_src_coord(c, scale_x, w, x0, x1, lx);
         const double wx0 = 1.0 - lx, gx = gxp[c];
         for (int i = 0; i < nr; ++i) {
             const float* ra = rows + (size_t)s_a[i] * w;
@@ -160,7 +117,7 @@ __global__ __launch_bounds__(DE_THREADS) void loss_kernel(const float* __restric
             acc = acc + q;
         }
     }
-    acc = wave_sum(acc);
+    acc = lanes_sum<64>(acc);
     if ((tid & 63) == 0) s_red[tid >> 6] = acc;
     __syncthreads();
     if (tid == 0) {
@@ -173,17 +130,8 @@ __global__ __launch_bounds__(DE_THREADS) void loss_kernel(const float* __restric
 // one block per map: its strips' partials in fixed order
 __global__ __launch_bounds__(DE_THREADS) void loss_final_kernel(const double* __restrict__ partial, int nstrips, double* __restrict__ sums) {
     __shared__ double sd[DE_THREADS];
-    const int tid = ttup_tid_x();
-    const double* p = partial + (size_t)ttup_bid_x() * nstrips;
-    double acc = 0.0;
-    for (int i = tid; i < nstrips; i += DE_THREADS) acc = acc + p[i];
-    sd[tid] = acc;
-    __syncthreads();
-    for (int off = DE_THREADS / 2; off >= 1; off >>= 1) {
-        if (tid < off) sd[tid] = sd[tid] + sd[tid + off];
-        __syncthreads();
-    }
-    if (tid == 0) sums[ttup_bid_x()] = sd[0];
+    const double s = block_tree_sum(partial + (size_t)ttup_bid_x() * nstrips, nstrips, sd);
+    if (ttup_tid_x() == 0) sums[ttup_bid_x()] = s;
 }
 
 // ---- the gradient of the heatmap loss into pred: grad = scale * sum_y sum_x 2 w (up - t) a_y(i) b_x(j)
@@ -284,25 +232,15 @@ __device__ __forceinline__ void block_partials(const double (&s)[DE_SUMS], const
     __shared__ int sc[DE_COUNTS][DE_WAVES];
     const int tid = ttup_tid_x(), wave = tid >> 6;
     for (int k = 0; k < DE_SUMS; ++k) {
-        const double v = wave_sum(s[k]);
+        const double v = lanes_sum<64>(s[k]);
         if ((tid & 63) == 0) sm[k][wave] = v;
     }
     for (int k = 0; k < DE_COUNTS; ++k) {
-        const int v = wave_sum(c[k]);
+        const int v = lanes_sum<64>(c[k]);
         if ((tid & 63) == 0) sc[k][wave] = v;
     }
     __syncthreads();
-    const long long blk = ttup_bid_x();
-    if (tid < DE_SUMS) {
-        double v = 0.0;
-        for (int k = 0; k < DE_WAVES; ++k) v = v + sm[tid][k];
-        psum[(long long)tid * nblocks + blk] = v;
-    } else if (tid >= 64 && tid < 64 + ncounts) {
-        const int q = tid - 64;
-        int v = 0;
-        for (int k = 0; k < DE_WAVES; ++k) v += sc[q][k];
-        pcnt[(long long)q * nblocks + blk] = v;
-    }
+    store_block_partials(sm, sc, ncounts, nblocks, psum, pcnt);
 }
 
 // sums: 0 distance to gt  1 distance to the streak as val() measures it, both over the visible samples with a detection (x, y > -100)
@@ -358,52 +296,6 @@ __global__ __launch_bounds__(DE_THREADS) void table_metrics_kernel(const float* 
     block_partials(s, c, 3 + tol.n, nblocks, psum, pcnt);
 }
 
-// one block per quantity (DE_SUMS + ncounts blocks): its per-block partials in fixed order; counts[ncounts] = n
-__global__ __launch_bounds__(DE_THREADS) void metrics_final_kernel(const double* __restrict__ psum, const int* __restrict__ pcnt, long long nblocks, int ncounts, long long n,
-                                                                    double* __restrict__ sums, long long* __restrict__ counts) {
-    __shared__ double sd[DE_THREADS];
-    __shared__ long long sl[DE_THREADS];
-    const int tid = ttup_tid_x(), q = ttup_bid_x();
-    if (q < DE_SUMS) {
-        double acc = 0.0;
-        for (long long i = tid; i < nblocks; i += DE_THREADS) acc = acc + psum[(long long)q * nblocks + i];
-        sd[tid] = acc;
-        __syncthreads();
-        for (int off = DE_THREADS / 2; off >= 1; off >>= 1) {
-            if (tid < off) sd[tid] = sd[tid] + sd[tid + off];
-            __syncthreads();
-        }
-        if (tid == 0) sums[q] = sd[0];
-    } else {
-        const int c = q - DE_SUMS;
-        long long acc = 0;
-        for (long long i = tid; i < nblocks; i += DE_THREADS) acc += pcnt[(long long)c * nblocks + i];
-        sl[tid] = acc;
-        __syncthreads();
-        for (int off = DE_THREADS / 2; off >= 1; off >>= 1) {
-            if (tid < off) sl[tid] += sl[tid + off];
-            __syncthreads();
-        }
-        if (tid == 0) counts[c] = sl[0];
-    }
-    if (q == 0 && tid == 0) counts[ncounts] = n;
-}
-
-// the largest strip height whose source rows fit DE_ROW_BYTES -> (strip, slots); strip = 0 when two rows do not fit
-void loss_plan(int h, int w, int out_h, int& strip, int& slots) {
-    const double scale = (double)h / (double)out_h;
-    for (strip = DE_STRIP; strip >= 1; --strip) {
-        slots = 0;
-        for (int r0 = 0; r0 < out_h; r0 += strip) {
-            int ylo;
-            bool contiguous;
-            const int s = strip_slots(r0, out_h - r0 < strip ? out_h - r0 : strip, scale, h, ylo, contiguous);
-            slots = s > slots ? s : slots;
-        }
-        if ((size_t)slots * w * sizeof(float) <= DE_ROW_BYTES) return;
-    }
-}
-
 long long metric_blocks(long long n) { return (n + DE_THREADS - 1) / DE_THREADS; }
 size_t metrics_workspace_bytes(long long n) { return n > 0 ? (size_t)metric_blocks(n) * (DE_SUMS * sizeof(double) + DE_COUNTS * sizeof(int)) : 0; }
 // the factors of every map, then one partial per map and strip (out_h strips at most: strip height 1)
@@ -419,12 +311,66 @@ int check_tolerances(const char* who, const double* tol, int ntol, Tolerances& t
     return TTUP_OK;
 }
 
-int check_metrics(const char* who, long long n, const void* ws, size_t ws_bytes) {
-    TTUP_REQUIRE(n > 0, TTUP_EINVAL, "%s: need at least one sample, got n = %lld", who, n);
-    TTUP_REQUIRE(((size_t)ws & 7) == 0, TTUP_EINVAL, "%s: the workspace must be 8-byte aligned", who);
-    TTUP_REQUIRE(ws_bytes >= metrics_workspace_bytes(n), TTUP_EINVAL, "%s: workspace of %zu bytes, need %zu (ttup_detect_metrics_workspace_bytes)", who, ws_bytes,
-                 metrics_workspace_bytes(n));
+// what ttup_detect_heatmap_loss and ttup_detect_heatmap_loss_grad (with_grad) share: the checks, both plans, the workspace, the
+// factors, the loss pass (the gradient entry skips it when sums_dev is null) and the gradient pass on the same factors
+int heatmap_loss_pass(const char* who, bool with_grad, const float* pred_dev, const double* centres_dev, const int* has_target_dev, int n, int c, int h, int w, double sigma,
+                      int out_h, int out_w, int weighted, double scale, void* workspace_dev, size_t workspace_bytes, double* sums_dev, float* grad_dev, void* stream) {
+    TTUP_REQUIRE(pred_dev && centres_dev && has_target_dev && workspace_dev && (with_grad ? grad_dev != nullptr : sums_dev != nullptr), TTUP_EINVAL, "%s: null pointer", who);
+    TTUP_REQUIRE(n > 0 && c > 0, TTUP_EINVAL, "%s: need at least one sample and one channel, got n = %d, c = %d", who, n, c);
+    TTUP_REQUIRE(h > 0 && w > 0 && out_h > 0 && out_w > 0, TTUP_EINVAL, "%s: empty heatmap or output: (%d, %d) -> (%d, %d)", who, h, w, out_h, out_w);
+    TTUP_REQUIRE(sigma > 0.0, TTUP_EINVAL, "%s: sigma must be positive, got %g", who, sigma);          // (a NaN fails the comparison too)
+    if (with_grad) TTUP_REQUIRE(isfinite(scale), TTUP_EINVAL, "%s: scale must be finite, got %g", who, scale);
+    const long long maps = (long long)n * c;
+    const LossPlan lp = loss_plan(h, w, out_h);          // the loss pass's limit holds for the pair, whether the sums are asked for or not
+    TTUP_REQUIRE(lp.strip >= 1, TTUP_EINVAL, "%s: two source rows of %d floats do not fit the %zu bytes of LDS %s keeps them in (w <= %zu)", who, w, DE_ROW_BYTES,
+                 with_grad ? "the loss pass" : "a workgroup", DE_ROW_BYTES / (2 * sizeof(float)));
+    const GradPlan gp = with_grad ? dg_plan(h, w, out_h, out_w) : GradPlan();
+    const int fblocks = (out_h + out_w + DE_THREADS - 1) / DE_THREADS;
+    if (with_grad) {
+        TTUP_REQUIRE(gp.strip >= 1 && gp.waves <= DG_MAX_WAVES && gp.lds <= DG_LDS_BYTES, TTUP_EINVAL, "%s: no plan for (%d, %d) -> (%d, %d)", who, h, w, out_h, out_w);
+        TTUP_REQUIRE(maps * lp.nstrips <= 0x7fffffffLL && maps * fblocks <= 0x7fffffffLL && maps * gp.nstrips * gp.groups <= 0x7fffffffLL, TTUP_EINVAL, "%s: %lld maps exceed the grid", who, maps);
+    } else {
+        TTUP_REQUIRE(maps * lp.nstrips <= 0x7fffffffLL && maps * fblocks <= 0x7fffffffLL, TTUP_EINVAL, "%s: %lld maps of %d strips exceed the grid", who, maps, lp.nstrips);
+    }
+    TTUP_REQUIRE(((size_t)workspace_dev & 7) == 0, TTUP_EINVAL, "%s: the workspace must be 8-byte aligned", who);
+    TTUP_REQUIRE(workspace_bytes >= loss_workspace_bytes(maps, out_h, out_w), TTUP_EINVAL, "%s: workspace of %zu bytes, need %zu (%s)", who, workspace_bytes,
+                 loss_workspace_bytes(maps, out_h, out_w), with_grad ? "ttup_detect_loss_grad_workspace_bytes" : "ttup_detect_loss_workspace_bytes");
+    double* fac = (double*)workspace_dev;
+    double* partial = fac + (size_t)maps * (out_h + out_w);
+    const double scale_y = (double)h / (double)out_h, scale_x = (double)w / (double)out_w;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(factor_kernel, dim3((unsigned)(maps * fblocks)), dim3(DE_THREADS), 0, st, centres_dev, has_target_dev, out_h, out_w, fblocks, 2.0 * sigma * sigma, fac);
+    TTUP_LAUNCH_CHECK();
+    if (sums_dev) {
+        hipLaunchKernelGGL(loss_kernel, dim3((unsigned)(maps * lp.nstrips)), dim3(DE_THREADS), lp.lds, st, pred_dev, (const double*)fac, h, w, out_h, out_w, scale_y, scale_x,
+                           lp.strip, lp.nstrips, weighted ? 1 : 0, partial);
+        TTUP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(loss_final_kernel, dim3((unsigned)maps), dim3(DE_THREADS), 0, st, (const double*)partial, lp.nstrips, sums_dev);
+        TTUP_LAUNCH_CHECK();
+    }
+    if (with_grad) {
+        hipLaunchKernelGGL(grad_kernel, dim3((unsigned)(maps * gp.nstrips * gp.groups)), dim3(gp.waves * 64), gp.lds, st, pred_dev, (const double*)fac, h, w, out_h, out_w,
+                           scale_y, scale_x, gp.strip, gp.nstrips, gp.waves, gp.groups, weighted ? 1 : 0, scale, grad_dev);
+        TTUP_LAUNCH_CHECK();
+    }
     return TTUP_OK;
+}
+
+// what the two metrics entries share once they know their item count: the workspace, the launch of their kernel (`launch`: nblocks,
+// partials, stream -> the hipLaunchKernelGGL of that kernel) and the final reduction
+template <typename Launch>
+int metrics_pass(const char* who, long long n, const Tolerances& tol, void* workspace_dev, size_t workspace_bytes, double* sums_dev, long long* counts_dev, void* stream,
+                 Launch launch) {
+    TTUP_REQUIRE(n > 0, TTUP_EINVAL, "%s: need at least one sample, got n = %lld", who, n);
+    TTUP_REQUIRE(((size_t)workspace_dev & 7) == 0, TTUP_EINVAL, "%s: the workspace must be 8-byte aligned", who);
+    TTUP_REQUIRE(workspace_bytes >= metrics_workspace_bytes(n), TTUP_EINVAL, "%s: workspace of %zu bytes, need %zu (ttup_detect_metrics_workspace_bytes)", who, workspace_bytes,
+                 metrics_workspace_bytes(n));
+    const long long nb = metric_blocks(n);
+    const EvalPartials p = eval_partials(workspace_dev, nb, DE_SUMS);
+    hipStream_t st = (hipStream_t)stream;
+    launch(nb, p, st);
+    TTUP_LAUNCH_CHECK();
+    return eval_finish(p, nb, DE_SUMS, 3 + tol.n, n, sums_dev, counts_dev, st);
 }
 
 }  // namespace
@@ -435,33 +381,8 @@ extern "C" size_t ttup_detect_metrics_workspace_bytes(int n_items) { return metr
 
 extern "C" int ttup_detect_heatmap_loss(const float* pred_dev, const double* centres_dev, const int* has_target_dev, int n, int c, int h, int w, double sigma, int out_h,
                                         int out_w, int weighted, void* workspace_dev, size_t workspace_bytes, double* sums_dev, void* stream) {
-    const char* who = "ttup_detect_heatmap_loss";
-    TTUP_REQUIRE(pred_dev && centres_dev && has_target_dev && workspace_dev && sums_dev, TTUP_EINVAL, "%s: null pointer", who);
-    TTUP_REQUIRE(n > 0 && c > 0, TTUP_EINVAL, "%s: need at least one sample and one channel, got n = %d, c = %d", who, n, c);
-    TTUP_REQUIRE(h > 0 && w > 0 && out_h > 0 && out_w > 0, TTUP_EINVAL, "%s: empty heatmap or output: (%d, %d) -> (%d, %d)", who, h, w, out_h, out_w);
-    TTUP_REQUIRE(sigma > 0.0, TTUP_EINVAL, "%s: sigma must be positive, got %g", who, sigma);          // (a NaN fails the comparison too)
-    const long long maps = (long long)n * c;
-    int strip, slots;
-    loss_plan(h, w, out_h, strip, slots);
-    TTUP_REQUIRE(strip >= 1, TTUP_EINVAL, "%s: two source rows of %d floats do not fit the %zu bytes of LDS a workgroup keeps them in (w <= %zu)", who, w, DE_ROW_BYTES,
-                 DE_ROW_BYTES / (2 * sizeof(float)));
-    const int nstrips = (out_h + strip - 1) / strip;
-    const int fblocks = (out_h + out_w + DE_THREADS - 1) / DE_THREADS;
-    TTUP_REQUIRE(maps * nstrips <= 0x7fffffffLL && maps * fblocks <= 0x7fffffffLL, TTUP_EINVAL, "%s: %lld maps of %d strips exceed the grid", who, maps, nstrips);
-    TTUP_REQUIRE(((size_t)workspace_dev & 7) == 0, TTUP_EINVAL, "%s: the workspace must be 8-byte aligned", who);
-    TTUP_REQUIRE(workspace_bytes >= loss_workspace_bytes(maps, out_h, out_w), TTUP_EINVAL, "%s: workspace of %zu bytes, need %zu (ttup_detect_loss_workspace_bytes)", who,
-                 workspace_bytes, loss_workspace_bytes(maps, out_h, out_w));
-    double* fac = (double*)workspace_dev;
-    double* partial = fac + (size_t)maps * (out_h + out_w);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(factor_kernel, dim3((unsigned)(maps * fblocks)), dim3(DE_THREADS), 0, st, centres_dev, has_target_dev, out_h, out_w, fblocks, 2.0 * sigma * sigma, fac);
-    TTUP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(loss_kernel, dim3((unsigned)(maps * nstrips)), dim3(DE_THREADS), (size_t)slots * w * sizeof(float), st, pred_dev, (const double*)fac, h, w, out_h, out_w,
-                       (double)h / (double)out_h, (double)w / (double)out_w, strip, nstrips, weighted ? 1 : 0, partial);
-    TTUP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(loss_final_kernel, dim3((unsigned)maps), dim3(DE_THREADS), 0, st, (const double*)partial, nstrips, sums_dev);
-    TTUP_LAUNCH_CHECK();
-    return TTUP_OK;
+    return heatmap_loss_pass("ttup_detect_heatmap_loss", false, pred_dev, centres_dev, has_target_dev, n, c, h, w, sigma, out_h, out_w, weighted, 0.0, workspace_dev,
+                             workspace_bytes, sums_dev, nullptr, stream);
 }
 
 extern "C" size_t ttup_detect_loss_grad_workspace_bytes(int n_maps, int h, int w, int out_h, int out_w) {
@@ -471,42 +392,8 @@ extern "C" size_t ttup_detect_loss_grad_workspace_bytes(int n_maps, int h, int w
 extern "C" int ttup_detect_heatmap_loss_grad(const float* pred_dev, const double* centres_dev, const int* has_target_dev, int n, int c, int h, int w, double sigma, int out_h,
                                              int out_w, int weighted, double scale, void* workspace_dev, size_t workspace_bytes, double* sums_dev, float* grad_dev,
                                              void* stream) {
-    const char* who = "ttup_detect_heatmap_loss_grad";
-    TTUP_REQUIRE(pred_dev && centres_dev && has_target_dev && workspace_dev && grad_dev, TTUP_EINVAL, "%s: null pointer", who);
-    TTUP_REQUIRE(n > 0 && c > 0, TTUP_EINVAL, "%s: need at least one sample and one channel, got n = %d, c = %d", who, n, c);
-    TTUP_REQUIRE(h > 0 && w > 0 && out_h > 0 && out_w > 0, TTUP_EINVAL, "%s: empty heatmap or output: (%d, %d) -> (%d, %d)", who, h, w, out_h, out_w);
-    TTUP_REQUIRE(sigma > 0.0, TTUP_EINVAL, "%s: sigma must be positive, got %g", who, sigma);
-    TTUP_REQUIRE(isfinite(scale), TTUP_EINVAL, "%s: scale must be finite, got %g", who, scale);
-    const long long maps = (long long)n * c;
-    const GradPlan plan = dg_plan(h, w, out_h, out_w);
-    int strip, slots;
-    loss_plan(h, w, out_h, strip, slots);          // the loss pass's limit holds for the pair, whether the sums are asked for or not
-    TTUP_REQUIRE(strip >= 1, TTUP_EINVAL, "%s: two source rows of %d floats do not fit the %zu bytes of LDS the loss pass keeps them in (w <= %zu)", who, w, DE_ROW_BYTES,
-                 DE_ROW_BYTES / (2 * sizeof(float)));
-    TTUP_REQUIRE(plan.strip >= 1 && plan.waves <= DG_MAX_WAVES && plan.lds <= DG_LDS_BYTES, TTUP_EINVAL, "%s: no plan for (%d, %d) -> (%d, %d)", who, h, w, out_h, out_w);
-    const int nstrips = (out_h + strip - 1) / strip;
-    const int fblocks = (out_h + out_w + DE_THREADS - 1) / DE_THREADS;
-    TTUP_REQUIRE(maps * nstrips <= 0x7fffffffLL && maps * fblocks <= 0x7fffffffLL && maps * plan.nstrips * plan.groups <= 0x7fffffffLL, TTUP_EINVAL, "%s: %lld maps exceed the grid", who, maps);
-    TTUP_REQUIRE(((size_t)workspace_dev & 7) == 0, TTUP_EINVAL, "%s: the workspace must be 8-byte aligned", who);
-    TTUP_REQUIRE(workspace_bytes >= loss_workspace_bytes(maps, out_h, out_w), TTUP_EINVAL, "%s: workspace of %zu bytes, need %zu (ttup_detect_loss_grad_workspace_bytes)", who,
-                 workspace_bytes, loss_workspace_bytes(maps, out_h, out_w));
-    double* fac = (double*)workspace_dev;
-    double* partial = fac + (size_t)maps * (out_h + out_w);
-    const double scale_y = (double)h / (double)out_h, scale_x = (double)w / (double)out_w;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(factor_kernel, dim3((unsigned)(maps * fblocks)), dim3(DE_THREADS), 0, st, centres_dev, has_target_dev, out_h, out_w, fblocks, 2.0 * sigma * sigma, fac);
-    TTUP_LAUNCH_CHECK();
-    if (sums_dev) {          // the loss pass's own launches on the same factors: the sums ttup_detect_heatmap_loss writes
-        hipLaunchKernelGGL(loss_kernel, dim3((unsigned)(maps * nstrips)), dim3(DE_THREADS), (size_t)slots * w * sizeof(float), st, pred_dev, (const double*)fac, h, w, out_h,
-                           out_w, scale_y, scale_x, strip, nstrips, weighted ? 1 : 0, partial);
-        TTUP_LAUNCH_CHECK();
-        hipLaunchKernelGGL(loss_final_kernel, dim3((unsigned)maps), dim3(DE_THREADS), 0, st, (const double*)partial, nstrips, sums_dev);
-        TTUP_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(grad_kernel, dim3((unsigned)(maps * plan.nstrips * plan.groups)), dim3(plan.waves * 64), plan.lds, st, pred_dev, (const double*)fac, h, w, out_h, out_w,
-                       scale_y, scale_x, plan.strip, plan.nstrips, plan.waves, plan.groups, weighted ? 1 : 0, scale, grad_dev);
-    TTUP_LAUNCH_CHECK();
-    return TTUP_OK;
+    return heatmap_loss_pass("ttup_detect_heatmap_loss_grad", true, pred_dev, centres_dev, has_target_dev, n, c, h, w, sigma, out_h, out_w, weighted, scale, workspace_dev,
+                             workspace_bytes, sums_dev, grad_dev, stream);
 }
 
 extern "C" int ttup_detect_ball_metrics(const float* pred_pos_dev, const float* gt_dev, const float* gt_min_dev, const float* gt_max_dev, const int* vis_dev, int n,
@@ -516,17 +403,10 @@ extern "C" int ttup_detect_ball_metrics(const float* pred_pos_dev, const float* 
     TTUP_REQUIRE(pred_pos_dev && gt_dev && gt_min_dev && gt_max_dev && vis_dev && workspace_dev && sums_dev && counts_dev, TTUP_EINVAL, "%s: null pointer", who);
     Tolerances tol;
     if (int rc = check_tolerances(who, tolerances, n_tolerances, tol)) return rc;
-    if (int rc = check_metrics(who, n, workspace_dev, workspace_bytes)) return rc;
-    const long long nb = metric_blocks(n);
-    double* psum = (double*)workspace_dev;
-    int* pcnt = (int*)(psum + nb * DE_SUMS);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(ball_metrics_kernel, dim3((unsigned)nb), dim3(DE_THREADS), 0, st, pred_pos_dev, gt_dev, gt_min_dev, gt_max_dev, vis_dev, (long long)n, tol, nb, psum, pcnt);
-    TTUP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(metrics_final_kernel, dim3(DE_SUMS + 3 + tol.n), dim3(DE_THREADS), 0, st, (const double*)psum, (const int*)pcnt, nb, 3 + tol.n, (long long)n, sums_dev,
-                       counts_dev);
-    TTUP_LAUNCH_CHECK();
-    return TTUP_OK;
+    return metrics_pass(who, n, tol, workspace_dev, workspace_bytes, sums_dev, counts_dev, stream, [&](long long nb, const EvalPartials& p, hipStream_t st) {
+        hipLaunchKernelGGL(ball_metrics_kernel, dim3((unsigned)nb), dim3(DE_THREADS), 0, st, pred_pos_dev, gt_dev, gt_min_dev, gt_max_dev, vis_dev, (long long)n, tol, nb, p.psum,
+                           p.pcnt);
+    });
 }
 
 extern "C" int ttup_detect_table_metrics(const float* pred_pos_dev, const float* gt_dev, int n, int keypoints, const double* tolerances, int n_tolerances,
@@ -538,17 +418,9 @@ extern "C" int ttup_detect_table_metrics(const float* pred_pos_dev, const float*
     TTUP_REQUIRE(n > 0 && keypoints > 0, TTUP_EINVAL, "%s: need at least one sample and one keypoint, got n = %d, keypoints = %d", who, n, keypoints);
     const long long items = (long long)n * keypoints;
     TTUP_REQUIRE(items <= 0x7fffffffLL, TTUP_EINVAL, "%s: %lld keypoints exceed 2^31 - 1", who, items);
-    if (int rc = check_metrics(who, items, workspace_dev, workspace_bytes)) return rc;
-    const long long nb = metric_blocks(items);
-    double* psum = (double*)workspace_dev;
-    int* pcnt = (int*)(psum + nb * DE_SUMS);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(table_metrics_kernel, dim3((unsigned)nb), dim3(DE_THREADS), 0, st, pred_pos_dev, gt_dev, items, tol, nb, psum, pcnt);
-    TTUP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(metrics_final_kernel, dim3(DE_SUMS + 3 + tol.n), dim3(DE_THREADS), 0, st, (const double*)psum, (const int*)pcnt, nb, 3 + tol.n, items, sums_dev,
-                       counts_dev);
-    TTUP_LAUNCH_CHECK();
-    return TTUP_OK;
+    return metrics_pass(who, items, tol, workspace_dev, workspace_bytes, sums_dev, counts_dev, stream, [&](long long nb, const EvalPartials& p, hipStream_t st) {
+        hipLaunchKernelGGL(table_metrics_kernel, dim3((unsigned)nb), dim3(DE_THREADS), 0, st, pred_pos_dev, gt_dev, items, tol, nb, p.psum, p.pcnt);
+    });
 }
 
 #include "no_packed_fp32_end.h"

@@ -27,8 +27,8 @@ constexpr int DG_LANES = 63;                      // source columns a wave owns:
 constexpr int DG_MAX_WAVES = 8;                   // waves per workgroup, at most
 constexpr size_t DG_LDS_BYTES = 60 * 1024;        // dynamic LDS of a workgroup, at most (there is no static part): 10 rows of 506 floats are 20 KB
 
-// torch's upsample_bilinear2d, align_corners = False, no antialiasing (the three IEEE operations of csrc/detect_eval.hip's src_coord):
-// scale = in / out
+// torch's upsample_bilinear2d, align_corners = False, no antialiasing; scale = in / out.  The coordinate lives here alone: the loss
+// pass (csrc/detect_eval.hip's loss_kernel, csrc/detect_loss_plan.h) reads it through dg_src_coord as the gradient does.
 // the clamped source coordinate of dst: an add, a multiply and a subtract, each rounded -- never an fma, on the device as on the
 // host (the pragma stands inside the body, as in mt19937.h, so that a unit that includes this header keeps its own setting).
 // This is the one place the coordinate is written: the ranges, the weights and the kernel's inner loop all come through it.
@@ -41,10 +41,11 @@ TTUP_HD inline double dg_coord(int dst, double scale) {
 // lambda of an output index whose lower source index is known to be i0 (the kernel's inner loop: i0 comes from dg_first's ranges)
 TTUP_HD inline double dg_lambda(int dst, double scale, int i0) { return dg_coord(dst, scale) - (double)i0; }
 
+// the source indices dst interpolates between and its lambda: i0 = floor of the coordinate, i1 clamped at the last index
 TTUP_HD inline void dg_src_coord(int dst, double scale, int in, int& i0, int& i1, double& lam) {
     const double s = dg_coord(dst, scale);
     i0 = (int)s;
-    if (i0 > in - 1) i0 = in - 1;
+    if (i0 > in - 1) i0 = in - 1;                        // (unreachable: s < in - 0.5; keeps every index in bounds whatever scale is)
     i1 = i0 < in - 1 ? i0 + 1 : i0;
     lam = s - (double)i0;
 }

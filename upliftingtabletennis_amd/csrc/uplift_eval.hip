@@ -11,7 +11,8 @@
 // Sums: a fixed tree that depends on N and T alone, no floating-point atomics, so two calls return the same bits --
 //   per lane over its time steps in order -> xor butterfly over the sample's 16 lanes -> the block's 16 samples in order
 //   (one partial per block and quantity, in the workspace) -> eval_final_kernel: one block per quantity, thread i adds the
-//   partials i, i + 256, ... in order, then a 256-leaf tree in LDS.
+//   partials i, i + 256, ... in order, then a 256-leaf tree in LDS.  The butterfly, the partials and the final kernel are
+//   csrc/eval_reduce.h's, shared with csrc/detect_eval.hip.
 //
 // Where this differs from the reference, on purpose:
 //   * a time step with mask == 0 is selected out, not multiplied by 0: a non-finite value in a masked slot is inert (val_real's
@@ -22,6 +23,7 @@
 //     of its local spin are NaN and component 2 is not, exactly as helper.py:411-418 leaves them.
 #include "no_packed_fp32_begin.h"
 #include "common.h"
+#include "eval_reduce.h"
 
 #include <math.h>
 
@@ -31,7 +33,7 @@ using namespace ttup;
 
 namespace {
 
-constexpr int EV_THREADS = 256;                          // threads per block of all three kernels
+constexpr int EV_THREADS = ER_THREADS;                       // threads per block of all three kernels
 constexpr int EV_LANES = 16;                             // lanes per sample
 constexpr int EV_SAMPLES = EV_THREADS / EV_LANES;        // samples per block
 constexpr int VAL_SUMS = 8, VAL_COUNTS = 12;             // ttup_uplift_val_metrics: sums_dev / counts_dev (without N)
@@ -39,11 +41,7 @@ constexpr int REAL_SUMS = 1, REAL_COUNTS = 4;            // ttup_uplift_val_real
 constexpr double IMG_WIDTH = 2560.0, IMG_HEIGHT = 1440.0;          // uplifting/helper.py:26
 constexpr int TOPSPIN_CLASS = 1, BACKSPIN_CLASS = 2;     // uplifting/data.py
 
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-    for (int off = EV_LANES / 2; off >= 1; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    return v;
-}
+__device__ __forceinline__ double group_sum(double v) { return lanes_sum<EV_LANES>(v); }          // over a sample's lanes
 
 // transform_rotationaxes (uplifting/helper.py:394-420) in fp64: e_x = (ex, ey, 0), e_y = e_z x e_x = (-ey, ex, 0), e_z = (0, 0, 1)
 __device__ __forceinline__ void local_spin(const float* __restrict__ rot, const float* __restrict__ pos, double w[3]) {
@@ -54,24 +52,6 @@ __device__ __forceinline__ void local_spin(const float* __restrict__ rot, const 
     w[0] = r0 * ex + r1 * ey;
     w[1] = r1 * ex - r0 * ey;
     w[2] = r2;
-}
-
-// the block's EV_SAMPLES per-sample values of each quantity, added in sample order -> one partial per block and quantity
-template <int NS, int NC>
-__device__ __forceinline__ void block_partials(const double (&sm)[NS][EV_SAMPLES], const int (&sc)[NC][EV_SAMPLES], long long nblocks, double* __restrict__ psum,
-                                               int* __restrict__ pcnt) {
-    const int tid = ttup_tid_x();
-    const long long blk = ttup_bid_x();
-    if (tid < NS) {
-        double s = 0.0;
-        for (int j = 0; j < EV_SAMPLES; ++j) s = s + sm[tid][j];
-        psum[(long long)tid * nblocks + blk] = s;
-    } else if (tid >= 64 && tid < 64 + NC) {
-        const int q = tid - 64;
-        int s = 0;
-        for (int j = 0; j < EV_SAMPLES; ++j) s += sc[q][j];
-        pcnt[(long long)q * nblocks + blk] = s;
-    }
 }
 
 // sums (per block): 0 ||d||  1 |dx|  2 |dy|  3 |dz|  4 | ||pred|| - ||gt|| |  5 angle [deg]  6 masked mean position error  7 ||d||^2
@@ -133,7 +113,7 @@ __global__ __launch_bounds__(EV_THREADS) void val_kernel(const float* __restrict
         for (int k = 0; k < VAL_COUNTS; ++k) sc[k][g] = c[k];
     }
     __syncthreads();
-    block_partials<VAL_SUMS, VAL_COUNTS>(sm, sc, nblocks, psum, pcnt);
+    store_block_partials(sm, sc, VAL_COUNTS, nblocks, psum, pcnt);          // the block's samples in order
 }
 
 // sums: 0 masked mean of the 2-D distance [px].  counts: TP TN FP FN (train.py:265-276).  scores[b]: local spin component 1;
@@ -199,38 +179,7 @@ __global__ __launch_bounds__(EV_THREADS) void val_real_kernel(const float* __res
         for (int k = 0; k < REAL_COUNTS; ++k) sc[k][g] = c[k];
     }
     __syncthreads();
-    block_partials<REAL_SUMS, REAL_COUNTS>(sm, sc, nblocks, psum, pcnt);
-}
-
-// one block per quantity (nsums + ncounts blocks): its per-block partials in fixed order; counts[ncounts] = n
-__global__ __launch_bounds__(EV_THREADS) void eval_final_kernel(const double* __restrict__ psum, const int* __restrict__ pcnt, long long nblocks, int nsums, int ncounts,
-                                                                 long long n, double* __restrict__ sums, long long* __restrict__ counts) {
-    __shared__ double sd[EV_THREADS];
-    __shared__ long long sl[EV_THREADS];
-    const int tid = ttup_tid_x(), q = ttup_bid_x();
-    if (q < nsums) {
-        double acc = 0.0;
-        for (long long i = tid; i < nblocks; i += EV_THREADS) acc = acc + psum[(long long)q * nblocks + i];
-        sd[tid] = acc;
-        __syncthreads();
-        for (int off = EV_THREADS / 2; off >= 1; off >>= 1) {
-            if (tid < off) sd[tid] = sd[tid] + sd[tid + off];
-            __syncthreads();
-        }
-        if (tid == 0) sums[q] = sd[0];
-    } else {
-        const int c = q - nsums;
-        long long acc = 0;
-        for (long long i = tid; i < nblocks; i += EV_THREADS) acc += pcnt[(long long)c * nblocks + i];
-        sl[tid] = acc;
-        __syncthreads();
-        for (int off = EV_THREADS / 2; off >= 1; off >>= 1) {
-            if (tid < off) sl[tid] += sl[tid + off];
-            __syncthreads();
-        }
-        if (tid == 0) counts[c] = sl[0];
-    }
-    if (q == 0 && tid == 0) counts[ncounts] = n;
+    store_block_partials(sm, sc, REAL_COUNTS, nblocks, psum, pcnt);
 }
 
 long long eval_blocks(long long n) { return (n + EV_SAMPLES - 1) / EV_SAMPLES; }
@@ -258,16 +207,12 @@ extern "C" int ttup_uplift_val_metrics(const float* pred_rot_dev, const float* p
                  "ttup_uplift_val_metrics: null pointer");
     if (int rc = check_common("ttup_uplift_val_metrics", n, t, workspace_dev, workspace_bytes)) return rc;
     const long long nb = eval_blocks(n);
-    double* psum = (double*)workspace_dev;
-    int* pcnt = (int*)(psum + nb * VAL_SUMS);
+    const EvalPartials p = eval_partials(workspace_dev, nb, VAL_SUMS);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(val_kernel, dim3((unsigned)nb), dim3(EV_THREADS), 0, st, pred_rot_dev, pred_pos_dev, r_world_dev, rotation_dev, mask_dev, (long long)n, t,
-                       transform_global ? 1 : 0, nb, psum, pcnt);
+                       transform_global ? 1 : 0, nb, p.psum, p.pcnt);
     TTUP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(eval_final_kernel, dim3(VAL_SUMS + VAL_COUNTS), dim3(EV_THREADS), 0, st, (const double*)psum, (const int*)pcnt, nb, VAL_SUMS, VAL_COUNTS, (long long)n, sums_dev,
-                       counts_dev);
-    TTUP_LAUNCH_CHECK();
-    return TTUP_OK;
+    return eval_finish(p, nb, VAL_SUMS, VAL_COUNTS, n, sums_dev, counts_dev, st);
 }
 
 extern "C" int ttup_uplift_val_real_metrics(const float* pred_rot_dev, const float* pred_pos_dev, const float* r_img_dev, const float* mask_dev, const float* mint_dev,
@@ -278,16 +223,12 @@ extern "C" int ttup_uplift_val_real_metrics(const float* pred_rot_dev, const flo
                  TTUP_EINVAL, "ttup_uplift_val_real_metrics: null pointer");
     if (int rc = check_common("ttup_uplift_val_real_metrics", n, t, workspace_dev, workspace_bytes)) return rc;
     const long long nb = eval_blocks(n);
-    double* psum = (double*)workspace_dev;
-    int* pcnt = (int*)(psum + nb * REAL_SUMS);
+    const EvalPartials p = eval_partials(workspace_dev, nb, REAL_SUMS);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(val_real_kernel, dim3((unsigned)nb), dim3(EV_THREADS), 0, st, pred_rot_dev, pred_pos_dev, r_img_dev, mask_dev, mint_dev, mext_dev, spin_class_dev,
-                       (long long)n, t, transform_global ? 1 : 0, nb, psum, pcnt, scores_dev, labels_dev);
+                       (long long)n, t, transform_global ? 1 : 0, nb, p.psum, p.pcnt, scores_dev, labels_dev);
     TTUP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(eval_final_kernel, dim3(REAL_SUMS + REAL_COUNTS), dim3(EV_THREADS), 0, st, (const double*)psum, (const int*)pcnt, nb, REAL_SUMS, REAL_COUNTS, (long long)n, sums_dev,
-                       counts_dev);
-    TTUP_LAUNCH_CHECK();
-    return TTUP_OK;
+    return eval_finish(p, nb, REAL_SUMS, REAL_COUNTS, n, sums_dev, counts_dev, st);
 }
 
 #include "no_packed_fp32_end.h"

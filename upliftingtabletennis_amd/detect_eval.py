@@ -58,9 +58,9 @@ def _workspace(nbytes, dev):
     return torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=dev)
 
 
-def heatmap_loss_device(pred, centres, has_target, sigma=6, weighted=False, size=(HEIGHT, WIDTH)):
-    """-> (N, C) float64 device tensor: per (sample, channel) the sum over the size[0] x size[1] output pixels of
-    w (up(pred) - target)^2 (see `heatmap_loss`).  Enqueued on the current stream; nothing synchronises."""
+def _heatmap_loss_call(pred, centres, has_target, sigma, weighted, size, scale=None, want_grad=False):
+    """What `heatmap_loss_device` and `heatmap_loss_grad_device` (want_grad) share: the operands on pred's device, the shape checks,
+    the workspace and the call -> (sums (N, C) float64, grad (N, C, h, w) float32 or None)."""
     _lib.require_gpu()
     lib = _lib.load()
     dev = _device_of(pred)
@@ -74,13 +74,27 @@ def heatmap_loss_device(pred, centres, has_target, sigma=6, weighted=False, size
         raise ValueError('centres must have shape (N, C, 2) and has_target (N, C) for pred %s, got %s and %s'
                          % (tuple(pred.shape), tuple(centres.shape), tuple(has_target.shape)))
     out_h, out_w = int(size[0]), int(size[1])
+    if want_grad and scale is None:
+        scale = 1.0 / (n * c * out_h * out_w)
     sums = torch.empty((n, c), dtype=torch.float64, device=dev)
+    grad = torch.empty((n, c, h, w), dtype=torch.float32, device=dev) if want_grad else None
+    head = (_lib.ptr(pred), _lib.ptr(centres), _lib.ptr(has_target), n, c, h, w, float(sigma), out_h, out_w, 1 if weighted else 0)
     with torch.cuda.device(dev):
-        nbytes = int(lib.ttup_detect_loss_workspace_bytes(n * c, out_h, out_w))
-        ws = _workspace(nbytes, dev)
-        _lib.check(lib.ttup_detect_heatmap_loss(_lib.ptr(pred), _lib.ptr(centres), _lib.ptr(has_target), n, c, h, w, float(sigma), out_h, out_w,
-                                                1 if weighted else 0, _lib.ptr(ws), nbytes, _lib.ptr(sums), _lib.stream_ptr()))
-    return sums
+        if want_grad:
+            nbytes = int(lib.ttup_detect_loss_grad_workspace_bytes(n * c, h, w, out_h, out_w))
+            ws = _workspace(nbytes, dev)
+            _lib.check(lib.ttup_detect_heatmap_loss_grad(*head, float(scale), _lib.ptr(ws), nbytes, _lib.ptr(sums), _lib.ptr(grad), _lib.stream_ptr()))
+        else:
+            nbytes = int(lib.ttup_detect_loss_workspace_bytes(n * c, out_h, out_w))
+            ws = _workspace(nbytes, dev)
+            _lib.check(lib.ttup_detect_heatmap_loss(*head, _lib.ptr(ws), nbytes, _lib.ptr(sums), _lib.stream_ptr()))
+    return sums, grad
+
+
+def heatmap_loss_device(pred, centres, has_target, sigma=6, weighted=False, size=(HEIGHT, WIDTH)):
+    """-> (N, C) float64 device tensor: per (sample, channel) the sum over the size[0] x size[1] output pixels of
+    w (up(pred) - target)^2 (see `heatmap_loss`).  Enqueued on the current stream; nothing synchronises."""
+    return _heatmap_loss_call(pred, centres, has_target, sigma, weighted, size)[0]
 
 
 def loss_from_sums(sums, size=(HEIGHT, WIDTH), batch_size=None):
@@ -116,29 +130,7 @@ def heatmap_loss_grad_device(pred, centres, has_target, sigma=6, weighted=True, 
     of scale * sums.sum() with respect to pred (csrc/detect_eval.hip grad_kernel).  scale=None: 1 / (N C size[0]
     size[1]), the element mean -- the reference's loss.backward() into the network's output.  Enqueued on the current stream;
     nothing synchronises."""
-    _lib.require_gpu()
-    lib = _lib.load()
-    dev = _device_of(pred)
-    pred = _to(pred, dev, torch.float32)
-    if pred.dim() != 4:
-        raise ValueError('pred must have shape (N, C, h, w), got %s' % (tuple(pred.shape),))
-    n, c, h, w = pred.shape
-    centres = _to(centres, dev, torch.float64)
-    has_target = _to(has_target, dev, torch.int32)
-    if tuple(centres.shape) != (n, c, 2) or tuple(has_target.shape) != (n, c):
-        raise ValueError('centres must have shape (N, C, 2) and has_target (N, C) for pred %s, got %s and %s'
-                         % (tuple(pred.shape), tuple(centres.shape), tuple(has_target.shape)))
-    out_h, out_w = int(size[0]), int(size[1])
-    if scale is None:
-        scale = 1.0 / (n * c * out_h * out_w)
-    sums = torch.empty((n, c), dtype=torch.float64, device=dev)
-    grad = torch.empty((n, c, h, w), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        nbytes = int(lib.ttup_detect_loss_grad_workspace_bytes(n * c, h, w, out_h, out_w))
-        ws = _workspace(nbytes, dev)
-        _lib.check(lib.ttup_detect_heatmap_loss_grad(_lib.ptr(pred), _lib.ptr(centres), _lib.ptr(has_target), n, c, h, w, float(sigma), out_h, out_w,
-                                                     1 if weighted else 0, float(scale), _lib.ptr(ws), nbytes, _lib.ptr(sums), _lib.ptr(grad), _lib.stream_ptr()))
-    return sums, grad
+    return _heatmap_loss_call(pred, centres, has_target, sigma, weighted, size, scale, want_grad=True)
 
 
 def heatmap_loss_grad(pred, centres, has_target, sigma=6, weighted=True, size=(HEIGHT, WIDTH), scale=None):
@@ -150,9 +142,22 @@ def heatmap_loss_grad(pred, centres, has_target, sigma=6, weighted=True, size=(H
     return loss_from_sums(sums.cpu().numpy(), size), grad
 
 
+def _metrics_call(entry, tolerances, n_items, operands, dev):
+    """What the two metrics wrappers share: the results, the workspace for n_items items and the call `entry(*operands, tolerances,
+    workspace, results, stream)` -> (sums float64 (2,), counts int64 (4 + len(tolerances),)) on `dev`."""
+    tol, ctol = tolerances
+    sums = torch.empty((2,), dtype=torch.float64, device=dev)
+    counts = torch.empty((4 + len(tol),), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        nbytes = int(_lib.load().ttup_detect_metrics_workspace_bytes(n_items))
+        ws = _workspace(nbytes, dev)
+        _lib.check(entry(*operands, ctol, len(tol), _lib.ptr(ws), nbytes, _lib.ptr(sums), _lib.ptr(counts), _lib.stream_ptr()))
+    return sums, counts
+
+
 def ball_metrics_device(pred_pos, gt_pos, gt_min, gt_max, vis, tolerances=(2, 5, 10)):
     """-> (sums float64 (2,), counts int64 (4 + len(tolerances),)) on the device, as ttup_detect_ball_metrics lays them out."""
-    tol, ctol = _tolerances(tolerances)
+    tolerances = _tolerances(tolerances)
     _lib.require_gpu()
     lib = _lib.load()
     dev = _device_of(pred_pos, gt_pos)
@@ -162,19 +167,12 @@ def ball_metrics_device(pred_pos, gt_pos, gt_min, gt_max, vis, tolerances=(2, 5,
     n = pred.shape[0]
     if pred.dim() != 2 or pred.shape[1] != 3 or any(tuple(a.shape) != (n, 2) for a in (gt, lo, hi)) or tuple(vis.shape) != (n,):
         raise ValueError('pred_pos must have shape (N, 3), gt_pos / gt_min / gt_max (N, 2) and vis (N,)')
-    sums = torch.empty((2,), dtype=torch.float64, device=dev)
-    counts = torch.empty((4 + len(tol),), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        nbytes = int(lib.ttup_detect_metrics_workspace_bytes(n))
-        ws = _workspace(nbytes, dev)
-        _lib.check(lib.ttup_detect_ball_metrics(_lib.ptr(pred), _lib.ptr(gt), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(vis), n, ctol, len(tol), _lib.ptr(ws), nbytes,
-                                                _lib.ptr(sums), _lib.ptr(counts), _lib.stream_ptr()))
-    return sums, counts
+    return _metrics_call(lib.ttup_detect_ball_metrics, tolerances, n, (_lib.ptr(pred), _lib.ptr(gt), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(vis), n), dev)
 
 
 def table_metrics_device(pred_pos, gt_pos, tolerances=(2, 5, 10)):
     """-> (sums float64 (2,), counts int64 (4 + len(tolerances),)) on the device, as ttup_detect_table_metrics lays them out."""
-    tol, ctol = _tolerances(tolerances)
+    tolerances = _tolerances(tolerances)
     _lib.require_gpu()
     lib = _lib.load()
     dev = _device_of(pred_pos, gt_pos)
@@ -182,14 +180,7 @@ def table_metrics_device(pred_pos, gt_pos, tolerances=(2, 5, 10)):
     if pred.dim() != 3 or pred.shape[2] != 3 or pred.shape != gt.shape:
         raise ValueError('pred_pos and gt_pos must both have shape (N, K, 3), got %s and %s' % (tuple(pred.shape), tuple(gt.shape)))
     n, k, _ = pred.shape
-    sums = torch.empty((2,), dtype=torch.float64, device=dev)
-    counts = torch.empty((4 + len(tol),), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        nbytes = int(lib.ttup_detect_metrics_workspace_bytes(n * k))
-        ws = _workspace(nbytes, dev)
-        _lib.check(lib.ttup_detect_table_metrics(_lib.ptr(pred), _lib.ptr(gt), n, k, ctol, len(tol), _lib.ptr(ws), nbytes, _lib.ptr(sums), _lib.ptr(counts),
-                                                 _lib.stream_ptr()))
-    return sums, counts
+    return _metrics_call(lib.ttup_detect_table_metrics, tolerances, n * k, (_lib.ptr(pred), _lib.ptr(gt), n, k), dev)
 
 
 def _ratio(num, den):

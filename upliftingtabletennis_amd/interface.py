@@ -195,6 +195,56 @@ class _HubDetector:
             return set()
         return self.cert.settle(calls, frames_u8, audit=audit, rerun=lambda c: self.cert.run(frames_u8[c.f0:c.f1]))
 
+    # `val`, `heatmap_loss_grad` and `head_loss_and_grad` of both detectors, over the two hooks BallDetector and TableDetector provide:
+    #   _net_input(images)            the network input of a run of images (ball: triples; table: frames)
+    #   _targets(n, *annotations)     the annotations of n images -> (centres (n,C,2) float64, has_target (n,C) int32)
+
+    def _chunks(self, images, centres, has):
+        """The forward in chunks of `max_batch` -> per chunk (`_certified_forward` of its input, its centres, its has_target)."""
+        for b0 in range(0, len(images), self.max_batch):
+            b1 = min(len(images), b0 + self.max_batch)
+            yield self._certified_forward(self._net_input(images[b0:b1])), centres[b0:b1], has[b0:b1]
+
+    def _val(self, images, annotations, sigma, weighted, variant, tolerances, batch_size, finish, metrics):
+        """`val`: per chunk the peaks refined with `variant` and the loss sums, both kept on the device; then `metrics(positions)` ->
+        device (sums, counts), one read-back, and `finish` for the ratios."""
+        centres, has = self._targets(len(images), *annotations)
+        pos, sums = [], []
+        for (heat, idx, win), c, t in self._chunks(images, centres, has):
+            pos.append(self.refine_peaks_as(idx, win, variant))
+            sums.append(detect_eval.heatmap_loss_device(heat, c, t, sigma, weighted, (HEIGHT, WIDTH)))
+        if not pos:
+            raise ValueError('need at least one sample')
+        loss_sums = torch.cat(sums)
+        msums, counts = metrics(torch.cat(pos))
+        msums, counts, loss_sums = detect_eval.read_back(msums, counts, loss_sums)
+        out = finish(msums, counts, [float(t) for t in tolerances])
+        out.update(loss=detect_eval.loss_from_sums(loss_sums, (HEIGHT, WIDTH), batch_size), loss_sums=loss_sums)
+        return out
+
+    def _heatmap_loss_grad(self, images, annotations, sigma, size, weighted):
+        """`heatmap_loss_grad`: per chunk the loss sums and the gradient, with the whole batch's scale."""
+        n = len(images)
+        centres, has = self._targets(n, *annotations)
+        scale = 1.0 / (max(n, 1) * has.shape[1] * int(size[0]) * int(size[1]))
+        sums, grads = [], []
+        for (heat, _, _), c, t in self._chunks(images, centres, has):
+            s, g = detect_eval.heatmap_loss_grad_device(heat, c, t, sigma, weighted, size, scale)
+            sums.append(s)
+            grads.append(g)
+        if not sums:
+            raise ValueError('need at least one sample')
+        return detect_eval.loss_from_sums(torch.cat(sums).cpu().numpy(), size), torch.cat(grads)
+
+    def _head_loss_and_grad(self, images, annotations, sigma, size, weighted, train):
+        """`head_loss_and_grad`: the whole batch in one call (one BatchNorm over it)."""
+        self._head_pass_check()
+        n = len(images)
+        centres, has = self._targets(n, *annotations)
+        if not n:
+            raise ValueError('need at least one sample')
+        return self._head_pass(self._net_input(images), centres, has, sigma, size, weighted, 1.0 / (n * has.shape[1] * int(size[0]) * int(size[1])), train)
+
 
 class BallDetector(_HubDetector):
     def __new__(cls, model_name='segformerpp_b2', *a, **k):
@@ -224,6 +274,13 @@ class BallDetector(_HubDetector):
             return np.zeros((0, 3)), np.zeros((0, 1) + self.heat_hw, np.float32)
         return np.concatenate(pred_pos, axis=0), np.concatenate(preds, axis=0)
 
+    def _net_input(self, images):
+        return torch.cat([wasb.preprocess_triples(self._upload(imgs), self.model_resolution) for imgs in images])
+
+    def _targets(self, n, ball_coords, vis):
+        centres = np.asarray(ball_coords, np.float64).reshape(n, 1, 2)
+        return centres, (np.asarray(vis).reshape(n) != detect_eval.BALL_INVISIBLE).astype(np.int32).reshape(n, 1)
+
     def val(self, images, ball_coords, min_coords, max_coords, vis, sigma=6, refine='ball', tolerances=(2, 5, 10), batch_size=None):
         """The reference's ball val() (balldetection/train.py:144-245) on this detector.  images: list (length B) of [prev, curr, next]
         BGR uint8 HWC arrays, as `predict` takes them; ball_coords / min_coords / max_coords (B,2) annotations in 1920x1080 px (the
@@ -236,26 +293,8 @@ class BallDetector(_HubDetector):
         Gaussian of `sigma` px around ball_coords (zeros where vis is BALL_INVISIBLE, as the TTHQ loader builds them); batch_size:
         the loader's batch size, whose per-batch means val() averages (None: one batch)."""
         variant = detect_eval.refine_variant(refine)
-        n = len(images)
-        centres = np.asarray(ball_coords, np.float64).reshape(n, 1, 2)
-        vis = np.asarray(vis).reshape(n)
-        has = (vis != detect_eval.BALL_INVISIBLE).astype(np.int32).reshape(n, 1)
-        w, h = self.model_resolution
-        pos, sums = [], []
-        for b0 in range(0, n, self.max_batch):
-            b1 = min(n, b0 + self.max_batch)
-            xs = [wasb.preprocess_triples(self._upload(imgs), (w, h)) for imgs in images[b0:b1]]
-            heat, idx, win = self._certified_forward(torch.cat(xs))
-            pos.append(self.refine_peaks_as(idx, win, variant))
-            sums.append(detect_eval.heatmap_loss_device(heat, centres[b0:b1], has[b0:b1], sigma, False, (HEIGHT, WIDTH)))
-        if not pos:
-            raise ValueError('need at least one sample')
-        loss_sums = torch.cat(sums)
-        msums, counts = detect_eval.ball_metrics_device(torch.cat(pos), ball_coords, min_coords, max_coords, vis, tolerances)
-        msums, counts, loss_sums = detect_eval.read_back(msums, counts, loss_sums)
-        out = detect_eval.finish_ball(msums, counts, [float(t) for t in tolerances])
-        out.update(loss=detect_eval.loss_from_sums(loss_sums, (HEIGHT, WIDTH), batch_size), loss_sums=loss_sums)
-        return out
+        return self._val(images, (ball_coords, vis), sigma, False, variant, tolerances, batch_size, detect_eval.finish_ball,
+                         lambda pos: detect_eval.ball_metrics_device(pos, ball_coords, min_coords, max_coords, np.asarray(vis).reshape(len(images)), tolerances))
 
     def heatmap_loss_grad(self, images, ball_coords, vis, sigma=6, size=(HEIGHT, WIDTH), weighted=True):
         """The reference's ball training loss (balldetection/train.py:112-113: weighted_mse_loss after F.interpolate to `size`;
@@ -263,22 +302,7 @@ class BallDetector(_HubDetector):
         images, ball_coords, vis as `val` takes them.  -> (loss: the element mean over the whole batch, grad (B,1,H,W) float32
         device tensor, shaped like the heatmaps: d loss / d heatmap).  The forward runs in the chunks `val` runs; no heatmap goes
         to the host."""
-        n = len(images)
-        centres = np.asarray(ball_coords, np.float64).reshape(n, 1, 2)
-        has = (np.asarray(vis).reshape(n) != detect_eval.BALL_INVISIBLE).astype(np.int32).reshape(n, 1)
-        w, h = self.model_resolution
-        scale = 1.0 / (max(n, 1) * int(size[0]) * int(size[1]))
-        sums, grads = [], []
-        for b0 in range(0, n, self.max_batch):
-            b1 = min(n, b0 + self.max_batch)
-            xs = [wasb.preprocess_triples(self._upload(imgs), (w, h)) for imgs in images[b0:b1]]
-            heat = self._certified_forward(torch.cat(xs))[0]
-            s, g = detect_eval.heatmap_loss_grad_device(heat, centres[b0:b1], has[b0:b1], sigma, weighted, size, scale)
-            sums.append(s)
-            grads.append(g)
-        if not sums:
-            raise ValueError('need at least one sample')
-        return detect_eval.loss_from_sums(torch.cat(sums).cpu().numpy(), size), torch.cat(grads)
+        return self._heatmap_loss_grad(images, (ball_coords, vis), sigma, size, weighted)
 
     def head_loss_and_grad(self, images, ball_coords, vis, sigma=6, size=(HEIGHT, WIDTH), weighted=True, train=True):
         """`heatmap_loss_grad` carried on through the keypoint head: the backbone's features, the head's
@@ -286,14 +310,7 @@ class BallDetector(_HubDetector):
         into the heatmaps and the head's backward.  -> (loss, {reference key: gradient} of the head's eight parameters, dfeat
         (B * tokens, 384): the gradient into last_norm's output).  Works on a copy of the detector's head parameters: the
         detector itself is unchanged.  ViTPose / f32 only."""
-        self._head_pass_check()
-        n = len(images)
-        centres = np.asarray(ball_coords, np.float64).reshape(n, 1, 2)
-        has = (np.asarray(vis).reshape(n) != detect_eval.BALL_INVISIBLE).astype(np.int32).reshape(n, 1)
-        if not n:
-            raise ValueError('need at least one sample')
-        x = torch.cat([wasb.preprocess_triples(self._upload(imgs), self.model_resolution) for imgs in images])
-        return self._head_pass(x, centres, has, sigma, size, weighted, 1.0 / (n * int(size[0]) * int(size[1])), train)
+        return self._head_loss_and_grad(images, (ball_coords, vis), sigma, size, weighted, train)
 
     def predict_clip(self, images):
         """Fast path for consecutive frames (what TableTennisPipeline.predict feeds the detector, interface.py:276-279):
@@ -345,65 +362,32 @@ class TableDetector(_HubDetector):
             return np.zeros((0, 13, 3)), np.zeros((0, 1, 13) + self.heat_hw, np.float32)
         return np.concatenate(pred_pos, axis=0), np.concatenate(preds, axis=0)
 
+    def _net_input(self, images):
+        return wasb.preprocess_frames(self._upload(images), self.model_resolution)
+
+    def _targets(self, n, table_coords):
+        coords = np.asarray(table_coords, np.float64).reshape(n, 13, 3)
+        return np.ascontiguousarray(coords[:, :, :2]), (coords[:, :, 2] == KEYPOINT_VISIBLE).astype(np.int32)
+
     def val(self, images, table_coords, sigma=6, tolerances=(2, 5, 10), batch_size=None):
         """The reference's table val() (tabledetection/train.py:131-201) on this detector.  images: list (length B) of BGR uint8 HWC
         frames; table_coords (B,13,3) [x, y, visibility] annotations in 1920x1080 px (the loader's integer pixel positions).
         -> {'loss', 'pck@2', 'pck@5', 'pck@10', 'avg_dist', 'ratio_detected', the counts of detect_eval.table_val_metrics,
         'loss_sums' (B,13)}.  Runs like `BallDetector.val`; the loss is val()'s weighted_mse_loss, against zeros for a keypoint
         whose visibility is not KEYPOINT_VISIBLE."""
-        n = len(images)
-        coords = np.asarray(table_coords, np.float64).reshape(n, 13, 3)
-        centres = np.ascontiguousarray(coords[:, :, :2])
-        has = (coords[:, :, 2] == KEYPOINT_VISIBLE).astype(np.int32)
-        pos, sums = [], []
-        for b0 in range(0, n, self.max_batch):
-            b1 = min(n, b0 + self.max_batch)
-            fr = self._upload(images[b0:b1])
-            heat, idx, win = self._certified_forward(wasb.preprocess_frames(fr, self.model_resolution))
-            pos.append(self.refine_peaks(idx, win).reshape(-1, 13, 3))
-            sums.append(detect_eval.heatmap_loss_device(heat, centres[b0:b1], has[b0:b1], sigma, True, (HEIGHT, WIDTH)))
-        if not pos:
-            raise ValueError('need at least one sample')
-        loss_sums = torch.cat(sums)
-        msums, counts = detect_eval.table_metrics_device(torch.cat(pos), coords, tolerances)
-        msums, counts, loss_sums = detect_eval.read_back(msums, counts, loss_sums)
-        out = detect_eval.finish_table(msums, counts, [float(t) for t in tolerances])
-        out.update(loss=detect_eval.loss_from_sums(loss_sums, (HEIGHT, WIDTH), batch_size), loss_sums=loss_sums)
-        return out
+        return self._val(images, (table_coords,), sigma, True, _lib.REFINE_TABLE, tolerances, batch_size, detect_eval.finish_table,
+                         lambda pos: detect_eval.table_metrics_device(pos.reshape(-1, 13, 3), np.asarray(table_coords, np.float64).reshape(len(images), 13, 3), tolerances))
 
     def heatmap_loss_grad(self, images, table_coords, sigma=6, size=(HEIGHT, WIDTH), weighted=True):
         """The reference's table training loss (tabledetection/train.py:106-107) on this detector and its gradient into the
         detector's heatmaps; images and table_coords as `val` takes them.  -> (loss, grad (B,13,H,W) float32 device tensor).  Runs
         like `BallDetector.heatmap_loss_grad`; the target of a keypoint whose visibility is not KEYPOINT_VISIBLE is zeros."""
-        n = len(images)
-        coords = np.asarray(table_coords, np.float64).reshape(n, 13, 3)
-        centres = np.ascontiguousarray(coords[:, :, :2])
-        has = (coords[:, :, 2] == KEYPOINT_VISIBLE).astype(np.int32)
-        scale = 1.0 / (max(n, 1) * 13 * int(size[0]) * int(size[1]))
-        sums, grads = [], []
-        for b0 in range(0, n, self.max_batch):
-            b1 = min(n, b0 + self.max_batch)
-            fr = self._upload(images[b0:b1])
-            heat = self._certified_forward(wasb.preprocess_frames(fr, self.model_resolution))[0]
-            s, g = detect_eval.heatmap_loss_grad_device(heat, centres[b0:b1], has[b0:b1], sigma, weighted, size, scale)
-            sums.append(s)
-            grads.append(g)
-        if not sums:
-            raise ValueError('need at least one sample')
-        return detect_eval.loss_from_sums(torch.cat(sums).cpu().numpy(), size), torch.cat(grads)
+        return self._heatmap_loss_grad(images, (table_coords,), sigma, size, weighted)
 
     def head_loss_and_grad(self, images, table_coords, sigma=6, size=(HEIGHT, WIDTH), weighted=True, train=True):
         """`heatmap_loss_grad` carried on through the keypoint head, like `BallDetector.head_loss_and_grad`.  -> (loss, grads,
         dfeat).  ViTPose / f32 only."""
-        self._head_pass_check()
-        n = len(images)
-        coords = np.asarray(table_coords, np.float64).reshape(n, 13, 3)
-        centres = np.ascontiguousarray(coords[:, :, :2])
-        has = (coords[:, :, 2] == KEYPOINT_VISIBLE).astype(np.int32)
-        if not n:
-            raise ValueError('need at least one sample')
-        x = wasb.preprocess_frames(self._upload(images), self.model_resolution)
-        return self._head_pass(x, centres, has, sigma, size, weighted, 1.0 / (n * 13 * int(size[0]) * int(size[1])), train)
+        return self._head_loss_and_grad(images, (table_coords,), sigma, size, weighted, train)
 
     def predict_keypoints(self, images):
         """`predict` without the heatmaps: (B,13,3) keypoints only.  Pre-processing, CNN, per-channel argmax and windows run
