@@ -291,6 +291,37 @@ int  ttup_vitpose_head_backward(ttup_vitpose_head* head, const float* dheat_dev,
                                 void* stream);
 int  ttup_vitpose_head_read_tap(ttup_vitpose_head* head, const char* tap, void* dst, size_t bytes);
 
+/* ---------------------------------------------------------------- ViTPose backbone: training-mode forward and backward
+ * The ViTPose-small backbone (Conv2d(k16,s16,p2) patch embedding + pos_embed, 12 pre-LN blocks, last_norm) with every block's
+ * activations kept, and its backward.  The 149 tensors stay where the caller keeps them, in the reference's layouts (device
+ * pointers, float32, 16-byte aligned), in the reference's state_dict order: pos_embed, patch_embed.proj.weight / .bias, per block
+ * norm1.weight / .bias, attn.qkv.weight / .bias, attn.proj.weight / .bias, norm2.weight / .bias, mlp.fc1.weight / .bias,
+ * mlp.fc2.weight / .bias, then last_norm.weight / .bias.  The handle owns one workspace (ttup_vitpose_grad_workspace_bytes) sized
+ * for max_batch samples of hp x wp tokens and in_ch in 1..16.
+ * forward: x_dev (batch,in_ch,16hp,16wp) -> feat_dev (batch*hp*wp, 384), last_norm's output.  drop_scale_dev: (12,2,batch) floats,
+ *   the factor on residual branch (block, half) of every sample (stochastic depth: 0 or 1/keep), drop_scale_len its length; null
+ *   and 0: every factor 1, and then feat is ttup_vitpose_features' bit for bit.
+ * backward: dfeat_dev (batch*hp*wp, 384), the batch of the last forward and the same parameters -> the 149 gradients (overwritten,
+ *   the parameters' shapes).  The gradient into the images is not computed.  It may run more than once per forward.  Same inputs,
+ *   same bits: no sum is atomic.
+ * read_tap (testing seam): "x" (block 0..12), "x_mid", "att" (rows,384), "qkv" (rows,1152), "lse" (rows,12), "pre" (rows,1536) of
+ *   block 0..11 of the last forward, and "dqkv" (rows,1152; block 0) of the last backward, to dst (exactly `bytes` long).
+ * TTUP_EINVAL before any device call: null pointers, in_ch outside 1..16, a non-positive grid or batch, more than 2^22 tokens, a
+ *   batch beyond max_batch, a drop_scale of another length than 24 * batch, a backward without a forward or with another batch,
+ *   an unknown tap or a wrong size. */
+#define TTUP_VITPOSE_BACKBONE_TENSORS 149
+typedef struct ttup_vitpose_grad ttup_vitpose_grad;
+typedef struct ttup_vitpose_backbone_params { const float* t[TTUP_VITPOSE_BACKBONE_TENSORS]; } ttup_vitpose_backbone_params;
+typedef struct ttup_vitpose_backbone_grads { float* t[TTUP_VITPOSE_BACKBONE_TENSORS]; } ttup_vitpose_backbone_grads;
+size_t ttup_vitpose_grad_workspace_bytes(int in_ch, int hp, int wp, int max_batch);          /* 0: refused arguments */
+int  ttup_vitpose_grad_create(int in_ch, int hp, int wp, int max_batch, ttup_vitpose_grad** out);
+void ttup_vitpose_grad_destroy(ttup_vitpose_grad* h);
+int  ttup_vitpose_grad_forward(ttup_vitpose_grad* h, const float* x_dev, int batch, const ttup_vitpose_backbone_params* params,
+                               const float* drop_scale_dev, long long drop_scale_len, float* feat_dev, void* stream);
+int  ttup_vitpose_grad_backward(ttup_vitpose_grad* h, const float* dfeat_dev, int batch, const ttup_vitpose_backbone_params* params,
+                                const ttup_vitpose_backbone_grads* grads, void* stream);
+int  ttup_vitpose_grad_read_tap(ttup_vitpose_grad* h, const char* tap, int block, void* dst, size_t bytes);
+
 /* ---------------------------------------------------------------- a3/a4: heatmap argmax + refine
  * Replaces extract_position_torch_gaussian (ball: helper_balldetection.py:29-110, called at
  * inference/utils.py:59; table: helper_tabledetection.py:50-156, called at interface.py:116).

@@ -109,6 +109,12 @@ SIGNATURES = {
     'ttup_vitpose_head_forward': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     'ttup_vitpose_head_backward': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     'ttup_vitpose_head_read_tap': (_i, [_vp, _c.c_char_p, _vp, _sz]),
+    'ttup_vitpose_grad_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'ttup_vitpose_grad_create': (_i, [_i, _i, _i, _i, _c.POINTER(_vp)]),
+    'ttup_vitpose_grad_destroy': (None, [_vp]),
+    'ttup_vitpose_grad_forward': (_i, [_vp, _vp, _i, _vp, _vp, _c.c_longlong, _vp, _vp]),
+    'ttup_vitpose_grad_backward': (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    'ttup_vitpose_grad_read_tap': (_i, [_vp, _c.c_char_p, _i, _vp, _sz]),
     'ttup_dataset_workspace_bytes': (_sz, [_i]),
     'ttup_dataset_seed': (_i, [_vp, _i, _vp, _sz, _vp]),
     'ttup_dataset_draws': (_i, [_vp, _sz, _i, _i, _i, _vp, _vp]),

@@ -20,7 +20,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, calib, detect_eval, glue, inference, refine, uplift, vitpose, vitpose_head, wasb, weights
+from . import _lib, calib, detect_eval, glue, inference, refine, uplift, vitpose, vitpose_backbone, vitpose_head, wasb, weights
 from .detect_eval import ball_val_metrics, heatmap_loss, heatmap_loss_grad, heatmap_loss_grad_device, table_val_metrics  # noqa: F401  (the evaluation functions, beside the detectors they measure)
 
 HEIGHT, WIDTH = 1080, 1920
@@ -236,6 +236,19 @@ class _HubDetector:
             raise ValueError('need at least one sample')
         return detect_eval.loss_from_sums(torch.cat(sums).cpu().numpy(), size), torch.cat(grads)
 
+    def _full_pass_check(self):
+        """`loss_and_grad` exists for the ViTPose detectors alone (theirs is the network whose backward is built)"""
+        raise NotImplementedError('loss_and_grad: only the ViTPose detectors have a backward (DESIGN.md section 30)')
+
+    def _loss_and_grad(self, images, annotations, sigma, size, weighted, train, drop_scale):
+        """`loss_and_grad`: the whole batch in one call (one BatchNorm over it)."""
+        self._full_pass_check()
+        n = len(images)
+        centres, has = self._targets(n, *annotations)
+        if not n:
+            raise ValueError('need at least one sample')
+        return self._full_pass(self._net_input(images), centres, has, sigma, size, weighted, 1.0 / (n * has.shape[1] * int(size[0]) * int(size[1])), train, drop_scale)
+
     def _head_loss_and_grad(self, images, annotations, sigma, size, weighted, train):
         """`head_loss_and_grad`: the whole batch in one call (one BatchNorm over it)."""
         self._head_pass_check()
@@ -311,6 +324,15 @@ class BallDetector(_HubDetector):
         (B * tokens, 384): the gradient into last_norm's output).  Works on a copy of the detector's head parameters: the
         detector itself is unchanged.  ViTPose / f32 only."""
         return self._head_loss_and_grad(images, (ball_coords, vis), sigma, size, weighted, train)
+
+    def loss_and_grad(self, images, ball_coords, vis, sigma=6, size=(HEIGHT, WIDTH), weighted=True, train=True, drop_scale=None):
+        """The ball training loss and the gradient of every parameter of the detector: the backbone's
+        training forward (drop_scale (12, 2, B): the stochastic-depth factor of every residual branch and sample, as
+        `vitpose_backbone.sample_drop_scale` draws them; None: all ones), the head's training-mode forward with the whole batch
+        in one BatchNorm (train=False: the running statistics), the loss's gradient into the heatmaps, the head's backward and
+        the backbone's.  -> (loss, {reference key: gradient} of the 157 parameters: 149 backbone + 8 head).  Works on a copy of
+        the detector's parameters: the detector itself is unchanged.  ViTPose / f32 only."""
+        return self._loss_and_grad(images, (ball_coords, vis), sigma, size, weighted, train, drop_scale)
 
     def predict_clip(self, images):
         """Fast path for consecutive frames (what TableTennisPipeline.predict feeds the detector, interface.py:276-279):
@@ -389,6 +411,11 @@ class TableDetector(_HubDetector):
         dfeat).  ViTPose / f32 only."""
         return self._head_loss_and_grad(images, (table_coords,), sigma, size, weighted, train)
 
+    def loss_and_grad(self, images, table_coords, sigma=6, size=(HEIGHT, WIDTH), weighted=True, train=True, drop_scale=None):
+        """The table training loss and the gradient of every parameter of the detector, like `BallDetector.loss_and_grad`.
+        -> (loss, grads).  ViTPose / f32 only."""
+        return self._loss_and_grad(images, (table_coords,), sigma, size, weighted, train, drop_scale)
+
     def predict_keypoints(self, images):
         """`predict` without the heatmaps: (B,13,3) keypoints only.  Pre-processing, CNN, per-channel argmax and windows run
         fused on the device; nothing but the 39 numbers per frame comes back to the host."""
@@ -423,6 +450,7 @@ class _ViTPoseHooks:
     def _keep_head(self, state_dict):
         """The head's parameters in the reference's layout, for `head_loss_and_grad` (the handle itself holds them BN-folded)"""
         self._head_state = {k: np.array(weights._np(v)) for k, v in state_dict.items() if '.keypoint_head.' in k}
+        self._backbone_state = {k: np.array(weights._np(v)) for k, v in state_dict.items() if '.backbone.' in k}          # for `loss_and_grad`
 
     def _head_pass_check(self):
         if self.model.dtype != 'f32':
@@ -438,6 +466,24 @@ class _ViTPoseHooks:
         sums, grad = detect_eval.heatmap_loss_grad_device(heat, centres, has, sigma, weighted, size, scale)
         grads, dfeat = head.backward(grad)
         return detect_eval.loss_from_sums(sums.cpu().numpy(), size), grads, dfeat
+
+    def _full_pass_check(self):
+        if self.model.dtype != 'f32':
+            raise ValueError("loss_and_grad needs dtype='f32': the training pass is fp32 (a %s handle)" % self.model.dtype)
+
+    def _full_pass(self, x, centres, has, sigma, size, weighted, scale, train, drop_scale):
+        """the backbone's training forward -> the head's (one BN over the whole batch) -> the loss's gradient -> the head's backward ->
+        the backbone's, on a backbone and a head of their own per call: copies of the parameters and workspaces sized for this
+        batch, freed with them"""
+        net = self.model
+        backbone = vitpose_backbone.ViTPoseBackbone(self._backbone_state, net.IN_CH, (net.W, net.H), max_batch=x.shape[0], device=net.device)
+        feat = backbone.forward(x, drop_scale)
+        head = vitpose_head.ViTPoseHead(self._head_state, net.OUT_CH, max_rows=feat.shape[0], device=net.device)
+        heat = head.forward(feat, (net.H // 16, net.W // 16), train=train)
+        sums, grad = detect_eval.heatmap_loss_grad_device(heat, centres, has, sigma, weighted, size, scale)
+        grads, dfeat = head.backward(grad)
+        grads.update(backbone.backward(dfeat))
+        return detect_eval.loss_from_sums(sums.cpu().numpy(), size), grads
 
 
 class ViTPoseBallDetector(_ViTPoseHooks, BallDetector):
