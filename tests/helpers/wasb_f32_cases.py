@@ -98,6 +98,12 @@ CASES = [
     # the ball detector on uint8 frames: preprocess_kernel<float> with three frames per sample, 6 frames of 80x104 resized to 72x104
     # (a real vertical interpolation); planted weights, so the argmax must equal the oracle's
     _case('72x104_frames', 72, 104, 4, kind='frames', seed=77, planted=True),
+    # preprocess_kernel<float> writing NHWC16 at its own edges (source sizes: E.SOURCE_HW): 24x40 frames upscaled to 32x56 -- all four
+    # clamps -- and frames of the network's size (the copy path), with three frames per sample and with one
+    _case('32x56_pre_up_frames', 32, 56, 4, kind='frames', seed=82),
+    _case('32x56_pre_up_table', 32, 56, 3, kind='table', seed=83),
+    _case('32x56_pre_same_frames', 32, 56, 4, kind='frames', seed=84),
+    _case('32x56_pre_same_table', 32, 56, 3, kind='table', seed=85),
 ]
 BY_ID = {c.id: c for c in CASES}
 # the cross-check kernels (each in a process of its own: csrc/conv.hip reads the switches once)
